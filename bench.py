@@ -102,7 +102,13 @@ def parse():
                     help="gmm-train: statistics of the best density only, or of every density by its posterior (reference: mode)")
     ap.add_argument("--gmm-type", default="diagonal-maximum", choices=["diagonal-maximum", "batch-diagonal-maximum-float", "SIMD-diagonal-maximum"])
     ap.add_argument("--gmm-frames", type=int, default=256, help="gmm / gmm-tied: frames per step (config 3: 256)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB: a larger array as a fixed, seeded sample of its rows (DIR/<name>_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: ms_per_step is the time of one timed step")
+    return args
 
 
 def free_port():
@@ -425,6 +431,13 @@ class NnPipeline:
     def epoch_reduce(self, world):
         self.red.all_reduce(comm=getattr(self, "comm", None))   # ONE collective (amx_comm_all_reduce_f64_dev; no-op in a single process)
 
+    def outputs(self):
+        """--dump-outputs: (name, tensor, valid leading rows or None) of what the last step handed its caller; the score buffer holds
+        the last scoring pass, the accumulators the whole run after the epoch reduce"""
+        last = self.F - (self.F - 1) // self.CHUNK * self.CHUNK
+        return [("ceps", self.ceps, None), ("scores", self.scores, last), ("best_state", self.best, None),
+                ("counts", self.counts, None), ("score_sum", self.score_sum, None)]
+
     def roofline(self):
         """The GEMM TEMPLATE of the NN leg (the kernel with the largest summed time of the step): algorithmic flops of all seven layers
         (84.7 MFLOP per frame) over the summed HIP-event time of their launches, against the dense bf16 / f16 matrix peak.
@@ -525,6 +538,11 @@ class Pipeline(NnPipeline):
                 self.gmm.score_stats_dev(x, T, self.gscores, self.gbestd, self.gstate, self.gcounts, self.gscore_sum)
                 self.gmm.accumulate_dev(x, T, self.gstate, self.gbestd, self.M, self.acc)
 
+    def outputs(self):
+        last = self.F - (self.F - 1) // self.GCHUNK * self.GCHUNK
+        return super().outputs() + [("gmm_scores", self.gscores, last), ("gmm_best_density", self.gbestd, last), ("gmm_best_state", self.gstate, last),
+                                    ("gmm_counts", self.gcounts, None), ("gmm_score_sum", self.gscore_sum, None), ("gmm_acc", self.acc, None)]
+
     def nn_leg(self):
         self.ctx.context_window(self.plan, self.ceps, 40, 5, 5, self.ctxwin, 440)
         for t0 in range(0, self.F, self.CHUNK):
@@ -621,6 +639,14 @@ class GmmTrain:
             else:
                 self.sc.accumulate_dev(x, T, self.state, self.bestd, self.M, self.acc)
 
+    def outputs(self):
+        last = self.F - (self.F - 1) // self.CHUNK * self.CHUNK
+        return [("ceps", self.ceps, None)] + self.gmm_outputs(last)
+
+    def gmm_outputs(self, last):
+        return [("scores", self.scores, last), ("best_density", self.bestd, last), ("best_state", self.state, last), ("counts", self.counts, None),
+                ("score_sum", self.score_sum, None), ("acc", self.acc, None)]
+
     def epoch_reduce(self, world):
         self.red.all_reduce(comm=getattr(self, "comm", None))   # ONE collective: 8 * (sum K + n_mean * (1 + d) + n_cov * (1 + d)) bytes = 53.8 MB here (+ counts, score sum)
 
@@ -677,6 +703,9 @@ class GmmTrained(GmmTrain):
     def step(self):
         self.sc.score_stats_dev(self.x, self.F, self.scores, self.bestd, self.state, self.counts, self.score_sum)
         self.sc.accumulate_dev(self.x, self.F, self.state, self.bestd, self.M, self.acc)
+
+    def outputs(self):
+        return self.gmm_outputs(None)
 
     def stage_report(self):
         import torch
@@ -760,6 +789,9 @@ class MfccOnly:
 
     def epoch_reduce(self, world):
         pass
+
+    def outputs(self):
+        return [("ceps", self.ceps, None)]
 
     def roofline(self):
         if self.gt:
@@ -855,6 +887,9 @@ class GmmOnly:
 
     def epoch_reduce(self, world):
         pass
+
+    def outputs(self):
+        return [("scores", self.scores, None)] + ([] if self.gmm_type == "batch-diagonal-maximum-float" else [("best_density", self.best, None)])
 
     def roofline(self):
         # exact-order distance: sub, mul, mul, add per (frame, density, dim) = 4 f32 VALU ops; the f32 vector peak is
@@ -956,6 +991,9 @@ class NnOnly:
     def epoch_reduce(self, world):
         pass
 
+    def outputs(self):
+        return [("scores", self.scores, None)]
+
     def roofline(self):
         ms, n = self.ctx.profile_get("ffnn_gemm_max")
         if n == 0:
@@ -1020,6 +1058,9 @@ class NullJob:
 
     def epoch_reduce(self, world):
         self.red.all_reduce()   # torch.distributed (gloo): the CPU stand-in of amx_comm_all_reduce_f64_dev
+
+    def outputs(self):
+        return [(n, self.red.view(n), None) for n in ("counts", "frames", "score_sum")]
 
     def roofline(self):
         return None
@@ -1370,8 +1411,46 @@ def smi_stretch(job):
     HWMON = smi.report("%d more steps of the same workload (%.1f s) behind the timed region" % (n, time.perf_counter() - t1))
 
 
-def measure(ctx, job, args, world):
-    """W untimed steps, then exactly K steps + the epoch reduce between barrier + synchronize; returns seconds"""
+DUMP_BYTES_PER_ARRAY = 9_000_000   # --dump-outputs: an array above this is written as a seeded sample of its rows
+DUMP_BYTES_TOTAL = 64_000_000
+
+
+def snapshot_outputs(job):
+    """--dump-outputs: host copies of job.outputs(), float32 from floating-point sources of 32 bits or fewer, float64 from f64 and
+    integer ones (exact).  An array above DUMP_BYTES_PER_ARRAY keeps a sample of its rows (along the first axis) drawn with a fixed
+    seed, so the same arguments pick the same rows in every build; their indices go to <name>_rows."""
+    import torch
+    items = job.outputs()
+    if any(t.is_cuda for _, t, _ in items):
+        torch.cuda.synchronize()
+    out = {}
+    for name, t, rows in items:
+        if rows is not None:
+            t = t[:rows]
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        row_bytes = int(np.prod(t.shape[1:], dtype=np.int64)) * (8 if wide else 4)
+        n = int(t.shape[0])
+        if n * row_bytes > DUMP_BYTES_PER_ARRAY:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_PER_ARRAY // row_bytes, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            out[name + "_rows"] = idx.astype(np.float64)
+        out[name] = (t.double() if wide else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES_TOTAL:
+        raise RuntimeError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_BYTES_TOTAL))
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return dict(dir=path, files=sorted(n + ".npy" for n in arrays), bytes=int(sum(a.nbytes for a in arrays.values())))
+
+
+def measure(ctx, job, args, world, dump=False):
+    """W untimed steps, then exactly K steps + the epoch reduce between barrier + synchronize; returns seconds.
+    dump: job.dumped = snapshot_outputs(job), taken behind the timed region and before the profiled pass below runs the steps again"""
     gpu = ctx is not None
     for _ in range(args.warmup):
         job.step()
@@ -1390,6 +1469,8 @@ def measure(ctx, job, args, world):
         # (each frame adds one to its best state's counter in the warm-up and the timed steps alike)
         job.reduced_frames = int(job.counts.sum().item())
         job.expected_frames = int(job.units) * (args.warmup + args.steps) * world
+    if dump:
+        job.dumped = snapshot_outputs(job)
     if gpu:
         # kernel timings (roofline, stages) come from a SECOND pass over the same steps with the per-launch HIP events on (for a
         # graph-replayed workload: with plain launches).  The survivor counter is reset WITH the profiler, so that it covers exactly
@@ -1675,7 +1756,7 @@ def main():
     rank, world, local = dist_setup(args)
     if not gpu:
         job = make_job(None, args, rank, world)
-        dt = measure(None, job, args, world)
+        dt = measure(None, job, args, world, dump=bool(args.dump_outputs) and rank == 0)
         import torch
         if job.walker is not None:
             job.gather_walks()
@@ -1686,13 +1767,14 @@ def main():
         dt = float(t.item())
         if rank == 0:
             units = job.units * args.steps * world   # weak scaling: every rank owns a batch of the same shape
+            dumped = write_outputs(args.dump_outputs, job.dumped) if args.dump_outputs else None
             print(json.dumps({"metric": "stand-in frames/s (host-only launcher check, not the product)", "value": round(units / dt, 1),
                               "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                               "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
                               "vs_baseline": None, "dtype": "none", "data": "synthetic",
                               "config": {"workload": "null (no GPU work)", "backend": "gloo", "ingest": ingest_mode(args, world)},
                               "epoch_reduce": dict(collectives=1, bytes=job.red.nbytes(), backend="gloo (CPU stand-in)"),
-                              "stages": job.stage_report()}))
+                              "stages": job.stage_report(), **({"dump_outputs": dumped} if dumped else {})}))
         if _dist_on():
             import torch.distributed as dist
             dist.barrier()
@@ -1709,7 +1791,8 @@ def main():
         comm = make_comm(ctx, rank, world)
         job = make_job(ctx, args, rank, world)
         job.comm = comm
-        dt = measure(ctx, job, args, world)
+        dt = measure(ctx, job, args, world, dump=bool(args.dump_outputs) and rank == 0)
+    dumped = write_outputs(args.dump_outputs, job.dumped) if args.dump_outputs and rank == 0 else None
     t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if _dist_on():
         import torch.distributed as dist
@@ -1728,6 +1811,9 @@ def main():
                 "data": "synthetic", "config": {"workload": WORKLOAD_NAMES[args.workload](args), "frames_per_step_per_gpu": job.units,
                                                 "contract": CONTRACT_TEXT[args.contract]},
                 "rtf": round(dt / (units * 0.01), 8), "build": rasr_amd.version()}
+        if dumped:
+            line["dump_outputs"] = dumped
+            job.dumped = None
         if getattr(job, "requested_precision", None) and job.requested_precision != getattr(job, "nn_precision", job.requested_precision):
             line["config"]["precision_fallback"] = ("requested %s, the handle computes in %s (amx_ffnn_precision: block-maximum statistic of the weights "
                                                     "above 4.0, tuning mx_fallback=auto)" % (job.requested_precision, job.nn_precision))

@@ -371,7 +371,7 @@ def ref_cache_block(feats, times):
     t = np.ascontiguousarray(times, np.float64)
     cap = x.size * 4 + x.shape[0] * 20 + 64
     buf = C.create_string_buffer(cap)
-    n = R.ref_cache_block_write(x, t.ctypes.data, x.shape[0], x.shape[1], buf, cap)
+    n = R.ref_cache_block_write(x, t.ctypes, x.shape[0], x.shape[1], buf, cap)
     if n < 0:
         raise RuntimeError("ref_cache_block_write failed (%d)" % n)
     return buf.raw[:n]
@@ -383,7 +383,7 @@ def ref_cache_block_parse(data, dim, max_frames):
     x = np.zeros((max_frames, dim), np.float32)
     t = np.zeros((max_frames, 2), np.float64)
     used, name = C.c_long(), C.create_string_buffer(64)
-    n = R.ref_cache_block_read(data, len(data), dim, x.ctypes.data, t.ctypes.data, max_frames, C.byref(used), name, 64)
+    n = R.ref_cache_block_read(data, len(data), dim, x.ctypes, t.ctypes, max_frames, C.byref(used), name, 64)
     if n < 0:
         raise RuntimeError("ref_cache_block_read failed (%d)" % n)
     return x[:n], t[:n], used.value, name.value.decode()
@@ -408,7 +408,7 @@ def ref_accumulate_vector(sum_, v, weight, kind):
     v = np.ascontiguousarray(v, dtype=np.float64 if kind == 4 else np.float32)
     R.ref_accumulate_vector.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int]
     R.ref_accumulate_vector.restype = None
-    R.ref_accumulate_vector(s.ctypes.data, v.ctypes.data, len(s), float(weight), kind)
+    R.ref_accumulate_vector(s.ctypes, v.ctypes, len(s), float(weight), kind)
     return s
 
 
@@ -417,7 +417,7 @@ def ref_log_exp_norm(v):
     v = np.ascontiguousarray(v, dtype=np.float64)
     R.ref_log_exp_norm.argtypes = [C.c_void_p, C.c_int]
     R.ref_log_exp_norm.restype = C.c_double
-    return R.ref_log_exp_norm(v.ctypes.data, len(v))
+    return R.ref_log_exp_norm(v.ctypes, len(v))
 
 
 def ref_normalized_minus(x, y, weight):
@@ -427,7 +427,7 @@ def ref_normalized_minus(x, y, weight):
     out = np.zeros(len(x), np.float32)
     R.ref_normalized_minus.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
     R.ref_normalized_minus.restype = None
-    R.ref_normalized_minus(x.ctypes.data, y.ctypes.data, len(x), float(weight), out.ctypes.data)
+    R.ref_normalized_minus(x.ctypes, y.ctypes, len(x), float(weight), out.ctypes)
     return out
 
 

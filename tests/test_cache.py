@@ -13,6 +13,7 @@ import pytest
 import rasr_amd
 from oracle import cache_format as cf
 from oracle.binding import load_ref
+from tests import ref_replay
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "ref_cache.json")))
@@ -43,9 +44,9 @@ def test_oracle_attribs_match_reference_xml(i):
     assert cf.attribs_xml(a["attrs"]) == a["xml"]
 
 
-def test_oracle_live_against_libref():
-    if load_ref() is None:
-        pytest.skip("reference tree not mounted")
+def test_oracle_live_against_libref(monkeypatch):
+    """the reference's own writer and reader (oracle/_ref, or their recorded answers) on seeded blocks"""
+    R = ref_replay.reference(monkeypatch, "test_cache.oracle_live_against_libref")
     from oracle.binding import ref_attribs_xml, ref_cache_block, ref_cache_block_parse
     rng = np.random.default_rng(5)
     for n, dim in ((7, 33), (64, 40), (2, 1)):
@@ -57,6 +58,7 @@ def test_oracle_live_against_libref():
         assert rx.tobytes() == x.tobytes() and rt.tobytes() == t.tobytes()
     attrs = {"a&b": "<1>", "q": "'\""}
     assert cf.attribs_xml(attrs) == ref_attribs_xml(attrs)
+    ref_replay.finish(R)
 
 
 # ---------------------------------------------------------------- the library writes what the reference writes

@@ -4,7 +4,8 @@ The reference's default configuration (-march=native, GCC's -ffp-contract=fast) 
 other f32 sums into fused multiply-adds; configured with -DMARCH=x86-64 it does not.  oracle/liboracle.so restates the second,
 oracle/liboracle_fma.so the first (orc.h).  Both are held, bit for bit, to
   * tests/golden/ref_contract.npz -- outputs of the reference compiled both ways (tests/golden/make_contract_golden.py), everywhere;
-  * oracle/_ref/libref.so / libref_native.so live on fresh inputs, where the reference tree is mounted (build container).
+  * oracle/_ref/libref.so / libref_native.so live on seeded inputs where the reference tree is mounted, and their recorded answers to the
+    same calls everywhere else (tests/ref_replay.py).
 Function-text pins (oracle/ref/extract_fn.py): a13 / a14 distance, combine rule and log-add scorer, f1 regression, a7 filter apply, a3 Hamming table, a18 batch-float sum, a1 preemphasis, a7 filter builder and boundary, a10 cosine transform, f4 AR-to-cepstrum, the gammatone filter bank and the integration nodes, f1 normalisation, f4 density clustering.
 """
 import ctypes as C
@@ -14,11 +15,10 @@ import numpy as np
 import pytest
 
 from oracle import OracleGmm
-from oracle.binding import CONTRACTS, Oracle, load_ref, oracle_matrix_multiply, oracle_regression
-from tests import synth
+from oracle.binding import CONTRACTS, Oracle, oracle_matrix_multiply, oracle_regression
+from tests import ref_replay, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-HAVE_REF = os.path.isdir("/root/reference/src")
 Z = np.load(os.path.join(GOLD, "ref_contract.npz"))
 DIMS = [40, 39, 33, 32, 24, 16, 7, 3, 45]
 
@@ -398,12 +398,11 @@ def test_scores_of_the_two_builds_differ_by_rounding_only():
     assert np.array_equal(a.argmin(axis=1), b.argmin(axis=1))
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not mounted")
 @pytest.mark.parametrize("contract", CONTRACTS)
-def test_live_against_the_compiled_reference(contract):
-    """fresh random inputs through the reference compiled with this build's flags (oracle/_ref)"""
-    R, L = load_ref(contract), Oracle(contract)
-    assert R is not None and hasattr(R, "ref_gdm_distance")
+def test_live_against_the_compiled_reference(contract, monkeypatch):
+    """seeded random inputs through the reference compiled with this build's flags (oracle/_ref, or its recorded answers)"""
+    R, L = ref_replay.reference(monkeypatch, "test_contract.live_against_the_compiled_reference[%s]" % contract, contract), Oracle(contract)
+    assert hasattr(R, "ref_gdm_distance")
     rng = np.random.default_rng(77)
     for dim in (40, 39, 33, 5):
         for _ in range(300):
@@ -460,3 +459,4 @@ def test_live_against_the_compiled_reference(contract):
             R.ref_batch_float_fill(ms.reshape(-1), cst, nk, xs.reshape(-1), T, pdim, out)
             got = np.array([L.orc_batch_float_fill(ms.reshape(-1), cst, nk, np.ascontiguousarray(xs[t]), pdim) for t in range(T)], np.float32)
             assert np.array_equal(bits(got), bits(out))
+    ref_replay.finish(R)

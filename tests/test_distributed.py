@@ -288,6 +288,24 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert rc != 0 and line is None and "WORLD_SIZE=1 but --gpus 2" in err
 
 
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as float32 / float64 .npy files, the same on a second run with the same
+    arguments; --steps sets the number of timed steps and the line carries ms_per_step.  Host-only stand-in (gloo): no GPU here."""
+    args = ["--backend", "gloo", "--workload", "null", "--steps", "3", "--warmup", "1", "--utterances", "9"]
+    runs = []
+    for d in ("a", "b"):
+        rc, line, err = _run_bench(args + ["--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err[-2000:]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert line["dump_outputs"]["files"] == ["counts.npy", "frames.npy", "score_sum.npy"]
+        runs.append({f: np.load(str(tmp_path / d / f)) for f in line["dump_outputs"]["files"]})
+    for f, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, runs[1][f]), f
+    assert runs[0]["frames.npy"][0] == line["stages"]["expected_frames"] == (1 + 3) * sum(100 + 7 * (i % 5) for i in range(9))
+    rc, line, err = _run_bench(["--backend", "gloo", "--workload", "null", "--steps", "0"])
+    assert rc != 0 and line is None and "--steps must be at least 1" in err
+
+
 def test_bench_product_workloads_refuse_the_cpu_backend():
     rc, line, err = _run_bench(["--backend", "gloo", "--workload", "nn"])
     assert rc != 0 and line is None and "no CPU path" in err

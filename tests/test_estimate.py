@@ -8,7 +8,7 @@ import pytest
 
 from oracle import OracleGmm
 from oracle import estimate as oe
-from tests import synth
+from tests import ref_replay, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "ref_estimate.json")
 
@@ -56,10 +56,10 @@ def test_oracle_matches_reference_functors_golden():
         assert got.tobytes() == bytes.fromhex(c["out"])
 
 
-def test_oracle_matches_reference_functors_live():
-    from oracle.binding import load_ref, ref_accumulate_vector, ref_log_exp_norm, ref_normalized_minus
-    if load_ref() is None:
-        pytest.skip("oracle/_ref/libref.so not built (no reference tree)")
+def test_oracle_matches_reference_functors_live(monkeypatch):
+    """the reference's functors (oracle/_ref, or their recorded answers) on seeded rows"""
+    from oracle.binding import ref_accumulate_vector, ref_log_exp_norm, ref_normalized_minus
+    R = ref_replay.reference(monkeypatch, "test_estimate.oracle_matches_reference_functors_live")
     rng = np.random.Generator(np.random.PCG64(5))
     for dim in (2, 16, 33):
         for kind in range(5):
@@ -71,6 +71,7 @@ def test_oracle_matches_reference_functors_live():
         assert oe.log_exp_norm(list(v)) == ref_log_exp_norm(v)
         x, y = np.abs(rng.standard_normal(dim)) * 100, np.abs(rng.standard_normal(dim))
         assert np.array_equal(oe.normalized_minus(x, y, 7.5), ref_normalized_minus(x, y, 7.5))
+    ref_replay.finish(R)
 
 
 def random_statistics(model, seed, frames=4000, zero_some=True):

@@ -1,6 +1,6 @@
 """CPU: pins the oracle (oracle/liboracle.so) against (a) outputs of the reference itself -- live through
-oracle/_ref/libref.so when /root/reference is mounted, and through the committed tests/golden/ref_* vectors
-everywhere -- (b) the known answers of SURVEY.md C.1, (c) the reference's unit-test vectors."""
+oracle/_ref/libref.so where the reference tree is mounted (elsewhere its recorded answers, tests/ref_replay.py), and
+through the committed tests/golden/ref_* vectors everywhere -- (b) the known answers of SURVEY.md C.1, (c) the reference's unit-test vectors."""
 import json
 import os
 
@@ -8,10 +8,9 @@ import numpy as np
 import pytest
 
 from oracle import MfccCfg, Oracle, OracleGmm, OracleMfcc, load_ref, oracle_ffnn_score
-from tests import synth
+from tests import ref_replay, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-HAVE_REF = os.path.isdir("/root/reference/src")
 
 
 def bits(a):
@@ -174,11 +173,9 @@ def test_gmm_normalisation_terms_against_reference_templates():
     assert np.array_equal(bits(isr[0]), bits(np.array(g["isr"], np.float32)))
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not mounted (GPU box)")
-def test_live_reference_build_agrees():
-    """Same checks against the freshly built reference TUs, on fresh random inputs."""
-    L, R = Oracle(), load_ref()
-    assert R is not None
+def test_live_reference_build_agrees(monkeypatch):
+    """Same checks against the freshly built reference TUs (or their recorded answers), on seeded random inputs."""
+    L, R = Oracle(), ref_replay.reference(monkeypatch, "test_oracle.live_reference_build_agrees")
     rng = np.random.Generator(np.random.PCG64(77))
     for n in (16, 128, 512, 2048):
         x = (rng.standard_normal(n) * 1e4).astype(np.float32)
@@ -190,13 +187,13 @@ def test_live_reference_build_agrees():
     for n in rng.integers(1, 60000, 40):
         n = int(n)
         fl = np.zeros(1000, np.int32)
-        nf = R.ref_window_frames(np.zeros(n, np.float32), n, 4096, 400, 160, 16000.0, 1000, fl.ctypes.data, None, None)
+        nf = R.ref_window_frames(np.zeros(n, np.float32), n, 4096, 400, 160, 16000.0, 1000, fl.ctypes, None, None)
         assert nf == m.n_frames(n)
         assert fl[nf - 1] == min(400, n - (nf - 1) * 160)
     from oracle.binding import oracle_activation
     xs = (rng.standard_normal(3000) * 6).astype(np.float32)
     nx, e = (-xs).astype(np.float32), np.zeros(3000, np.float32)
-    R.ref_mt_vr_exp(3000, nx.ctypes.data, e.ctypes.data)
+    R.ref_mt_vr_exp(3000, nx.ctypes, e.ctypes)
     assert np.array_equal(bits(oracle_activation(xs, 2)), bits((1.0 / (1.0 + e.astype(np.float64))).astype(np.float32)))
     from oracle.binding import oracle_time_window_frames
     for _ in range(60):   # Signal::TimeWindowBuffer (temporal integration) on fresh lengths / shifts / block sizes
@@ -204,7 +201,7 @@ def test_live_reference_build_agrees():
         n, block = int(rng.integers(1, 20000)), int(rng.integers(1, 5000))
         cap = n // shift + 8
         fl, first = np.zeros(cap, np.int32), np.zeros(cap, np.int64)
-        nf = R.ref_time_window_frames(n, block, 2, length, shift, 0, 16000.0, cap, fl.ctypes.data, None, first.ctypes.data)
+        nf = R.ref_time_window_frames(n, block, 2, length, shift, 0, 16000.0, cap, fl.ctypes, None, first.ctypes)
         starts, lens = oracle_time_window_frames(n, length, shift)
         assert nf == len(starts) and np.array_equal(first[:nf], starts) and np.array_equal(fl[:nf], lens), (n, length, shift, block)
     for f in rng.uniform(0, 8000, 50):
@@ -226,6 +223,7 @@ def test_live_reference_build_agrees():
     _, isr, ln = OracleGmm(model).tables()
     assert ln[0] == np.float32(R.ref_gauss_log_norm_factor(v, 39))
     assert all(isr[0][i] == np.float32(R.ref_inverse_square_root(float(v[i]))) for i in range(39))
+    ref_replay.finish(R)
 
 
 def _oracle_dct_apply(table, x):
