@@ -354,8 +354,10 @@ typedef struct {
      *   Every mode takes both (round 6).  Bit-exact, in the named build: AMX_GMM_MAX scores and density indices, AMX_GMM_BATCH_FLOAT,
      *   AMX_GMM_PRESELECTION_FLOAT (clustering included), amx_gmm_best_density_dev, the quantised scorers (integer arithmetic; their
      *   host-side gaussLogNormFactor follows the contract).  AMX_GMM_SUM: the DISTANCES and the best density follow the contract bit
-     *   for bit; the log-add score itself is a streaming sum with the device's expf / logf -- within 1e-5 of the reference's two-pass
-     *   form in either mode, not bit-exact.  Baum-Welch statistics: 2e-5 (the same expf).  fused_waves=13 (a lab kernel) has no fma
+     *   for bit; the log-add score is the reference's two-pass form (the first minimum, then the sum of expf(best - s_k) in density order) on
+     *   those bits with the device's expf / logf: not bit-exact (but bit-exact for one-density mixtures), within 1e-5 of the reference,
+     *   and no further from the exact value of the same expression than 4x the reference's own f32 error plus 1e-6 max(1, |score|)
+     *   on every kernel route (tests/test_gmm_sum_gpu.py).  Baum-Welch statistics: 2e-5 (the same expf).  fused_waves=13 (a lab kernel) has no fma
      *   form and fails the creation with AMX_ERR_UNSUPPORTED.  tests/test_gmm_contract_gpu.py, tests/test_contract_gpu.py.
      *
      * Kernel selection for A/B runs and tests -- every path gives the same scores and density indices bit for bit (within a contract):

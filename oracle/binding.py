@@ -186,6 +186,7 @@ def Oracle(contract=None):
         f.restype = C.POINTER(C.c_float)
         f.argtypes = [C.c_void_p]
     L.orc_gmm_score.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, f32p, C.c_void_p]
+    L.orc_gmm_sum_entries.argtypes = [C.c_void_p, f32p, C.c_int, f32p]
     L.orc_gmm_score_batch_float.restype = C.c_int
     L.orc_gmm_score_batch_float.argtypes = [C.c_void_p, f64p, f32p, f32p, C.c_int, f32p]
     L.orc_gmm_score_simd.restype = C.c_int
@@ -542,6 +543,14 @@ class OracleGmm:
         self.L.orc_gmm_score(self.h, mode, feats.reshape(-1), T, sc.reshape(-1),
                              best.ctypes.data if want_best else None)
         return (sc, best) if want_best else sc
+
+    def sum_entries(self, feats):
+        """the f32 per-density scores the log-add scorer combines: [T, sum K_m], column mix_offsets[m] + k = density k of mixture m"""
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        T = feats.shape[0]
+        out = np.zeros((T, int(self.m["mix_offsets"][-1])), np.float32)
+        self.L.orc_gmm_sum_entries(self.h, feats.reshape(-1), T, out.reshape(-1))
+        return out
 
     def accumulator_size(self):
         return int(self.L.orc_gmm_accumulator_size(self.h))

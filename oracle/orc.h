@@ -216,6 +216,9 @@ const float* orc_gmm_log_norm(const orc_gmm* h);           /* [n_cov] */
 /* mode 0 = maximum approximation, 1 = log-add.  feats [T x dim] row-major;
  * scores [T x n_mix]; best [T x n_mix] density-in-mixture index (nullable) */
 void orc_gmm_score(const orc_gmm* h, int mode, const float* feats, int T, float* scores, uint32_t* best);
+/* the f32 per-density scores the log-add scorer (mode 1) combines, (f32)(0.5 * ((m2lw + logNorm) + dist)): out [T x sum K_m], entry
+ * (t, mix_offsets[m] + k) for density k of mixture m -- for a high-precision restatement of the combine (tests/sum_reference.py) */
+void orc_gmm_sum_entries(const orc_gmm* h, const float* feats, int T, float* out);
 /* GaussDiagonalMaximumFeatureScorer::distance alone (pinned by tests/test_contract.py on the reference's own function text) */
 float orc_gmm_distance(const float* x, const float* mu, const float* inv_sqrt_var, int dim);
 /* Mm::BatchFloatFeatureScorer arithmetic (pooled covariance only, n_cov == 1) */

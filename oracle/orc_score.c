@@ -131,6 +131,26 @@ static float orc_distance(const float* x, const float* mu, const float* isr, int
 
 float orc_gmm_distance(const float* x, const float* mu, const float* isr, int dim) { return orc_distance(x, mu, isr, dim); }
 
+/* the per-density scores of GaussDiagonalSumFeatureScorer::calculateScoreAndDensity (:263-288) for frame x and mixture m, in density
+ * order: (f32)(0.5 * ((m2lw + logNorm) + dist)), the sum all f32 */
+static void orc_sum_entries(const orc_gmm* h, const float* x, int m, float* sk) {
+    uint32_t k0 = h->mix_off[m], k1 = h->mix_off[m + 1];
+    for (uint32_t k = k0; k < k1; ++k) {
+        uint32_t d     = h->dens_index[k];
+        uint32_t c     = h->dens_cov[d];
+        float    dist  = orc_distance(x, h->means + (size_t)h->dens_mean[d] * h->dim, h->isr + (size_t)c * h->dim, h->dim);
+        float    score = h->m2lw[k] + h->lognorm[c] + dist;
+        sk[k - k0]     = (float)(0.5 * score);
+    }
+}
+
+void orc_gmm_sum_entries(const orc_gmm* h, const float* feats, int T, float* out) {
+    size_t nk = h->mix_off[h->n_mix];
+    for (int t = 0; t < T; ++t)
+        for (int m = 0; m < h->n_mix; ++m)
+            orc_sum_entries(h, feats + (size_t)t * h->dim, m, out + (size_t)t * nk + h->mix_off[m]);
+}
+
 void orc_gmm_score(const orc_gmm* h, int mode, const float* feats, int T, float* scores, uint32_t* best) {
     int    maxk = 0;
     for (int m = 0; m < h->n_mix; ++m) {
@@ -164,15 +184,8 @@ void orc_gmm_score(const orc_gmm* h, int mode, const float* feats, int T, float*
                     best[(size_t)t * h->n_mix + m] = bestDns;
             }
             else {
-                /* GaussDiagonalSumFeatureScorer (:252-298): all f32 */
-                for (uint32_t k = k0; k < k1; ++k) {
-                    uint32_t d     = h->dens_index[k];
-                    uint32_t c     = h->dens_cov[d];
-                    float    dist  = orc_distance(x, h->means + (size_t)h->dens_mean[d] * h->dim,
-                                                  h->isr + (size_t)c * h->dim, h->dim);
-                    float    score = h->m2lw[k] + h->lognorm[c] + dist;
-                    sk[k - k0]     = (float)(0.5 * score);
-                }
+                /* GaussDiagonalSumFeatureScorer (:252-298): all f32; two passes, the minimum first, then the sum in density order */
+                orc_sum_entries(h, x, m, sk);
                 float    bestScore = FLT_MAX;
                 uint32_t bestDns   = UINT32_MAX;
                 for (uint32_t k = 0; k < k1 - k0; ++k)

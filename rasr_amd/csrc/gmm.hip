@@ -120,30 +120,37 @@ struct MaxState {
         idx             = c ? k : idx;
         best_d          = (double)best;
     }
+    __device__ __forceinline__ void  add2(float, float) {}
     __device__ __forceinline__ float result_d() const { return 0.5f * best; }
     __device__ __forceinline__ float result() const { return 0.5f * best; }
-    static constexpr bool kF64 = true;
+    static constexpr bool kF64     = true;
+    static constexpr bool kTwoPass = false;
 };
 
+// GaussDiagonalSumFeatureScorer::calculateScoreAndDensity (Mm/GaussDiagonalMaximumFeatureScorer.cc:263-288), all f32, in the
+// reference's two passes over the same entries s_k = 0.5 * ((m2lw + logNorm) + dist): add() finds the first strict minimum,
+// add2() then sums expf(best - s_k) in density order.  The one-pass online form this replaces (rescale the sum at every new
+// minimum) rounds expf once more per rescale: on entries that fall in list order it landed 5.1e-5 from the exact value where the
+// reference's own f32 error is 4.4e-6 (tests/test_gmm_sum_gpu.py test_ordered_lists).  The second pass costs the full-size tied
+// combine (4096 x 10 000 x 256 frames) 5.6 -> 6.5 ms.
 struct SumState {
     float    best = FLT_MAX;
     float    sum  = 0.f;
     uint32_t idx  = 0xffffffffu;
-    __device__ __forceinline__ void add(double, float c32, float dist, uint32_t k) {
-        float score = c32 + dist;  // (m2lw + logNorm) + dist, all f32
-        float s     = 0.5f * score;
+    static __device__ __forceinline__ float entry(float c32, float dist) { return 0.5f * (c32 + dist); }
+    __device__ __forceinline__ void         add(double, float c32, float dist, uint32_t k) {
+        const float s = entry(c32, dist);
         if (best > s) {
-            sum  = sum * expf(s - best) + 1.f;
             best = s;
             idx  = k;
         }
-        else
-            sum = sum + expf(best - s);
     }
+    __device__ __forceinline__ void  add2(float c32, float dist) { sum = sum + expf(best - entry(c32, dist)); }
     __device__ __forceinline__ float result() const { return best - logf(sum); }
     __device__ __forceinline__ void  add_d(double, double, uint32_t) {}
     __device__ __forceinline__ float result_d() const { return result(); }
-    static constexpr bool kF64 = false;
+    static constexpr bool kF64     = false;
+    static constexpr bool kTwoPass = true;
 };
 
 // DIM > 0: features in registers; DIM == 0: runtime dimension, features in LDS
@@ -190,19 +197,21 @@ __global__ __launch_bounds__(256) void gmm_direct_kernel(const float* __restrict
     // wave-uniform loop bounds (blockIdx only)
     const int m0 = blockIdx.x * p.mix_tile;
     const int m1 = min(m0 + p.mix_tile, p.n_mix);
+    auto distance = [&](uint32_t k) {
+        const float* mu = p.means + (size_t)p.k_mean[k] * (DIM > 0 ? DIM : p.dim);
+        const float* is = p.isr + (size_t)p.k_cov[k] * (DIM > 0 ? DIM : p.dim);
+        if (DIM > 0)
+            return gmm_distance<(DIM > 0 ? DIM : 1), FMA>(x, mu, is);
+        return gmm_distance_rt<FMA>(xs, p.dim, mu, is);
+    };
     for (int m = m0; m < m1; ++m) {
         const uint32_t k0 = p.mix_off[m], k1 = p.mix_off[m + 1];
         State          st;
-        for (uint32_t k = k0; k < k1; ++k) {
-            const float* mu = p.means + (size_t)p.k_mean[k] * (DIM > 0 ? DIM : p.dim);
-            const float* is = p.isr + (size_t)p.k_cov[k] * (DIM > 0 ? DIM : p.dim);
-            float        dist;
-            if (DIM > 0)
-                dist = gmm_distance<(DIM > 0 ? DIM : 1), FMA>(x, mu, is);
-            else
-                dist = gmm_distance_rt<FMA>(xs, p.dim, mu, is);
-            st.add(p.k_c64[k], p.k_c32[k], dist, k - k0);
-        }
+        for (uint32_t k = k0; k < k1; ++k)
+            st.add(p.k_c64[k], p.k_c32[k], distance(k), k - k0);
+        if constexpr (State::kTwoPass)  // the distances once more (the same arithmetic: the same bits), now that the minimum is known
+            for (uint32_t k = k0; k < k1; ++k)
+                st.add2(p.k_c32[k], distance(k));
         if (live) {
             p.scores[(size_t)t * p.n_mix + m] = st.result();
             if (p.best)
@@ -715,6 +724,15 @@ __global__ __launch_bounds__(256) void gmm_combine_uniform_kernel(const float* _
 #pragma unroll
             for (int f = 0; f < FR; ++f)
                 st[f].add(0.0, c32, g_dist[row + f], (uint32_t)k);
+        }
+    }
+    if constexpr (State::kTwoPass) {
+        for (int k = 0; k < dims.K; ++k) {
+            const float  c32 = g_m2lw_t[(size_t)k * dims.mix_pad + mm] + g_ln32[k];
+            const size_t row = (size_t)g_k_dens[k] * dims.Tpad + t0;
+#pragma unroll
+            for (int f = 0; f < FR; ++f)
+                st[f].add2(c32, g_dist[row + f]);
         }
     }
     if (live) {
@@ -1571,6 +1589,9 @@ __global__ __launch_bounds__(256) void gmm_combine_kernel(const float* __restric
             float dist = p.dist[(size_t)p.k_dens[k] * p.Tpad + tt];
             st.add(p.k_c64[k], p.k_c32[k], dist, k - k0);
         }
+        if constexpr (State::kTwoPass)
+            for (uint32_t k = k0; k < k1; ++k)
+                st.add2(p.k_c32[k], p.dist[(size_t)p.k_dens[k] * p.Tpad + tt]);
         if (live) {
             p.scores[(size_t)t * p.n_mix + m] = st.result();
             if (p.best)

@@ -80,8 +80,8 @@ def test_tied_mixture_partial_lists(ctx):
 
 @pytest.mark.parametrize("tied", [False, True])
 def test_log_add_scorer(ctx, tied):
-    """diagonal-sum: f32 throughout; the device uses a single-pass online log-sum-exp, the reference a
-    two-pass one, and expf/logf differ by ulps -> 1e-5 relative (requirement: 1e-4)."""
+    """diagonal-sum: f32 throughout, the reference's two passes on both sides; expf/logf differ by ulps -> 1e-5 relative
+    (requirement: 1e-4).  tests/test_gmm_sum_gpu.py holds every route to the f64 value as well."""
     import rasr_amd
     from oracle import OracleGmm
     model = synth.gmm_tied(100, 32, 40, seed=15) if tied else synth.gmm_cart(100, 1, 8, 40, seed=14, pooled=False)
