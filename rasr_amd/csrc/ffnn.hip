@@ -1526,31 +1526,7 @@ int ensure_workspace(amx_ffnn* h, int Tpad) {
     h->d_in = h->d_act[0] = h->d_act[1] = nullptr;
     h->cap_T                            = 0;
     const size_t planes = h->precision == AMX_PREC_BF16X3 ? 2 : 1;  // split bf16: rows are [hi plane | lo plane]
-    if (h->is_mx()) {  // 25 KB blocks per (256 rows, 32 k)
-        // The split-K workspace (tuning ksplit) is sized HERE, with the other buffers and outside any stream capture -- launch_mx
-        // used to grow it lazily, which on a retry after a failed allocation happened inside hipStreamBeginCapture and wrote through an
-        // iterator of the graph map it had just cleared (advisor, round 5).  Upper bound over the layers that can run split at this
-        // batch size: tiles of 128 x 64, four computing waves of two 32 x 32 blocks, 16 x 64 floats each.  A failed allocation
-        // switches the split off for the life of the handle (the default order: bit-identical to a handle created without ksplit).
-        if (h->mx_ksplit > 1) {
-            size_t need = 0;
-            for (int l = 0; l < h->n_layers; ++l) {
-                const long tiles = (long)(h->Npad[l] / 128) * (Tpad / 64);
-                if (tiles * h->mx_ksplit <= (long)std::max(h->ctx->n_cu, 8) && h->Kpad[l] / 32 >= 8 * h->mx_ksplit)
-                    need = std::max(need, (size_t)tiles * h->mx_ksplit * 4 * 2 * 16 * 64);
-            }
-            if (need > h->ks_ws_cap) {
-                hipFree(h->d_ks_ws);
-                h->d_ks_ws   = nullptr;
-                h->ks_ws_cap = 0;
-                if (hipMalloc((void**)&h->d_ks_ws, need * 4) != hipSuccess) {
-                    (void)hipGetLastError();
-                    h->mx_ksplit = 1;
-                }
-                else
-                    h->ks_ws_cap = need;
-            }
-        }
+    if (h->is_mx()) {  // 25 KB blocks per (256 rows, 32 k); the split-K workspace is sized once, by size_split_k_workspace
         AMX_HIP(hipMalloc(&h->d_in, (size_t)(Tpad / 256) * (h->Kpad[0] / 32) * amx::mx::BLK));
         if (h->max_hidden_pad > 0) {
             AMX_HIP(hipMalloc(&h->d_act[0], (size_t)(Tpad / 256) * (h->max_hidden_pad / 32) * amx::mx::BLK));
@@ -1566,6 +1542,42 @@ int ensure_workspace(amx_ffnn* h, int Tpad) {
     }
     h->cap_T = Tpad;
     return AMX_OK;
+}
+
+// The split-K workspace (tuning ksplit) is sized once, when the handle is created: outside any stream capture, and for the worst pass
+// that can ever run split, whatever the batch sizes of the calls to come.  (It used to be sized with the other buffers, for the layers
+// that split at the pass that grew them: a handle whose first pass had 1024 frames got no workspace, and its later 256-frame fills ran
+// the default order -- the scores of a fill depended on what the handle had scored before.)  A layer splits where its 128 x 64 tiles
+// times ksplit fit the CUs (launch_mx); the tile count grows with the padded batch, so the walk over Tpad = 256, 512, ... ends at the
+// first size where no layer fits.  Per tile: four computing waves of two 32 x 32 blocks, 16 x 64 floats each.  A failed allocation
+// switches the split off for the life of the handle (the default order: bit-identical to a handle created without ksplit).
+void size_split_k_workspace(amx_ffnn* h) {
+    if (!h->is_mx() || h->mx_ksplit <= 1)
+        return;
+    const long ncu  = std::max(h->ctx->n_cu, 8);
+    size_t     need = 0;
+    for (int Tpad = amx::PAD_NT;; Tpad += amx::PAD_NT) {
+        bool fits = false;
+        for (int l = 0; l < h->n_layers; ++l) {
+            const long tiles = (long)(h->Npad[l] / 128) * (Tpad / 64);
+            if (tiles * h->mx_ksplit > ncu)
+                continue;
+            fits = true;
+            if (h->Kpad[l] / 32 >= 8 * h->mx_ksplit)
+                need = std::max(need, (size_t)tiles * h->mx_ksplit * 4 * 2 * 16 * 64);
+        }
+        if (!fits)
+            break;
+    }
+    if (need == 0)
+        return;
+    if (hipMalloc((void**)&h->d_ks_ws, need * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_ks_ws   = nullptr;
+        h->mx_ksplit = 1;
+        return;
+    }
+    h->ks_ws_cap = need;
 }
 
 // tile configurations of the bf16 GEMM, selected at run time (amx_ffnn_model.tuning tile=N overrides for experiments)
@@ -1733,7 +1745,7 @@ void launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, 
         h->Kpad[l] / 32 >= 8 * h->mx_ksplit)
         ksplit = h->mx_ksplit;
     if (ksplit > 1 && (size_t)ntn * ntt * ksplit * C::NW * C::MI * C::MJ * 16 * 64 > h->ks_ws_cap)
-        ksplit = 1;  // (ensure_workspace sizes the workspace for every layer that can run split; nothing is allocated here: this may be inside a stream capture)
+        ksplit = 1;  // (size_split_k_workspace sizes the workspace for every pass that can run split; nothing is allocated here: this may be inside a stream capture)
     int       grid   = std::min(ntn * ntt * ksplit, per_cu * std::max(h->ctx->n_cu, 8));
     if (grid >= 8)
         grid &= ~7;  // keep blockIdx % 8 == tile index % 8 for every stride step
@@ -2202,6 +2214,7 @@ int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
         }
         h->d_bias.push_back(db);
     }
+    size_split_k_workspace(h);
     *out = h;
     return AMX_OK;
 }

@@ -135,6 +135,13 @@ def test_f16mx_split_k_mode_config4_against_the_oracle_and_across_buffer_sizes(c
             assert np.array_equal(part.view(np.uint32), got[t0:t0 + n].view(np.uint32)), (n, t0, rep_)
     # a fill that straddles two of the reference fills is still the same frames through the same split kernels
     assert np.array_equal(nn.score(x[100:300]).view(np.uint32), got[100:300].view(np.uint32))
+    # ... and on a handle whose FIRST pass is the 1024 frames that nothing splits: its fills of 256 are still split (the workspace is
+    # sized for every pass that can split, not for the pass that first grew the buffers)
+    nn_l = rasr_amd.NnBatchFeatureScorer(ctx, Ws, bs, acts, log_prior=logp, priori_scale=1.0, precision="f16mx", tuning="ksplit=4")
+    assert np.array_equal(nn_l.score(x).view(np.uint32), dflt.view(np.uint32))
+    for t0 in range(0, T, 256):
+        assert np.array_equal(nn_l.score(x[t0:t0 + 256]).view(np.uint32), got[t0:t0 + 256].view(np.uint32)), t0
+    del nn_l
     for d, act in (([440, 300, 33, 64, 50], 1), ([64, 96, 96, 10], 2), ([200, 2048, 2048, 40], 3)):
         W2, b2, a2, l2 = synth.ffnn(d, seed=11 + act, act=act)
         x2 = feats(200, d[0], 12)
