@@ -19,6 +19,11 @@ reference's partition rule (weak scaling: every rank owns a full batch); the onl
 the accumulators at the end of the timed epoch, through the library's own entry point (amx_comm_all_reduce_f64_dev = RCCL);
 torch.distributed carries the barrier, the max over ranks of the time and the 128-byte communicator id.  Rank 0 prints one
 JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.  --full adds
+everything else the line can carry, behind the timed region: the per-launch pass (roofline, stages, shader clock), the rocm-smi
+stretch, the streamed-ingest comparison, the CPU baseline with its parity check (--no-cpu-baseline drops them), and for the
+default workload the secondary configs and the decoder-facing rates (--no-configs drops them).
 """
 import argparse
 import json
@@ -87,8 +92,11 @@ def parse():
     ap.add_argument("--gmm-tuning", default=None, help='amx_gmm_model.tuning of every GMM scorer the workload builds, e.g. "screen=0" (A/B runs)')
     ap.add_argument("--nn-tuning", default=None, help='amx_ffnn_model.tuning, e.g. "tile=4" or "graph=1"')
     ap.add_argument("--mfcc-tuning", default=None, help='amx_mfcc_cfg.tuning, e.g. "fft=mfma" or "wgs=3"')
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary BASELINE configs of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else the line can carry (see the module docstring); "
+                         "a plain run only times its steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity check")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the secondary BASELINE configs of the default run")
     ap.add_argument("--precision", default="f16mx", choices=["bf16", "bf16x3", "f16mx", "fp32"],
                     help="NN GEMM inputs: f16mx = f16 product + one MX-fp6 scaled product for both cross terms (default since round 4: meets "
                          "north_star's 1e-4 bar against the f32 reference at 1.5 units of matrix time per product), bf16x3 = split bf16, "
@@ -1448,9 +1456,10 @@ def write_outputs(path, arrays):
     return dict(dir=path, files=sorted(n + ".npy" for n in arrays), bytes=int(sum(a.nbytes for a in arrays.values())))
 
 
-def measure(ctx, job, args, world, dump=False):
+def measure(ctx, job, args, world, dump=False, profile=True):
     """W untimed steps, then exactly K steps + the epoch reduce between barrier + synchronize; returns seconds.
-    dump: job.dumped = snapshot_outputs(job), taken behind the timed region and before the profiled pass below runs the steps again"""
+    dump: job.dumped = snapshot_outputs(job), taken behind the timed region and before the profiled pass below runs the steps again.
+    profile: run that pass (roofline, stages, shader clock); a plain run's headline skips it"""
     gpu = ctx is not None
     for _ in range(args.warmup):
         job.step()
@@ -1471,7 +1480,7 @@ def measure(ctx, job, args, world, dump=False):
         job.expected_frames = int(job.units) * (args.warmup + args.steps) * world
     if dump:
         job.dumped = snapshot_outputs(job)
-    if gpu:
+    if gpu and profile:
         # kernel timings (roofline, stages) come from a SECOND pass over the same steps with the per-launch HIP events on (for a
         # graph-replayed workload: with plain launches).  The survivor counter is reset WITH the profiler, so that it covers exactly
         # the launches the events cover.
@@ -1495,7 +1504,6 @@ def measure(ctx, job, args, world, dump=False):
         if ok.any():
             SHADER_CLOCK_GHZ = round(float(np.median(per[ok])), 3)   # the median: single XCDs read 1.5 or 2.9 GHz over 160 ms (s_memtime counts per CU, unaligned)
             SHADER_CLOCK_XCD = [round(float(v), 3) if o else None for v, o in zip(per, ok)]
-    if gpu:
         ctx.profile(False)
     return dt
 
@@ -1791,7 +1799,7 @@ def main():
         comm = make_comm(ctx, rank, world)
         job = make_job(ctx, args, rank, world)
         job.comm = comm
-        dt = measure(ctx, job, args, world, dump=bool(args.dump_outputs) and rank == 0)
+        dt = measure(ctx, job, args, world, dump=bool(args.dump_outputs) and rank == 0, profile=args.full)
     dumped = write_outputs(args.dump_outputs, job.dumped) if args.dump_outputs and rank == 0 else None
     t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if _dist_on():
@@ -1810,24 +1818,25 @@ def main():
                          if args.workload in ("pipeline", "nn-pipeline", "nn") else "f32",
                 "data": "synthetic", "config": {"workload": WORKLOAD_NAMES[args.workload](args), "frames_per_step_per_gpu": job.units,
                                                 "contract": CONTRACT_TEXT[args.contract]},
-                "rtf": round(dt / (units * 0.01), 8), "build": rasr_amd.version()}
+                "rtf": round(dt / (units * 0.01), 8), "build": rasr_amd.version(), "full": args.full}
         if dumped:
             line["dump_outputs"] = dumped
             job.dumped = None
         if getattr(job, "requested_precision", None) and job.requested_precision != getattr(job, "nn_precision", job.requested_precision):
             line["config"]["precision_fallback"] = ("requested %s, the handle computes in %s (amx_ffnn_precision: block-maximum statistic of the weights "
                                                     "above 4.0, tuning mx_fallback=auto)" % (job.requested_precision, job.nn_precision))
-        line["roofline"] = job.roofline()
-        if line["roofline"] and line["roofline"].get("traffic") is not None:
-            line["roofline"]["traffic_source"] = TRAFFIC_SOURCE + " (offline rocprofv3 --pmc passes on the profiling box, not this run)"
-        line["stages"] = job.stage_report()
-        if world == 1:
+        if args.full:
+            line["roofline"] = job.roofline()
+            if line["roofline"] and line["roofline"].get("traffic") is not None:
+                line["roofline"]["traffic_source"] = TRAFFIC_SOURCE + " (offline rocprofv3 --pmc passes on the profiling box, not this run)"
+            line["stages"] = job.stage_report()
+        if args.full and world == 1:
             try:
                 with torch.cuda.stream(stream):
                     smi_stretch(job)
             except Exception:  # never take the headline down
                 pass
-        if line["roofline"] and (SHADER_CLOCK_GHZ or HWMON):
+        if line.get("roofline") and (SHADER_CLOCK_GHZ or HWMON):
             r = line["roofline"]
             # the driver's figure where it exists; the counters' otherwise (s_memtime is a counter per CU, the CUs' counters are not
             # aligned: between two short samples on different CUs of an XCD the difference is off by their offset -- single XCDs read 1.5
@@ -1860,23 +1869,26 @@ def main():
         elif hasattr(job, "setup_ingest") and getattr(job, "pcm", None) is not None and world == 1:
             line["ingest"] = dict(mode="resident", sample_format="f32", bytes_over_link_per_step=0,
                                   note="the same %d utterances every step, in HBM before the timed region" % args.utterances)
-            try:
-                with torch.cuda.stream(stream):
-                    line["ingest"]["streamed"] = streamed_comparison(ctx, job, args, value)
-            except Exception as e:  # never take the headline down
-                line["ingest"]["streamed"] = dict(error=str(e)[:200])
+            if args.full:
+                try:
+                    with torch.cuda.stream(stream):
+                        line["ingest"]["streamed"] = streamed_comparison(ctx, job, args, value)
+                except Exception as e:  # never take the headline down
+                    line["ingest"]["streamed"] = dict(error=str(e)[:200])
         if hasattr(job, "red"):
-            ms_ar, n_ar = ctx.profile_get("all_reduce")
             line["epoch_reduce"] = dict(collectives=1, bytes=job.red.nbytes(),
                                         backend="rccl via amx_comm_all_reduce_f64_dev (%d ranks)" % comm.world if comm else "none (single process)")
             if hasattr(job, "reduced_frames"):
                 line["epoch_reduce"].update(reduced_frames=job.reduced_frames, expected_frames=job.expected_frames,
                                             reduce_ok=bool(job.reduced_frames == job.expected_frames))
-        line["config"]["timing"] = ("value / ms_per_step: K steps with the library's per-launch events OFF; roofline / stages: a second pass over "
-                                    "min(K, 20) steps with a HIP-event pair around every launch on the stream the kernels run on")
+        line["config"]["timing"] = "value / ms_per_step: K steps with the library's per-launch events OFF"
+        if args.full:
+            line["config"]["timing"] += ("; roofline / stages: a second pass over min(K, 20) steps with a HIP-event pair around every launch on "
+                                         "the stream the kernels run on")
         if is_graph_mode(args):
-            line["config"]["launch"] = "forward pass replayed as one HIP graph; roofline / stages timed in the second pass with plain launches"
-        if not args.no_cpu_baseline and world == 1:
+            line["config"]["launch"] = "forward pass replayed as one HIP graph" + ("; roofline / stages timed in the second pass with plain launches"
+                                                                                    if args.full else "")
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(args.workload, args.contract)
             line["cpu_baseline"] = cb
             line["speedup_vs_cpu"] = round(value / world / cb["value"], 1)
@@ -1887,7 +1899,7 @@ def main():
                         line["parity_check"] = parity_check(ctx, job, args)
                 except Exception as e:  # never take the headline down
                     line["parity_check"] = dict(error=str(e)[:300])
-        if args.workload == "pipeline" and world == 1 and not args.no_configs:
+        if args.full and args.workload == "pipeline" and world == 1 and not args.no_configs:
             job = None
             torch.cuda.empty_cache()
             with torch.cuda.stream(stream):

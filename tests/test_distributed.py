@@ -465,6 +465,36 @@ def test_bench_product_control_flow_at_two_ranks(workload):
     assert "cpu_baseline" not in line and "configs" not in line   # rank 0 at N > 1 reports the job, not the 1-GPU extras
 
 
+def test_bench_plain_run_does_only_its_steps():
+    """`bench.py --steps K --warmup W` on one GPU: W + K steps on the device and the headline, nothing behind it.  With --full the
+    same command adds the per-launch pass (stages) and the streamed-ingest comparison -- here without the CPU baseline, the secondary
+    configs and the rocm-smi stretch -- and the headline's fields keep their meaning."""
+    K, W, U = 3, 1, 4
+    argv = ["--steps", str(K), "--warmup", str(W), "--utterances", str(U), "--utt-seconds", "1"]
+    rc, lines, err = _run_fake_device_bench(argv)
+    assert rc == 0, err[-3000:]
+    line = next(l for l in lines if "metric" in l)
+    fake = next(l for l in lines if l.get("fake_device"))
+    assert fake["front_end_runs_on_rank0"] == W + K
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == K and line["warmup"] == W
+    for key in ("roofline", "stages", "cpu_baseline", "parity_check", "configs", "decoder_facing"):
+        assert key not in line, key
+    assert line["ingest"]["mode"] == "resident" and "streamed" not in line["ingest"]
+    assert line["epoch_reduce"]["reduce_ok"] and line["epoch_reduce"]["reduced_frames"] == U * 99 * (W + K)
+    plain = line
+    rc, lines, err = _run_fake_device_bench(argv + ["--full", "--no-cpu-baseline", "--no-configs"], env_extra={"AMX_BENCH_NO_SMI": "1"})
+    assert rc == 0, err[-3000:]
+    line = next(l for l in lines if "metric" in l)
+    fake = next(l for l in lines if l.get("fake_device"))
+    passes = W + K + min(K, 20)                          # warm-up, timed steps, per-launch pass
+    assert fake["front_end_runs_on_rank0"] == 3 * passes  # the headline, the streamed run, the resident s16 run
+    assert line["full"] is True and "stages" in line and "roofline" in line
+    assert line["ingest"]["streamed"]["utterances_visited"] == passes * U
+    assert "cpu_baseline" not in line and "configs" not in line
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert line[key] == plain[key], key
+
+
 def test_bench_product_branch_refuses_a_world_size_mismatch():
     rc, lines, err = _run_fake_device_bench(["--gpus", "4", "--steps", "1", "--warmup", "0", "--utterances", "2", "--utt-seconds", "1"],
                                             env_extra={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})

@@ -5,7 +5,7 @@ a=$1; b=$2; shift 2
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 for rep in 1 2 3; do
   for lib in $a $b; do
-    AMX_LIBRARY=$root/$lib python $root/bench.py "$@" --no-cpu-baseline 2>/dev/null | tail -1 | \
+    AMX_LIBRARY=$root/$lib python $root/bench.py "$@" --full --no-cpu-baseline 2>/dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); s=d['stages']; print('$lib', d['ms_per_step'], {k: s[k]['avg_ms'] for k in s if isinstance(s[k], dict) and 'avg_ms' in s[k]})"
   done
 done

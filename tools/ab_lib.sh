@@ -19,7 +19,7 @@ fi
 shift
 for rep in 1 2 3; do
   for lib in librasr_amd_old.so librasr_amd.so; do
-    AMX_LIBRARY=$PWD/rasr_amd/$lib python bench.py "$@" --no-cpu-baseline --no-configs 2>&1 | grep "^{" | tail -1 | \
+    AMX_LIBRARY=$PWD/rasr_amd/$lib python bench.py "$@" --full --no-cpu-baseline --no-configs 2>&1 | grep "^{" | tail -1 | \
       python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$lib', d['ms_per_step'], {k: v.get('avg_ms') for k, v in d.get('stages', {}).items() if isinstance(v, dict)})"
   done
 done

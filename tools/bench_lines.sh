@@ -4,7 +4,7 @@ round=${1:-r05}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$round
 mkdir -p $out
-line() { name=$1; shift; python $root/bench.py "$@" 2>/dev/null | tail -1 > $out/${name}_bench.log; }
+line() { name=$1; shift; python $root/bench.py --full "$@" 2>/dev/null | tail -1 > $out/${name}_bench.log; }
 python $root/bench.py --no-cpu-baseline --no-configs > /dev/null 2>&1
 line pipeline --steps 10 --warmup 2
 line pipeline-streamed --ingest streamed --steps 20 --warmup 2 --no-cpu-baseline --no-configs
@@ -25,5 +25,5 @@ line nn-bf16 --workload nn --precision bf16 --steps 50 --warmup 5 --no-cpu-basel
 line mfcc-plp --workload mfcc --front-end plp --steps 8 --warmup 2 --no-cpu-baseline
 line mfcc-mfplp --workload mfcc --front-end mfplp --steps 8 --warmup 2 --no-cpu-baseline
 line mfcc-gammatone --workload mfcc --front-end gammatone --steps 3 --warmup 1 --no-cpu-baseline
-AMX_BENCH_FORCE_DIST=1 python $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | grep "^{\"metric\"" | tail -1 > $out/force_dist_bench.log
+AMX_BENCH_FORCE_DIST=1 python $root/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | grep "^{\"metric\"" | tail -1 > $out/force_dist_bench.log
 ls $out

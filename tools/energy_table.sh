@@ -13,7 +13,7 @@ cd $root
 run() {  # name, env-assignments (or -), bench args...
     name=$1; envs=$2; shift 2
     if [ "$envs" = "-" ]; then envs=""; fi
-    env $envs python bench.py "$@" --no-cpu-baseline --no-configs 2>$out/$name.err | grep '^{"metric"' | tail -1 > $out/$name.json
+    env $envs python bench.py "$@" --full --no-cpu-baseline --no-configs 2>$out/$name.err | grep '^{"metric"' | tail -1 > $out/$name.json
     [ -s $out/$name.json ] || echo "energy_table: $name produced no line: $(tail -1 $out/$name.err)"
 }
 PL=tools/build/librasr_amd_plain.so
@@ -36,7 +36,7 @@ cd /tmp && export TMPDIR=/tmp
 for g in default 8x8 2x16 32x4; do
     rm -rf /tmp/en_pmc_$g
     tun=""; [ "$g" != "default" ] && tun="--nn-tuning group=$g"
-    AMX_BENCH_NO_SMI=1 timeout 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/en_pmc_$g -- python $root/bench.py --workload nn-pipeline --steps 3 --warmup 1 --no-cpu-baseline --no-configs $tun > /tmp/en_pmc_$g.log 2>&1
+    AMX_BENCH_NO_SMI=1 timeout 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/en_pmc_$g -- python $root/bench.py --workload nn-pipeline --steps 3 --warmup 1 --full --no-cpu-baseline --no-configs $tun > /tmp/en_pmc_$g.log 2>&1
     f=$(find /tmp/en_pmc_$g -name "*counter_collection.csv" | head -1)
     [ -n "$f" ] && python $root/tools/pmc_summary.py $f gemm_mx > $out/l2_group_$g.txt
 done

@@ -6,7 +6,7 @@ timeout 1500 python -m pytest tests -m gpu -q > $out/gpu_tests_lease5.log 2>&1; 
 tail -3 $out/gpu_tests_lease5.log
 ONLY='^gmm-tied$' bash tools/profile_all.sh r06 > /dev/null 2>&1
 cat $out/gmm-tied_bench.log | cut -c1-300
-python bench.py 2>/dev/null | grep '^{"metric"' | tail -1 > $out/default_bench.log
+python bench.py --full 2>/dev/null | grep '^{"metric"' | tail -1 > $out/default_bench.log
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06/default_bench.log').read())

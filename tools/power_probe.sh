@@ -19,8 +19,8 @@ echo "columns: sclk, socket power (W); cap: $(rocm-smi --showmaxpower 2>&1 | gre
 sample "output layer 2048 -> 10000, 47 952 frames, f16mx, tile=8 (ping-pong, the default): 3000 passes" python tools/out_layer_time.py tile=8 47952 3000
 sample "the same, tile=9 (one self-pipelined wave per SIMD)" python tools/out_layer_time.py tile=9 47952 3000
 sample "the same, tile=2 (round 4's kernel: eight waves in phase)" python tools/out_layer_time.py tile=2 47952 3000
-sample "bench.py --workload nn-pipeline --steps 600 (MFCC -> ctx11 -> FFNN 440-6x2048-10000)" python bench.py --workload nn-pipeline --no-cpu-baseline --no-configs --steps 600 --warmup 3
-sample "bench.py --workload gmm --steps 1500 (fused GMM scorer, cfg3-cart)" python bench.py --workload gmm --no-cpu-baseline --no-configs --steps 1500 --warmup 3
-sample "bench.py --workload pipeline --steps 400 (headline: both scorers)" python bench.py --no-cpu-baseline --no-configs --steps 400 --warmup 3
-sample "bench.py --workload nn-pipeline --precision bf16 --steps 600" python bench.py --workload nn-pipeline --precision bf16 --no-cpu-baseline --no-configs --steps 600 --warmup 3
+sample "bench.py --workload nn-pipeline --steps 600 (MFCC -> ctx11 -> FFNN 440-6x2048-10000)" python bench.py --workload nn-pipeline --full --no-cpu-baseline --no-configs --steps 600 --warmup 3
+sample "bench.py --workload gmm --steps 1500 (fused GMM scorer, cfg3-cart)" python bench.py --workload gmm --full --no-cpu-baseline --no-configs --steps 1500 --warmup 3
+sample "bench.py --workload pipeline --steps 400 (headline: both scorers)" python bench.py --full --no-cpu-baseline --no-configs --steps 400 --warmup 3
+sample "bench.py --workload nn-pipeline --precision bf16 --steps 600" python bench.py --workload nn-pipeline --precision bf16 --full --no-cpu-baseline --no-configs --steps 600 --warmup 3
 cat $L

@@ -31,10 +31,10 @@ only() { [ -z "$ONLY" ] || [[ "$1" =~ $ONLY ]]; }  # ONLY=<regex>: just the work
 run_stats() {  # name, bench args...
     only $1 || return 0
     name=$1; shift
-    python $root/bench.py "$@" 2>/tmp/bench_$name.err | tail -1 > $out/${name}_bench.log
+    python $root/bench.py --full "$@" 2>/tmp/bench_$name.err | tail -1 > $out/${name}_bench.log
     grep -q '^{"metric"' $out/${name}_bench.log || { echo "$out/${name}_bench.log: no JSON line (bench.py $*): $(tail -1 /tmp/bench_$name.err)" >> $out/FAILED; mv $out/${name}_bench.log $out/${name}_bench.log.FAILED; }
     rm -rf /tmp/prof_$name
-    AMX_BENCH_NO_SMI=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $root/bench.py "$@" --no-cpu-baseline --no-configs > /tmp/prof_$name.log 2>&1
+    AMX_BENCH_NO_SMI=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $root/bench.py "$@" --full --no-cpu-baseline --no-configs > /tmp/prof_$name.log 2>&1
     f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1)
     if [ -n "$f" ]; then cp $f $out/${name}_kernel_stats.csv; else echo "$name: rocprofv3 left no kernel_stats.csv" >> $out/FAILED; fi
 }
@@ -45,7 +45,7 @@ run_pmc() {  # name, suffix, counters..., -- bench args...
     while [ "$1" != "--" ]; do ctrs+=("$1"); shift; done
     shift
     rm -rf /tmp/pmc_${name}_$suf
-    AMX_BENCH_NO_SMI=1 timeout 300 rocprofv3 --kernel-trace --pmc "${ctrs[@]}" --output-format csv -d /tmp/pmc_${name}_$suf -- python $root/bench.py "$@" --no-cpu-baseline --no-configs > /tmp/pmc_${name}_$suf.log 2>&1
+    AMX_BENCH_NO_SMI=1 timeout 300 rocprofv3 --kernel-trace --pmc "${ctrs[@]}" --output-format csv -d /tmp/pmc_${name}_$suf -- python $root/bench.py "$@" --full --no-cpu-baseline --no-configs > /tmp/pmc_${name}_$suf.log 2>&1
     f=$(find /tmp/pmc_${name}_$suf -name "*counter_collection.csv" | head -1)
     [ -n "$f" ] && python $root/tools/pmc_summary.py $f > $out/pmc/${name}_$suf.txt
 }
@@ -93,7 +93,7 @@ run_pmc gmm-tied write WRITE_SIZE -- --workload gmm-tied --steps 5 --warmup 2
 if [ -n "$ONLY" ]; then ls -la $out $out/pmc; exit 0; fi
 (cd $root && timeout 1500 python -m pytest tests -m gpu -q > $out/gpu_tests.log 2>&1)
 (cd $root && for f in "fuzz_frontends.py 300 31" "fuzz_scorers.py 300 32" "fuzz_gmm.py 200 33" "fuzz_tied.py 300 34" "fuzz_more.py 100 35" "fuzz_ffnn.py 40 36" "fuzz_backend.py 100 37"; do echo "== tools/$f"; timeout 900 python tools/$f 2>&1 | grep -v amdgpu.ids | tail -2; done > $out/gpu_fuzz.log 2>&1)
-AMX_BENCH_FORCE_DIST=1 python $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | grep "^{\"metric\"" | tail -1 > $out/force_dist_bench.log
+AMX_BENCH_FORCE_DIST=1 python $root/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | grep "^{\"metric\"" | tail -1 > $out/force_dist_bench.log
 python $root/tools/gemm_comparator.py > $out/gemm_comparator.json 2>/dev/null
 [ -x $root/tools/build/feed_probe ] && $root/tools/build/feed_probe > $out/feed_probe.log 2>&1
 if [ -f $root/tools/build/librasr_amd_lab.so ]; then

@@ -15,12 +15,12 @@ variant() {  # label, library ("" = product), gmm tuning ("" = none)
     ( cd $root
       if [ -n "$lib" ]; then export AMX_LIBRARY=$root/$lib; fi
       timeout 600 python -m pytest tests/test_gmm_gpu.py tests/test_gmm_contract_gpu.py -x -q -k "tied" 2>&1 | tail -1 >> $out
-      python bench.py --workload gmm-tied --steps 200 --warmup 100 --no-cpu-baseline ${tun:+--gmm-tuning $tun} 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
+      python bench.py --workload gmm-tied --steps 200 --warmup 100 --full --no-cpu-baseline ${tun:+--gmm-tuning $tun} 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}
 print('   %.4f ms per 256 frames  (%s frames/s)  frac %s  surviving fraction %s  %s' % (d['ms_per_step'], d['value'], r.get('frac'), r.get('surviving_fraction'), r.get('time_is', r.get('kernel'))))" >> $out
       cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_tied
-      rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_tied -- python $root/bench.py --workload gmm-tied --no-cpu-baseline --steps 40 --warmup 5 ${tun:+--gmm-tuning $tun} > /dev/null 2>&1
+      rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_tied -- python $root/bench.py --workload gmm-tied --full --no-cpu-baseline --steps 40 --warmup 5 ${tun:+--gmm-tuning $tun} > /dev/null 2>&1
       f=$(find /tmp/prof_tied -name "*kernel_stats.csv" | head -1)
       [ -n "$f" ] && python3 - "$f" >> $out <<'PY'
 import csv, sys
