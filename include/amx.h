@@ -526,7 +526,9 @@ void amx_mixture_set_destroy(amx_mixture_set* ms);
 
 /* ------------------------------------------------------------------ feed-forward NN scorer */
 
-enum { AMX_ACT_NONE = 0, AMX_ACT_RELU = 1, AMX_ACT_SIGMOID = 2, AMX_ACT_TANH = 3 };
+/* AMX_ACT_ELU: RASR's `elu` layer with its alpha fixed at 1 (Nn/ActivationLayer.cc:331-396, Math::FastMatrix<f32>::elu,
+ * Math/FastMatrix.hh:1658-1667): x < 0 ? exp(x) - 1 : x, the exponential is std::exp on a float (expf); a NaN stays NaN. */
+enum { AMX_ACT_NONE = 0, AMX_ACT_RELU = 1, AMX_ACT_SIGMOID = 2, AMX_ACT_TANH = 3, AMX_ACT_ELU = 4 };
 /* MFMA input type; accumulation is always f32.  AMX_PREC_BF16X3 = split bf16: every operand is hi + lo (two bf16 values) and a
  * product is taken as hi hi + lo hi + hi lo -- three bf16 MFMA products, ~2^-16 relative error per product: the mode that meets
  * the 1e-4 bar of the f32 reference (Math::gemm<f32>, Math/Blas.hh:402-420) at a third of the bf16 rate */
@@ -582,6 +584,38 @@ typedef struct {
 } amx_ffnn_model;
 
 int  amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* model, amx_ffnn** out);
+
+/* Layer types of Nn::NeuralNetwork (Nn/NeuralNetworkLayer.cc:34-56) beyond the linear + activation chain of amx_ffnn_model; an
+ * optional descriptor next to the model, which stays as it is.
+ * Preprocessing layers in front of layer 0, applied in pre_type order to the f32 features while they are packed for the first GEMM
+ * (no extra pass over the frames); they stack (e.g. log, then mean and variance):
+ *   AMX_NN_PRE_LOGARITHM          `logarithm` (Nn/PreprocessingLayer.cc:40-74): FastMatrix::log -> Math::vr_log
+ *                                 (Math/FastVectorOperations.hh:86-90), the unqualified `log` on a float, which resolves to ::log(double)
+ *                                 there (the same header and overload set as mt_vr_exp): (float)log((double)x).
+ *   AMX_NN_PRE_MEAN_AND_VARIANCE  `mean-and-variance-normalization` (Nn/PreprocessingLayer.cc:86-177, `mean-file` and
+ *                                 `standard-deviation-file`, f32 vectors: amx_nn_vector_read_f32): addToAllColumns(mean, -1) then
+ *                                 divideRowsByScalars(stddev) = scal((f32)1 / s) (Math/FastMatrix.hh:1356-1361,1439-1444):
+ *                                 x' = (x - m) * r with r = 1.0f / s.  A zero or negative s is accepted, as the reference does.
+ * `maxoutvar` (Nn/ActivationLayer.cc:404-520, Math::FastMatrix::maxoutvar, Math/FastMatrix.hh:840-860): maxout_groups[l] = G > 0
+ * puts a maxout behind layer l, which then computes maxout(act_l(W_l x + b_l)) with G outputs (in_dim[l + 1] == G).  Output g is
+ * the maximum of its group of consecutive units: the first element is the start value and a later one replaces it only if it is
+ * strictly greater (a NaN in first position stays, a later NaN never wins).  Group sizes: maxout_sizes[l] (`maxout-sizes`, a
+ * Math::Vector<u32> file: amx_nn_vector_read_u32), each >= 1 and adding up to out_dim[l]; NULL = `maxout-size`, out_dim[l] / G each
+ * (it must divide).  No maxout after the output layer.
+ * ext == NULL is amx_ffnn_create.  Invalid descriptors return AMX_ERR_INVALID with a message naming the layer.  The network's hidden
+ * dimension (amx_ffnn_hidden_dim) is the width after the last hidden layer's maxout; a network without hidden layers exports its
+ * preprocessed input from amx_ffnn_forward_hidden_dev. */
+enum { AMX_NN_PRE_LOGARITHM = 1, AMX_NN_PRE_MEAN_AND_VARIANCE = 2 };
+#define AMX_NN_MAX_PRE 4
+typedef struct {
+    int                 n_pre;          /* preprocessing layers in front of layer 0, applied in this order (0..AMX_NN_MAX_PRE) */
+    const int*          pre_type;       /* [n_pre] AMX_NN_PRE_* */
+    const float* const* pre_mean;       /* [n_pre] each [in_dim[0]] for AMX_NN_PRE_MEAN_AND_VARIANCE, else NULL */
+    const float* const* pre_stddev;     /* [n_pre] each [in_dim[0]] for AMX_NN_PRE_MEAN_AND_VARIANCE, else NULL */
+    const int*          maxout_groups;  /* nullable [n_layers]: 0 = none, G > 0 = maxoutvar with G outputs behind layer l */
+    const int* const*   maxout_sizes;   /* nullable [n_layers]: [G] group sizes, NULL = out_dim[l] / G each */
+} amx_ffnn_layers;
+int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* model, const amx_ffnn_layers* ext, amx_ffnn** out);
 void amx_ffnn_destroy(amx_ffnn* h);
 int  amx_ffnn_input_dim(const amx_ffnn* h);
 int  amx_ffnn_output_dim(const amx_ffnn* h);
@@ -637,6 +671,9 @@ int amx_nn_vector_read_f32(const char* path, int* n, float** data);
 int amx_nn_vector_write_f32(const char* path, int n, const float* data);
 int amx_nn_vector_read_s32(const char* path, int* n, int** data);
 int amx_nn_vector_write_s32(const char* path, int n, const int* data);
+/* Math::Vector<u32> (maxoutvar's `maxout-sizes`): XML `<vector-u32 size="n">` or `bin:<path>` (u32 n + raw elements; Math/Module.cc:28-29
+ * registers both for u32).  A file of another element type is refused.  *data is malloc'ed (amx_free). */
+int amx_nn_vector_read_u32(const char* path, int* n, uint32_t** data);
 
 /* ------------------------------------------------------------------ device buffers for resident score blocks
  * A decoder asks for ONE score at a time (Mm::FeatureScorer::ContextScorer::score, Mm/FeatureScorer.hh:31-46) and usually for a few

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AMX_GMM_BATCH_FLOAT, AMX_GMM_BAUM_WELCH, AMX_GMM_MAX, AMX_GMM_SUM, AMX_GMM_VITERBI,  # noqa: F401
+from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AMX_ACT_ELU, AMX_GMM_BATCH_FLOAT, AMX_GMM_BAUM_WELCH, AMX_GMM_MAX, AMX_GMM_SUM, AMX_GMM_VITERBI,  # noqa: F401
                    AMX_PREC_BF16, AMX_PREC_FP32, AmxError, MfccCfg)
 
 __all__ = ["Context", "MfccExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
@@ -528,8 +528,12 @@ class GmmFeatureScorer:
 class NnBatchFeatureScorer:
     """Nn::BatchFeatureScorer: Ws[l] is [out, in] (RASR weights_[0] is the same memory, [in x out] col-major)."""
 
-    def __init__(self, ctx, Ws, biases, activations, log_prior=None, priori_scale=1.0, precision="bf16", class_to_output=None, tuning=None):
-        """class_to_output: Nn::ClassLabelWrapper mapping [n_classes] (emission -> network output, -1 = disregarded class)"""
+    def __init__(self, ctx, Ws, biases, activations, log_prior=None, priori_scale=1.0, precision="bf16", class_to_output=None, tuning=None,
+                 preprocessing=None, maxout=None):
+        """class_to_output: Nn::ClassLabelWrapper mapping [n_classes] (emission -> network output, -1 = disregarded class)
+        preprocessing: layers in front of layer 0, in order: "logarithm", or ("mean-and-variance-normalization", mean, stddev)
+        maxout: {layer: G (maxout-size: out_dim / G units per group) or [group sizes] (maxout-sizes)} -- a maxoutvar behind that layer;
+        activations may hold AMX_ACT_ELU (4).  Either argument goes through amx_ffnn_create_ex (include/amx.h)."""
         self.ctx, self.L = ctx, ctx.L
         n = len(Ws)
         self._Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in Ws]
@@ -546,10 +550,43 @@ class NnBatchFeatureScorer:
                             {"fp32": AMX_PREC_FP32, "bf16": AMX_PREC_BF16, "bf16x3": _lib.AMX_PREC_BF16X3, "f16mx": _lib.AMX_PREC_F16MX}[precision],
                             0 if self._map is None else len(self._map), _ptr(self._map), _tuning(tuning))   # e.g. tuning="tile=3"
         h = C.c_void_p()
-        _lib.check(self.L.amx_ffnn_create(ctx.h, C.byref(st), C.byref(h)))
+        if preprocessing or maxout:
+            ext = self._layers(n, preprocessing or [], maxout or {})
+            _lib.check(self.L.amx_ffnn_create_ex(ctx.h, C.byref(st), C.byref(ext), C.byref(h)))
+        else:
+            _lib.check(self.L.amx_ffnn_create(ctx.h, C.byref(st), C.byref(h)))
         self.h = h
         self.in_dim, self.out_dim = int(self._ind[0]), int(self.L.amx_ffnn_output_dim(h))
         self.hidden_dim = int(self.L.amx_ffnn_hidden_dim(h))
+
+    def _layers(self, n, preprocessing, maxout):
+        """amx_ffnn_layers for the preprocessing list and the maxout map (the arrays stay referenced by self)"""
+        names = {"logarithm": _lib.AMX_NN_PRE_LOGARITHM, "mean-and-variance-normalization": _lib.AMX_NN_PRE_MEAN_AND_VARIANCE}
+        types, vecs = [], []
+        for p in preprocessing:
+            p = (p,) if isinstance(p, str) else tuple(p)
+            if p[0] not in names:
+                raise ValueError("unknown preprocessing layer %r (expected %s)" % (p[0], " | ".join(names)))
+            types.append(names[p[0]])
+            vecs.append([None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in p[1:3]] if len(p) >= 3 else [None, None])
+        self._pre_vecs = vecs
+        self._pre_type = np.array(types, np.int32)
+        self._pre_mean = (C.c_void_p * max(len(vecs), 1))(*[_ptr(v[0]) for v in vecs])
+        self._pre_std = (C.c_void_p * max(len(vecs), 1))(*[_ptr(v[1]) for v in vecs])
+        items = maxout.items() if isinstance(maxout, dict) else enumerate(maxout)
+        groups, sizes = np.zeros(n, np.int32), [None] * n
+        for l, g in items:
+            if g is None or (np.isscalar(g) and int(g) == 0):
+                continue
+            if np.isscalar(g):
+                groups[l] = int(g)
+            else:
+                sizes[l] = np.ascontiguousarray(g, dtype=np.int32)
+                groups[l] = len(sizes[l])
+        self._mo_groups, self._mo_sizes_arr = groups, sizes
+        self._mo_sizes = (C.c_void_p * n)(*[_ptr(v) for v in sizes])
+        return _lib.FfnnLayers(len(types), _ptr(self._pre_type) if types else None, C.cast(self._pre_mean, C.c_void_p),
+                               C.cast(self._pre_std, C.c_void_p), self._mo_groups.ctypes.data, C.cast(self._mo_sizes, C.c_void_p))
 
     def __del__(self):
         try:
@@ -647,6 +684,11 @@ def write_prior(path, log_prior):
 def read_class_labels(path):
     """Nn::ClassLabelWrapper::load: Math::Vector<s32> xml file -> mapping int32[n_classes]"""
     return _read_vector("amx_nn_vector_read_s32", path, C.c_int, np.int32)
+
+
+def read_maxout_sizes(path):
+    """maxoutvar's `maxout-sizes`: Math::Vector<u32> file (xml, or bin:<path>) -> group sizes uint32[G]"""
+    return _read_vector("amx_nn_vector_read_u32", path, C.c_uint32, np.uint32)
 
 
 def write_class_labels(path, mapping):

@@ -12,7 +12,9 @@ LIB_PATH = os.environ.get("AMX_LIBRARY", os.path.join(_HERE, "librasr_amd.so")) 
 AMX_OK, AMX_ERR_INVALID, AMX_ERR_UNSUPPORTED, AMX_ERR_DEVICE, AMX_ERR_STATE = 0, -1, -2, -3, -4
 AMX_GMM_MAX, AMX_GMM_SUM, AMX_GMM_BATCH_FLOAT, AMX_GMM_SIMD, AMX_GMM_BATCH_INT, AMX_GMM_PRESELECTION_FLOAT, AMX_GMM_PRESELECTION_INT = 0, 1, 2, 3, 4, 5, 6
 AMX_GMM_VITERBI, AMX_GMM_BAUM_WELCH = 0, 1
-AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH = 0, 1, 2, 3
+AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AMX_ACT_ELU = 0, 1, 2, 3, 4
+AMX_NN_PRE_LOGARITHM, AMX_NN_PRE_MEAN_AND_VARIANCE = 1, 2
+AMX_NN_MAX_PRE = 4
 AMX_PREC_FP32, AMX_PREC_BF16, AMX_PREC_BF16X3, AMX_PREC_F16MX = 0, 1, 2, 3
 AMX_NN_TOP_LINEAR, AMX_NN_TOP_SOFTMAX = 0, 1
 AMX_ARCHIVE_READ, AMX_ARCHIVE_WRITE = 0, 1
@@ -72,6 +74,11 @@ class FfnnModel(C.Structure):
                 ("bias", C.c_void_p), ("activation", C.c_void_p), ("log_prior", C.c_void_p),
                 ("prior_scale", C.c_float), ("precision", C.c_int), ("n_classes", C.c_int), ("class_to_output", C.c_void_p),
                 ("tuning", C.c_char_p)]
+
+
+class FfnnLayers(C.Structure):
+    _fields_ = [("n_pre", C.c_int), ("pre_type", C.c_void_p), ("pre_mean", C.c_void_p), ("pre_stddev", C.c_void_p),
+                ("maxout_groups", C.c_void_p), ("maxout_sizes", C.c_void_p)]
 
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against amx.h
@@ -152,6 +159,7 @@ SIGNATURES = {
     "amx_mixture_set_view": (C.c_int, [_P, C.POINTER(GmmModel)]),
     "amx_mixture_set_destroy": (None, [_P]),
     "amx_ffnn_create": (C.c_int, [_P, C.POINTER(FfnnModel), C.POINTER(_P)]),
+    "amx_ffnn_create_ex": (C.c_int, [_P, C.POINTER(FfnnModel), C.POINTER(FfnnLayers), C.POINTER(_P)]),
     "amx_ffnn_destroy": (None, [_P]),
     "amx_ffnn_input_dim": (C.c_int, [_P]),
     "amx_ffnn_output_dim": (C.c_int, [_P]),
@@ -173,6 +181,7 @@ SIGNATURES = {
     "amx_nn_vector_write_f32": (C.c_int, [C.c_char_p, C.c_int, _P]),
     "amx_nn_vector_read_s32": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(_P)]),
     "amx_nn_vector_write_s32": (C.c_int, [C.c_char_p, C.c_int, _P]),
+    "amx_nn_vector_read_u32": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(_P)]),
     "amx_nn_matrix_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
     "amx_nn_matrix_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P]),
     "amx_free": (None, [_P]),

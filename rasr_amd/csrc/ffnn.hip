@@ -70,17 +70,78 @@ __device__ __forceinline__ float activate(float v) {
         return 1.f / (1.f + expf(-v));  // Math/FastMatrix.hh:802-808
     if (ACT == AMX_ACT_TANH)
         return tanhf(v);
+    if (ACT == AMX_ACT_ELU)
+        return v < 0.f ? expf(v) - 1.f : v;  // Math/FastMatrix.hh:1658-1667, alpha 1: std::exp on a float; a NaN stays NaN
     return v;
 }
 
+// ---- value sources of the operand pack kernels: what element (t, k) of the next GEMM's operand is (t < T, k < K; the rest is zero)
+// preprocessing layers of amx_ffnn_layers in front of layer 0 (AMX_NN_PRE_*), in order
+struct PreOps {
+    int          n;
+    int          type[AMX_NN_MAX_PRE];
+    const float* mean[AMX_NN_MAX_PRE];
+    const float* rstd[AMX_NN_MAX_PRE];  // (f32)1 / stddev, rounded on the host
+};
+
+// the input features of a network without preprocessing layers: f32 rows as they are
+struct RawSrc {
+    const float* x;
+    int          ldx;
+    __device__ __forceinline__ float operator()(int t, int k) const { return x[(size_t)t * ldx + k]; }
+};
+
+// the input features: f32 rows, through the preprocessing layers
+struct FeatSrc {
+    const float* x;
+    int          ldx;
+    PreOps       pre;
+    __device__ __forceinline__ float operator()(int t, int k) const {
+        float v = x[(size_t)t * ldx + k];
+#pragma unroll
+        for (int i = 0; i < AMX_NN_MAX_PRE; ++i) {
+            if (i >= pre.n)
+                break;
+            if (pre.type[i] == AMX_NN_PRE_LOGARITHM)
+                v = (float)log((double)v);  // Math::vr_log: the unqualified log on a float is ::log(double) there, narrowed
+            else {
+                v = v - pre.mean[i][k];  // addToAllColumns(mean, -1): x + (-1 * m), the product is exact
+                v = v * pre.rstd[i][k];  // divideRowsByScalars: scal((f32)1 / s)
+            }
+        }
+        return v;
+    }
+};
+
+// maxoutvar (Math::FastMatrix::maxoutvar, Math/FastMatrix.hh:840-860) over the f32 rows of the layer in front of it, which left
+// through the score epilogue as -(W x + b) (exact): output g = the first of act(-v) over its group, replaced only by a strictly
+// greater later element (a NaN in first position stays, a later NaN never wins)
+template<int ACT>
+struct MaxoutSrc {
+    const float* v;
+    int          ld;
+    const int*   off;
+    const int*   size;
+    __device__ __forceinline__ float operator()(int t, int g) const {
+        const float* r = v + (size_t)t * ld + off[g];
+        float        m = activate<ACT>(-r[0]);
+        for (int j = 1, n = size[g]; j < n; ++j) {
+            const float c = activate<ACT>(-r[j]);
+            if (c > m)
+                m = c;
+        }
+        return m;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
-// f32 frames -> bf16 [Tpad x Kpad], zero padded
-__global__ __launch_bounds__(256) void pack_input_bf16(const float* __restrict__ x, int ldx, int T, int K, bf16_t* __restrict__ out,
-                                                      int Kpad, int Tpad) {
+// f32 frames (or a maxout) -> bf16 [Tpad x Kpad], zero padded
+template<class S>
+__global__ __launch_bounds__(256) void pack_input_bf16(S src, int T, int K, bf16_t* __restrict__ out, int Kpad, int Tpad) {
     const long long n = (long long)Tpad * Kpad;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         int   t = (int)(i / Kpad), k = (int)(i - (long long)t * Kpad);
-        float v = (t < T && k < K) ? x[(size_t)t * ldx + k] : 0.f;
+        float v = (t < T && k < K) ? src(t, k) : 0.f;
         out[i]  = f2bf(v);
     }
 }
@@ -90,12 +151,12 @@ __global__ __launch_bounds__(256) void pack_input_bf16(const float* __restrict__
 // instead of one, relative error of a product ~2^-16 instead of 2^-8.  Operand rows are [hi plane | lo plane]; the GEMM kernels
 // stage both planes of a K-tile and issue the three products from one set of fragment reads (GemmCfg::X3).
 // features -> [Tpad x 2 seg] bf16
-__global__ __launch_bounds__(256) void pack_input_bf16x3(const float* __restrict__ x, int ldx, int T, int K, bf16_t* __restrict__ out,
-                                                        int seg, int Tpad) {
+template<class S>
+__global__ __launch_bounds__(256) void pack_input_bf16x3(S src, int T, int K, bf16_t* __restrict__ out, int seg, int Tpad) {
     const long long n = (long long)Tpad * seg;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int    t = (int)(i / seg), k = (int)(i - (long long)t * seg);
-        const float  v = (t < T && k < K) ? x[(size_t)t * ldx + k] : 0.f;
+        const float  v = (t < T && k < K) ? src(t, k) : 0.f;
         const bf16_t hi = f2bf(v);
         bf16_t*      o = out + (size_t)t * 2 * seg + k;
         o[0]           = hi;
@@ -236,12 +297,13 @@ __global__ __launch_bounds__(256) void precomputed_score_kernel(const float* __r
     }
 }
 
-__global__ __launch_bounds__(256) void pack_input_f32(const float* __restrict__ x, int ldx, int T, int K, float* __restrict__ out,
-                                                     int Kpad, int Tpad) {
+// f32 frames (or a maxout) -> f32 [Tpad x Kpad], zero padded; with Kpad = K and Tpad = T: the plain [T x K] rows
+template<class S>
+__global__ __launch_bounds__(256) void pack_input_f32(S src, int T, int K, float* __restrict__ out, int Kpad, int Tpad) {
     const long long n = (long long)Tpad * Kpad;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         int t = (int)(i / Kpad), k = (int)(i - (long long)t * Kpad);
-        out[i] = (t < T && k < K) ? x[(size_t)t * ldx + k] : 0.f;
+        out[i] = (t < T && k < K) ? src(t, k) : 0.f;
     }
 }
 
@@ -1494,6 +1556,13 @@ struct amx_ffnn {
     // AMX_PREC_F16MX: host-mapped word the kernels set when a value leaves the f16 range (sticky: every later call fails)
     unsigned* h_overflow = nullptr;
     unsigned* d_overflow = nullptr;
+    // amx_ffnn_layers: preprocessing of the features (device vectors in pre), maxoutvar behind hidden layers
+    amx::PreOps         pre{};
+    std::vector<float*> d_pre;      // the mean / reciprocal stddev vectors pre points to
+    std::vector<int>    mo_groups;  // per layer: G outputs of its maxout, 0 = none
+    std::vector<int*>   d_mo_off, d_mo_size;  // per layer [G] first unit and size of every group (nullptr without maxout)
+    int    mo_width = 0;            // widest layer in front of a maxout
+    float* d_mo     = nullptr;      // its f32 rows -(W x + b) [cap_T x mo_width]
     size_t elt() const { return precision == AMX_PREC_FP32 ? 4 : 2; }
     bool   mfma_bf16() const { return precision != AMX_PREC_FP32; }  // everything but the exact-f32 kernels (fused statistics, HIP graphs)
     bool   is_mx() const { return precision == AMX_PREC_F16MX; }
@@ -1523,8 +1592,12 @@ int ensure_workspace(amx_ffnn* h, int Tpad) {
     hipFree(h->d_in);
     hipFree(h->d_act[0]);
     hipFree(h->d_act[1]);
+    hipFree(h->d_mo);
     h->d_in = h->d_act[0] = h->d_act[1] = nullptr;
+    h->d_mo                             = nullptr;
     h->cap_T                            = 0;
+    if (h->mo_width > 0)
+        AMX_HIP(hipMalloc((void**)&h->d_mo, (size_t)Tpad * h->mo_width * 4));
     const size_t planes = h->precision == AMX_PREC_BF16X3 ? 2 : 1;  // split bf16: rows are [hi plane | lo plane]
     if (h->is_mx()) {  // 25 KB blocks per (256 rows, 32 k); the split-K workspace is sized once, by size_split_k_workspace
         AMX_HIP(hipMalloc(&h->d_in, (size_t)(Tpad / 256) * (h->Kpad[0] / 32) * amx::mx::BLK));
@@ -1890,6 +1963,41 @@ case 11:   // round 5's hidden-layer loop (no read-ahead): A/B runs
     }
 }
 
+// f(std::integral_constant<int, ACT>) for the layer's activation; NONE_ONLY: only the AMX_ACT_NONE case is instantiated
+template<bool NONE_ONLY = false, class F>
+void with_act(int act, F&& f) {
+    using std::integral_constant;
+    if constexpr (NONE_ONLY)
+        f(integral_constant<int, AMX_ACT_NONE>());
+    else
+        switch (act) {
+            case AMX_ACT_RELU: f(integral_constant<int, AMX_ACT_RELU>()); break;
+            case AMX_ACT_SIGMOID: f(integral_constant<int, AMX_ACT_SIGMOID>()); break;
+            case AMX_ACT_TANH: f(integral_constant<int, AMX_ACT_TANH>()); break;
+            case AMX_ACT_ELU: f(integral_constant<int, AMX_ACT_ELU>()); break;
+            default: f(integral_constant<int, AMX_ACT_NONE>()); break;
+        }
+}
+
+// the operand of the next GEMM in the handle's format from a value source (amx::FeatSrc: the features; amx::MaxoutSrc: a maxout):
+// padded rows [Tpad x Kp] (f32, bf16, split bf16 [hi | lo] with the lo plane at column Kp), or f16mx blocks [Tpad / 256][Kp / 32] with
+// the overflow flag set for a value outside the f16 range
+template<class S>
+void pack_operand(amx_ffnn* h, const S& src, int T, int K, void* out, int Kp, int Tpad) {
+    hipStream_t st     = h->ctx->stream;
+    const int   blocks = (int)std::min<long long>(4096, ((long long)Tpad * Kp + 255) / 256);
+    if (h->is_mx()) {
+        const int b2 = (int)std::min<long long>(8192, ((long long)Tpad * (Kp / 32) * 2 + 255) / 256);
+        hipLaunchKernelGGL(amx::mx::pack_input_mx<S>, dim3(b2), dim3(256), 0, st, src, T, K, (char*)out, Kp / 32, Tpad, h->d_overflow);
+    }
+    else if (h->precision == AMX_PREC_BF16X3)
+        hipLaunchKernelGGL(amx::pack_input_bf16x3<S>, dim3(blocks), dim3(256), 0, st, src, T, K, (amx::bf16_t*)out, Kp, Tpad);
+    else if (h->precision == AMX_PREC_BF16)
+        hipLaunchKernelGGL(amx::pack_input_bf16<S>, dim3(blocks), dim3(256), 0, st, src, T, K, (amx::bf16_t*)out, Kp, Tpad);
+    else
+        hipLaunchKernelGGL(amx::pack_input_f32<S>, dim3(blocks), dim3(256), 0, st, src, T, K, (float*)out, Kp, Tpad);
+}
+
 template<bool LAST>
 int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
     hipStream_t            st = h->ctx->stream;
@@ -1901,37 +2009,23 @@ int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo,
         hipEventCreate(&e1);
         hipEventRecord(e0, st);
     }
+    // LAST (the score epilogue: the output layer, or a hidden layer leaving as f32 rows -(W x + b)) never applies an activation: only
+    // its AMX_ACT_NONE instantiation exists
     const int act = LAST ? AMX_ACT_NONE : h->act[l];
-    if (h->is_mx()) {  // LAST with l < n_layers - 1: the last hidden layer as f32 rows (amx_ffnn_forward_hidden_dev)
-        switch (act) {
-            case AMX_ACT_RELU: launch_mx_cfg<AMX_ACT_RELU, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); break;
-            case AMX_ACT_SIGMOID: launch_mx_cfg<AMX_ACT_SIGMOID, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); break;
-            case AMX_ACT_TANH: launch_mx_cfg<AMX_ACT_TANH, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); break;
-            default: launch_mx_cfg<AMX_ACT_NONE, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); break;
-        }
+    if (h->is_mx()) {  // LAST with l < n_layers - 1: a hidden layer as f32 rows (amx_ffnn_forward_hidden_dev, maxout)
+        with_act<LAST>(act, [&](auto a) { launch_mx_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); });
     }
     else if (h->mfma_bf16()) {
-        switch (act) {
-            case AMX_ACT_RELU: launch_bf16_cfg<AMX_ACT_RELU, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            case AMX_ACT_SIGMOID: launch_bf16_cfg<AMX_ACT_SIGMOID, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            case AMX_ACT_TANH: launch_bf16_cfg<AMX_ACT_TANH, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            default: launch_bf16_cfg<AMX_ACT_NONE, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-        }
+        with_act<LAST>(act, [&](auto a) { launch_bf16_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad); });
     }
     else {
         const int ntn = h->Npad[l] / amx::BN, ntt = Tpad / amx::BT;
         dim3      grid(ntn * ntt), block(256);
         const int nv = h->out[l];
-#define AMX_L(ACT)                                                                                                   \
-    hipLaunchKernelGGL((amx::gemm_f32_kernel<ACT, LAST>), grid, block, 0, st, (const float*)h->d_W[l], (const float*)x, \
-                       h->d_bias[l], (float*)out, h->Kpad[l], ldx, ldo, nv, T, ntn);
-        switch (act) {
-            case AMX_ACT_RELU: AMX_L(AMX_ACT_RELU) break;
-            case AMX_ACT_SIGMOID: AMX_L(AMX_ACT_SIGMOID) break;
-            case AMX_ACT_TANH: AMX_L(AMX_ACT_TANH) break;
-            default: AMX_L(AMX_ACT_NONE) break;
-        }
-#undef AMX_L
+        with_act<LAST>(act, [&](auto a) {
+            hipLaunchKernelGGL((amx::gemm_f32_kernel<decltype(a)::value, LAST>), grid, block, 0, st, (const float*)h->d_W[l], (const float*)x,
+                               h->d_bias[l], (float*)out, h->Kpad[l], ldx, ldo, nv, T, ntn);
+        });
     }
     if (time_max) {
         hipEventRecord(e1, st);
@@ -1941,11 +2035,42 @@ int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo,
     return AMX_OK;
 }
 
+// hidden layer l with a maxout behind it: W x + b leaves through the score epilogue as exact f32 rows -(W x + b) (d_mo), then the maxout
+// of act(-v) becomes the next operand (dst: Kp columns, Trows rows, zero padded; export: plain f32 rows [T x G], Kp = G, Trows = T)
+int launch_maxout_layer(amx_ffnn* h, int l, const void* x, int ldx, void* dst, int Kp, int T, int Trows, int Tpad, bool export_f32) {
+    float* const    pm = h->cur_part_min;  // the arg-min partials belong to the output layer
+    unsigned* const pi = h->cur_part_idx;
+    h->cur_part_min    = nullptr;
+    h->cur_part_idx    = nullptr;
+    const int r        = launch_layer<true>(h, l, x, ldx, h->d_mo, h->out[l], T, Tpad);
+    h->cur_part_min    = pm;
+    h->cur_part_idx    = pi;
+    if (r != AMX_OK)
+        return r;
+    const int G = h->mo_groups[l];
+    amx::ScopedKernelTimer timer(h->ctx, "ffnn_maxout");
+    with_act(h->act[l], [&](auto a) {
+        const amx::MaxoutSrc<decltype(a)::value> src{h->d_mo, h->out[l], h->d_mo_off[l], h->d_mo_size[l]};
+        if (export_f32) {
+            const int blocks = (int)std::min<long long>(4096, ((long long)Trows * Kp + 255) / 256);
+            hipLaunchKernelGGL(amx::pack_input_f32<decltype(src)>, dim3(blocks), dim3(256), 0, h->ctx->stream, src, T, G, (float*)dst, Kp, Trows);
+        }
+        else
+            pack_operand(h, src, T, G, dst, Kp, Trows);
+    });
+    AMX_HIP(hipGetLastError());
+    return AMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
+    return amx_ffnn_create_ex(ctx, m, nullptr, out);
+}
+
+int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_layers* ext, amx_ffnn** out) {
     AMX_REQUIRE(ctx && m && out, AMX_ERR_INVALID, "amx_ffnn_create: NULL argument");
     *out = nullptr;
     AMX_REQUIRE(m->n_layers >= 1 && m->in_dim && m->out_dim && m->W && m->bias && m->activation, AMX_ERR_INVALID,
@@ -1953,12 +2078,63 @@ int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
     AMX_REQUIRE(m->precision == AMX_PREC_FP32 || m->precision == AMX_PREC_BF16 || m->precision == AMX_PREC_BF16X3 ||
                         m->precision == AMX_PREC_F16MX,
                 AMX_ERR_INVALID, "amx_ffnn_create: unknown precision");
+    // ---- amx_ffnn_layers: preprocessing layers (Nn/PreprocessingLayer.cc) and maxoutvar group sizes (Nn/ActivationLayer.cc:404-470)
+    const int        n_pre = ext ? ext->n_pre : 0;
+    std::vector<int> mo_groups((size_t)m->n_layers, 0);
+    std::vector<std::vector<int>> mo_size((size_t)m->n_layers);
+    AMX_REQUIRE(n_pre >= 0 && n_pre <= AMX_NN_MAX_PRE, AMX_ERR_INVALID, "amx_ffnn_create_ex: %d preprocessing layers (0 to %d)", n_pre,
+                AMX_NN_MAX_PRE);
+    AMX_REQUIRE(n_pre == 0 || ext->pre_type, AMX_ERR_INVALID, "amx_ffnn_create_ex: %d preprocessing layers without pre_type", n_pre);
+    for (int i = 0; i < n_pre; ++i) {
+        const int ty = ext->pre_type[i];
+        AMX_REQUIRE(ty == AMX_NN_PRE_LOGARITHM || ty == AMX_NN_PRE_MEAN_AND_VARIANCE, AMX_ERR_INVALID,
+                    "amx_ffnn_create_ex: preprocessing layer %d: unknown type %d", i, ty);
+        if (ty == AMX_NN_PRE_MEAN_AND_VARIANCE) {
+            AMX_REQUIRE(ext->pre_mean && ext->pre_mean[i], AMX_ERR_INVALID,
+                        "amx_ffnn_create_ex: preprocessing layer %d (mean-and-variance-normalization) has no mean vector", i);
+            AMX_REQUIRE(ext->pre_stddev && ext->pre_stddev[i], AMX_ERR_INVALID,
+                        "amx_ffnn_create_ex: preprocessing layer %d (mean-and-variance-normalization) has no standard deviation vector", i);
+        }
+    }
+    if (ext && ext->maxout_groups)
+        for (int l = 0; l < m->n_layers; ++l) {
+            const int G = ext->maxout_groups[l];
+            if (G == 0)
+                continue;
+            AMX_REQUIRE(G > 0, AMX_ERR_INVALID, "amx_ffnn_create_ex: layer %d: maxout with %d outputs", l, G);
+            AMX_REQUIRE(l + 1 < m->n_layers, AMX_ERR_INVALID, "amx_ffnn_create_ex: layer %d is the output layer: no maxout behind it", l);
+            AMX_REQUIRE(m->out_dim[l] > 0, AMX_ERR_INVALID, "amx_ffnn_create: layer %d is empty", l);
+            const int* sz = ext->maxout_sizes ? ext->maxout_sizes[l] : nullptr;
+            auto&      v  = mo_size[l];
+            if (sz) {  // maxout-sizes: require_eq(getInputDimension(0), sum of the sizes)
+                long sum = 0;
+                for (int g = 0; g < G; ++g) {
+                    AMX_REQUIRE(sz[g] >= 1, AMX_ERR_INVALID, "amx_ffnn_create_ex: layer %d: maxout group %d has size %d (at least 1)", l, g, sz[g]);
+                    sum += sz[g];
+                }
+                AMX_REQUIRE(sum == m->out_dim[l], AMX_ERR_INVALID,
+                            "amx_ffnn_create_ex: layer %d: maxout group sizes add up to %ld, the layer has %d outputs "
+                            "(require_eq(getInputDimension(0), inputsize_))", l, sum, m->out_dim[l]);
+                v.assign(sz, sz + G);
+            }
+            else {  // maxout-size: require_eq(getInputDimension(0), maxoutSize_ * getOutputDimension())
+                AMX_REQUIRE(m->out_dim[l] % G == 0, AMX_ERR_INVALID,
+                            "amx_ffnn_create_ex: layer %d: %d outputs do not split into %d maxout groups of one size "
+                            "(require_eq(getInputDimension(0), maxoutSize_ * getOutputDimension()))", l, m->out_dim[l], G);
+                v.assign((size_t)G, m->out_dim[l] / G);
+            }
+            mo_groups[l] = G;
+        }
     for (int l = 0; l < m->n_layers; ++l) {
         AMX_REQUIRE(m->in_dim[l] > 0 && m->out_dim[l] > 0 && m->W[l], AMX_ERR_INVALID, "amx_ffnn_create: layer %d is empty", l);
-        if (l > 0)
+        if (l > 0 && mo_groups[l - 1] > 0)
+            AMX_REQUIRE(m->in_dim[l] == mo_groups[l - 1], AMX_ERR_INVALID,
+                        "amx_ffnn_create_ex: layer %d input dimension %d != %d outputs of the maxout behind layer %d", l, m->in_dim[l],
+                        mo_groups[l - 1], l - 1);
+        else if (l > 0)
             AMX_REQUIRE(m->in_dim[l] == m->out_dim[l - 1], AMX_ERR_INVALID,
                         "amx_ffnn_create: layer %d input dimension %d != previous output %d", l, m->in_dim[l], m->out_dim[l - 1]);
-        AMX_REQUIRE(m->activation[l] >= AMX_ACT_NONE && m->activation[l] <= AMX_ACT_TANH, AMX_ERR_INVALID,
+        AMX_REQUIRE(m->activation[l] >= AMX_ACT_NONE && m->activation[l] <= AMX_ACT_ELU, AMX_ERR_INVALID,
                     "amx_ffnn_create: unknown activation in layer %d", l);
     }
     // Nn::BatchFeatureScorer: "output layer must be of type 'linear+softmax'" with the softmax switched off
@@ -2110,10 +2286,13 @@ int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
         *h->h_overflow = 0;
     }
     long      best_flops = -1;
+    h->mo_groups = mo_groups;
     for (int l = 0; l < m->n_layers; ++l) {
         h->in.push_back(m->in_dim[l]);
         h->out.push_back(out_dim[l]);
         h->act.push_back(m->activation[l]);
+        if (mo_groups[l] > 0)
+            h->mo_width = std::max(h->mo_width, out_dim[l]);
         // hidden activations are stored with a row stride of Npad(l-1) >= Kpad(l)
         h->Kpad.push_back(pad_to(m->in_dim[l], kmult));
         h->Npad.push_back(pad_to(out_dim[l], amx::PAD_NT));
@@ -2214,6 +2393,49 @@ int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
         }
         h->d_bias.push_back(db);
     }
+    // preprocessing vectors: the mean as given, the standard deviation as its f32 reciprocal (divideRowsByScalars' (T)1.0 / s)
+    const int K0 = m->in_dim[0];
+    h->pre.n     = n_pre;
+    for (int i = 0; i < n_pre; ++i) {
+        h->pre.type[i] = ext->pre_type[i];
+        if (ext->pre_type[i] != AMX_NN_PRE_MEAN_AND_VARIANCE)
+            continue;
+        std::vector<float> mr((size_t)2 * K0);
+        for (int k = 0; k < K0; ++k) {
+            mr[k]      = ext->pre_mean[i][k];
+            mr[K0 + k] = 1.0f / ext->pre_stddev[i][k];
+        }
+        float* d = nullptr;
+        if (hipMalloc((void**)&d, mr.size() * 4) != hipSuccess || hipMemcpy(d, mr.data(), mr.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(d);
+            amx::set_error("amx_ffnn_create_ex: device allocation of preprocessing layer %d failed", i);
+            amx_ffnn_destroy(h);
+            return AMX_ERR_DEVICE;
+        }
+        h->d_pre.push_back(d);
+        h->pre.mean[i] = d;
+        h->pre.rstd[i] = d + K0;
+    }
+    // maxout groups: first unit and size of each
+    h->d_mo_off.assign((size_t)m->n_layers, nullptr);
+    h->d_mo_size.assign((size_t)m->n_layers, nullptr);
+    for (int l = 0; l < m->n_layers; ++l) {
+        const int G = mo_groups[l];
+        if (G == 0)
+            continue;
+        std::vector<int> off((size_t)G, 0);
+        for (int g = 1; g < G; ++g)
+            off[g] = off[g - 1] + mo_size[l][g - 1];
+        if (hipMalloc((void**)&h->d_mo_off[l], (size_t)G * 4) != hipSuccess || hipMalloc((void**)&h->d_mo_size[l], (size_t)G * 4) != hipSuccess ||
+            hipMemcpy(h->d_mo_off[l], off.data(), (size_t)G * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(h->d_mo_size[l], mo_size[l].data(), (size_t)G * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            amx::set_error("amx_ffnn_create_ex: device allocation of the maxout behind layer %d failed", l);
+            amx_ffnn_destroy(h);
+            return AMX_ERR_DEVICE;
+        }
+    }
     size_split_k_workspace(h);
     *out = h;
     return AMX_OK;
@@ -2240,6 +2462,13 @@ void amx_ffnn_destroy(amx_ffnn* h) {
     if (h->h_overflow)
         hipHostFree(h->h_overflow);
     hipFree(h->d_ks_ws);
+    hipFree(h->d_mo);
+    for (float* p : h->d_pre)
+        hipFree(p);
+    for (int* p : h->d_mo_off)
+        hipFree(p);
+    for (int* p : h->d_mo_size)
+        hipFree(p);
     for (auto& kv : h->graphs)
         if (kv.second)  // nullptr marks a signature seen once
             hipGraphExecDestroy(kv.second);
@@ -2350,23 +2579,13 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
         if (r != AMX_OK)
             return r;
         const float* x = feats_dev + (size_t)t0 * feats_stride;
+        const amx::FeatSrc feats{x, feats_stride, h->pre};  // the preprocessing layers run inside the pack kernel
         {
             amx::ScopedKernelTimer timer(h->ctx, "ffnn_pack");
-            const int blocks = (int)std::min<long long>(4096, ((long long)Tpad * h->Kpad[0] + 255) / 256);
-            if (h->is_mx()) {
-                const int b2 = (int)std::min<long long>(8192, ((long long)Tpad * (h->Kpad[0] / 32) * 2 + 255) / 256);
-                hipLaunchKernelGGL(amx::mx::pack_input_mx, dim3(b2), dim3(256), 0, h->ctx->stream, x, feats_stride, Tc, h->in[0], (char*)h->d_in,
-                                   h->Kpad[0] / 32, Tpad, h->d_overflow);
-            }
-            else if (h->precision == AMX_PREC_BF16X3)
-                hipLaunchKernelGGL(amx::pack_input_bf16x3, dim3(blocks), dim3(256), 0, h->ctx->stream, x, feats_stride, Tc, h->in[0],
-                                   (amx::bf16_t*)h->d_in, h->Kpad[0], Tpad);
-            else if (h->precision == AMX_PREC_BF16)
-                hipLaunchKernelGGL(amx::pack_input_bf16, dim3(blocks), dim3(256), 0, h->ctx->stream, x, feats_stride, Tc, h->in[0],
-                                   (amx::bf16_t*)h->d_in, h->Kpad[0], Tpad);
-            else
-                hipLaunchKernelGGL(amx::pack_input_f32, dim3(blocks), dim3(256), 0, h->ctx->stream, x, feats_stride, Tc, h->in[0],
-                                   (float*)h->d_in, h->Kpad[0], Tpad);
+            if (h->pre.n > 0)
+                pack_operand(h, feats, Tc, h->in[0], h->d_in, h->Kpad[0], Tpad);
+            else  // a network without preprocessing layers packs its features with the kernels it always had
+                pack_operand(h, amx::RawSrc{x, feats_stride}, Tc, h->in[0], h->d_in, h->Kpad[0], Tpad);
             AMX_HIP(hipGetLastError());
         }
         const void* cur = h->d_in;
@@ -2401,9 +2620,14 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
                 // -(W x + b) in f32 (exact), act(-v) restores the activation; a network without hidden layers exports its input
                 const int H = h->in[L - 1];
                 float*    dst = hidden_out + (size_t)t0 * H;
-                if (L == 1) {
-                    const int blocks = (int)std::min<long long>(8192, ((long long)Tc * H + 255) / 256);
-                    hipLaunchKernelGGL(amx::export_hidden_kernel<0>, dim3(blocks), dim3(256), 0, h->ctx->stream, (const void*)x, feats_stride, 0, Tc, H, dst);
+                if (L == 1) {  // the preprocessed features (forwardHiddenLayers runs the preprocessing layers), exact f32 rows
+                    const int blocks = (int)std::min<long long>(4096, ((long long)Tc * H + 255) / 256);
+                    hipLaunchKernelGGL(amx::pack_input_f32<amx::FeatSrc>, dim3(blocks), dim3(256), 0, h->ctx->stream, feats, Tc, H, dst, H, Tc);
+                }
+                else if (l == L - 2 && h->mo_groups[l] > 0) {  // the maxout of the f32 rows, written as f32 rows [Tc x G]
+                    r = launch_maxout_layer(h, l, cur, ldx, dst, H, Tc, Tc, Tpad, true);
+                    if (r != AMX_OK)
+                        return r;
                 }
                 else if (l == L - 2) {
                     r = launch_layer<true>(h, l, cur, ldx, dst, H, Tc, Tpad);
@@ -2411,12 +2635,9 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
                         return r;
                     const long long n = (long long)Tc * H;
                     const int blocks = (int)std::min<long long>(8192, (n + 255) / 256);
-                    switch (h->act[l]) {
-                        case AMX_ACT_RELU: hipLaunchKernelGGL(amx::mx::neg_act_kernel<AMX_ACT_RELU>, dim3(blocks), dim3(256), 0, h->ctx->stream, dst, n); break;
-                        case AMX_ACT_SIGMOID: hipLaunchKernelGGL(amx::mx::neg_act_kernel<AMX_ACT_SIGMOID>, dim3(blocks), dim3(256), 0, h->ctx->stream, dst, n); break;
-                        case AMX_ACT_TANH: hipLaunchKernelGGL(amx::mx::neg_act_kernel<AMX_ACT_TANH>, dim3(blocks), dim3(256), 0, h->ctx->stream, dst, n); break;
-                        default: hipLaunchKernelGGL(amx::mx::neg_act_kernel<AMX_ACT_NONE>, dim3(blocks), dim3(256), 0, h->ctx->stream, dst, n); break;
-                    }
+                    with_act(h->act[l], [&](auto a) {
+                        hipLaunchKernelGGL(amx::mx::neg_act_kernel<decltype(a)::value>, dim3(blocks), dim3(256), 0, h->ctx->stream, dst, n);
+                    });
                 }
                 AMX_HIP(hipGetLastError());
                 if (L == 1 || l == L - 2)
@@ -2448,6 +2669,12 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
                 else if (r == AMX_OK && stats)  // fp32 parity path: separate arg-min pass over the scores
                     r = amx_stats_accumulate_dev(h->ctx, sc, Tc, h->out[l], best_state_dev ? best_state_dev + t0 : nullptr, counts_dev,
                                                  score_sum_dev);
+            }
+            else if (h->mo_groups[l] > 0) {  // maxout: the next layer's operand [Tpad x Kpad(l + 1)] in the handle's format
+                void* dst = h->d_act[l & 1];
+                r         = launch_maxout_layer(h, l, cur, ldx, dst, h->Kpad[l + 1], Tc, Tpad, Tpad, false);
+                cur       = dst;
+                ldx       = h->is_mx() ? h->Kpad[l + 1] / 32 : planes * h->Kpad[l + 1];
             }
             else {
                 void* dst = h->d_act[l & 1];  // split bf16: the epilogue applies the activation and writes both planes

@@ -185,10 +185,10 @@ __device__ __forceinline__ void lane_store(char* blk, int r, int hh, const LaneP
     *(uint4*)(blk + r_off(r, hh))     = p.rec;
 }
 
-// f32 frames [T x K] (row stride ldx) -> blocks [Tpad / 256][KT].  Two lanes per (frame, K-tile): lane half hh holds the natural
-// indices 8 g + 4 hh + e, exactly like an accumulator lane of the GEMM epilogue, so both go through lane_pack / lane_store.
-__global__ __launch_bounds__(256) void pack_input_mx(const float* __restrict__ x, int ldx, int T, int K, char* __restrict__ out, int KT, int Tpad,
-                                                    unsigned* __restrict__ overflow) {
+// f32 frames [T x K] (or a maxout: the value source S) -> blocks [Tpad / 256][KT].  Two lanes per (frame, K-tile): lane half hh holds
+// the natural indices 8 g + 4 hh + e, exactly like an accumulator lane of the GEMM epilogue, so both go through lane_pack / lane_store.
+template<class S>
+__global__ __launch_bounds__(256) void pack_input_mx(S src, int T, int K, char* __restrict__ out, int KT, int Tpad, unsigned* __restrict__ overflow) {
     const long long n = (long long)Tpad * KT * 2;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int       hh = (int)(i & 1);
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void pack_input_mx(const float* __restrict__ x
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int   k = kt * 32 + 8 * g + 4 * hh + e;
-                const float v = (t < T && k < K) ? x[(size_t)t * ldx + k] : 0.f;
+                const float v = (t < T && k < K) ? src(t, k) : 0.f;  // the range check sees the preprocessed value
                 a[4 * g + e]  = v;
                 m             = (v != v) ? __builtin_inff() : fmaxf(m, fabsf(v));  // a NaN counts as out of range (fmaxf would drop it)
             }

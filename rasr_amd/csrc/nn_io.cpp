@@ -10,6 +10,7 @@
 #include <cctype>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -161,6 +162,10 @@ static int vector_read_xml(const char* path, const char* type, int* n, T** data,
             }
             break;
         }
+        if (std::is_unsigned<T>::value && !(x >= 0.0)) {  // a u32 vector holds no negative number
+            amx::set_error("%s: '%s': %g is not an unsigned value", who, path, x);
+            return AMX_ERR_INVALID;
+        }
         v.push_back((T)x);
         c = end;
     }
@@ -247,6 +252,33 @@ int amx_nn_vector_read_s32(const char* path, int* n, int** data) {
     *n    = 0;
     const char* p = strncmp(path, "xml:", 4) == 0 ? path + 4 : path;
     return vector_read_xml<int>(p, "s32", n, data, "amx_nn_vector_read_s32");
+}
+
+// Math::Vector<u32> (the maxoutvar layer's `maxout-sizes` file, Nn/ActivationLayer.cc:404-520): XML `<vector-u32>` or `bin:` (u32 n +
+// raw elements); Math/Module.cc:28-29 registers both formats for u32
+int amx_nn_vector_read_u32(const char* path, int* n, uint32_t** data) {
+    AMX_REQUIRE(path && n && data, AMX_ERR_INVALID, "amx_nn_vector_read_u32: NULL argument");
+    *data = nullptr;
+    *n    = 0;
+    if (strncmp(path, "bin:", 4) == 0) {
+        FILE* f = fopen(path + 4, "rb");
+        AMX_REQUIRE(f, AMX_ERR_INVALID, "amx_nn_vector_read_u32: cannot open '%s'", path + 4);
+        uint32_t  sz = 0;
+        bool      ok = read_u32(f, &sz) && sz < (1u << 30);
+        uint32_t* d  = ok ? (uint32_t*)malloc(std::max<size_t>(sz, 1) * 4) : nullptr;
+        ok           = ok && d && fread(d, 4, sz, f) == sz;
+        fclose(f);
+        if (!ok) {
+            free(d);
+            amx::set_error("amx_nn_vector_read_u32: '%s' is not a binary Math::Vector<u32>", path + 4);
+            return AMX_ERR_INVALID;
+        }
+        *n    = (int)sz;
+        *data = d;
+        return AMX_OK;
+    }
+    const char* p = strncmp(path, "xml:", 4) == 0 ? path + 4 : path;
+    return vector_read_xml<uint32_t>(p, "u32", n, data, "amx_nn_vector_read_u32");
 }
 
 int amx_nn_vector_write_s32(const char* path, int n, const int* data) {

@@ -166,6 +166,13 @@ public:
         if (amx_ffnn_create(ctx, &model, &h_) != AMX_OK)
             throw std::runtime_error(amx_last_error());
     }
+    /** a network with preprocessing layers, ELU or maxoutvar layers (amx_ffnn_create_ex; INTEGRATION.md says how the adapter folds
+     *  RASR's layer list into model + layers) */
+    FfnnBackend(amx_ctx* ctx, const amx_ffnn_model& model, const amx_ffnn_layers& layers)
+            : h_(nullptr), block_(ctx) {
+        if (amx_ffnn_create_ex(ctx, &model, &layers, &h_) != AMX_OK)
+            throw std::runtime_error(amx_last_error());
+    }
     ~FfnnBackend() { amx_ffnn_destroy(h_); }
     unsigned nEmissions() const { return (unsigned)amx_ffnn_output_dim(h_); }
     unsigned dimension() const { return (unsigned)amx_ffnn_input_dim(h_); }
