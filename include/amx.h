@@ -200,6 +200,29 @@ int  amx_mfcc_plan_frame_offsets(const amx_mfcc_plan* p, long* frame_offsets /*[
 int  amx_mfcc_run_plan_dev(amx_mfcc* h, const amx_mfcc_plan* p, const float* pcm_dev, float* ceps_dev);
 int  amx_mfcc_run_plan_dev_s16(amx_mfcc* h, const amx_mfcc_plan* p, const int16_t* pcm_dev, float* ceps_dev);
 
+/* Vocal tract length normalisation in the filter bank: signal-filterbank's
+ *     warping-function = nest(linear-2($(warping-factor), limit), mel)      (bark for PLP)
+ * (Signal/Filterbank.cc:798-816, Math/AnalyticFunctionFactory.cc:394-430), with the factor chosen per segment.  linear-2 is the
+ * two-piece linear function of slope `factor` up to limit * fs/2 that maps fs/2 onto itself (a factor > 1: the inverse of the one
+ * built for 1 / factor); it is applied in front of cfg->warping, which still selects mel or bark.  A handle holds one filter bank per
+ * factor, all built and uploaded at creation; factor 1 gives the unwarped bank bit for bit.  All banks must have the same number of
+ * filters (AMX_ERR_INVALID naming the two factors otherwise).  Every entry point that takes no factor (amx_mfcc_run*,
+ * amx_mfcc_plan_create, amx_mfcc_tables) uses factors[0].  A plan names one of the handle's factors per segment (exactly, else
+ * AMX_ERR_INVALID naming the segment); the kernel picks the bank per tile. */
+#define AMX_MFCC_MAX_WARPING_FACTORS 64
+typedef struct {
+    double        limit;      /* linear-2's second argument, in (0, 1); RASR recipes use 0.875 */
+    int           n_factors;  /* 1 .. AMX_MFCC_MAX_WARPING_FACTORS */
+    const double* factors;    /* [n_factors] each finite and > 0, no duplicates; factors[0] is the handle's default */
+} amx_mfcc_vtln;
+int amx_mfcc_create_vtln(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out);
+int amx_mfcc_plan_create_vtln(amx_mfcc* h, int n_seg, const long* sample_offsets /*[n_seg+1]*/, const double* warping_factor /*[n_seg]*/,
+                              amx_mfcc_plan** out);
+/* amx_mfcc_tables for the bank of one of the handle's factors (AMX_ERR_INVALID for any other factor; a handle made by
+ * amx_mfcc_create has the one factor 1) */
+int amx_mfcc_tables_vtln(const amx_mfcc* h, double warping_factor, float* window, int* filter_start, int* filter_end,
+                         int* filter_offset, float* filter_weights, float* dct);
+
 /* ------------------------------------------------------------------ sample stream in front of the feature chains (samples.flow)
  * signal-dc-detection (Signal::DcDetection, src/Signal/DcDetection.cc:90-235): a host-side scan over one segment's samples that tells
  * the caller which sample ranges reach the feature chain.  Runs of at least min-dc-length seconds whose samples stay within

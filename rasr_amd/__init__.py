@@ -222,13 +222,17 @@ class Context:
 
 
 class _Plan:
-    def __init__(self, owner, sample_offsets):
+    def __init__(self, owner, sample_offsets, warping_factors=None):
         self.owner = owner
         self.L = owner.L
         off = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         self.n_seg = len(off) - 1
         h = C.c_void_p()
-        _lib.check(self.L.amx_mfcc_plan_create(owner.h, self.n_seg, off.ctypes.data, C.byref(h)))
+        if warping_factors is None:
+            _lib.check(self.L.amx_mfcc_plan_create(owner.h, self.n_seg, off.ctypes.data, C.byref(h)))
+        else:  # VTLN: one of the handle's warping factors per segment
+            wf = np.ascontiguousarray(np.broadcast_to(np.asarray(warping_factors, np.float64), (self.n_seg,)))
+            _lib.check(self.L.amx_mfcc_plan_create_vtln(owner.h, self.n_seg, off.ctypes.data, wf.ctypes.data, C.byref(h)))
         self.h = h
         self.total_frames = int(self.L.amx_mfcc_plan_total_frames(h))
         fo = np.zeros(self.n_seg + 1, np.int64)
@@ -299,17 +303,27 @@ class MfccExtractor:
     def __init__(self, ctx, nr_cepstrum_coefficients=16, filter_width=268.258, sample_rate=16000.0, alpha=1.0,
                  length=0.025, shift=0.01, maximum_input_size=0.025, apply_scale=True, spacing=0.0,
                  warp_differential_unit=True, normalize=False, front_end="mfcc", nr_autocorrelation_coefficients=0,
-                 intensity_loudness_power=0.33, type="triangular", boundary="stretch-to-cover", warping_function="mel", tuning=None):
+                 intensity_loudness_power=0.33, type="triangular", boundary="stretch-to-cover", warping_function="mel", tuning=None,
+                 warping_factors=None, vtln_limit=0.875):
         """front_end "mfcc" (mfcc.flow), "mfplp" (mfplp.flow: pass normalize=True and nr_autocorrelation_coefficients) or "plp"
-        (plp.flow: MfccExtractor.plp() fills in that file's values); type / boundary / warping_function are signal-filterbank's"""
-        self.ctx, self.L = ctx, ctx.L
+        (plp.flow: MfccExtractor.plp() fills in that file's values); type / boundary / warping_function are signal-filterbank's.
+        warping_factors (VTLN): the factors of warping-function = nest(linear-2(factor, vtln_limit), mel | bark), one filter bank each;
+        the first is the default of every call that names none.  ctx = None: a host-only handle (tables and geometry only)."""
+        self.ctx, self.L = ctx, (ctx.L if ctx is not None else _lib.lib())
         cfg = MfccCfg(sample_rate, length, shift, alpha, maximum_input_size, int(apply_scale), filter_width, spacing,
                       int(warp_differential_unit), nr_cepstrum_coefficients, int(normalize),
                       {"mfcc": 0, "mfplp": 1, "plp": 2}[front_end], int(nr_autocorrelation_coefficients), float(intensity_loudness_power),
                       {"triangular": 0, "trapeze": 1}[type], {"stretch-to-cover": 0, "include-boundary": 1, "emphasize-boundary": 2}[boundary],
                       {"mel": 0, "bark": 1}[warping_function], _tuning(tuning))
         h = C.c_void_p()
-        _lib.check(self.L.amx_mfcc_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.warping_factors = None
+        if warping_factors is None:
+            _lib.check(self.L.amx_mfcc_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        else:
+            wf = np.ascontiguousarray(np.atleast_1d(np.asarray(warping_factors, np.float64)))
+            vt = _lib.MfccVtln(float(vtln_limit), len(wf), wf.ctypes.data)
+            _lib.check(self.L.amx_mfcc_create_vtln(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(vt), C.byref(h)))
+            self.warping_factors = tuple(float(f) for f in wf)
         self.h = h
         info = _lib.MfccInfo()
         _lib.check(self.L.amx_mfcc_describe(h, C.byref(info)))
@@ -344,20 +358,27 @@ class MfccExtractor:
     def frame_start_time(self, frame):
         return float(self.L.amx_mfcc_frame_start_time(self.h, frame))
 
-    def tables(self):
+    def tables(self, warping_factor=None):
+        """the kernel's tables; warping_factor: those of one of the handle's VTLN factors (amx_mfcc_tables_vtln)"""
         i = self.info
         win = np.zeros(i.frame_len, np.float32)
         fs, fe, fo = np.zeros(i.n_filters, np.int32), np.zeros(i.n_filters, np.int32), np.zeros(i.n_filters + 1, np.int32)
-        _lib.check(self.L.amx_mfcc_tables(self.h, None, None, None, fo.ctypes.data, None, None))
+        if warping_factor is None:
+            get = self.L.amx_mfcc_tables
+        else:
+            get = lambda *a: self.L.amx_mfcc_tables_vtln(a[0], float(warping_factor), *a[1:])  # noqa: E731
+        _lib.check(get(self.h, None, None, None, fo.ctypes.data, None, None))
         fw = np.zeros(int(fo[-1]), np.float32)
         dct = np.zeros((i.n_transform, i.n_transform_inputs), np.float32)
-        _lib.check(self.L.amx_mfcc_tables(self.h, win.ctypes.data, fs.ctypes.data, fe.ctypes.data, fo.ctypes.data,
-                                          fw.ctypes.data, dct.ctypes.data))
+        _lib.check(get(self.h, win.ctypes.data, fs.ctypes.data, fe.ctypes.data, fo.ctypes.data, fw.ctypes.data, dct.ctypes.data))
         return dict(window=win, filter_start=fs, filter_end=fe, filter_offset=fo, filter_weights=fw, dct=dct)
 
-    def run(self, pcm):
+    def run(self, pcm, warping_factor=None):
         """host path: one segment of samples -> [n_frames, n_ceps].  An int16 array goes through the s16 entry point (the samples as
-        the audio file holds them, widened inside the kernel); anything else is taken as f32 sample values"""
+        the audio file holds them, widened inside the kernel); anything else is taken as f32 sample values.  warping_factor: one of
+        the handle's VTLN factors (None: the first)"""
+        if warping_factor is not None:
+            return self.run_batch([pcm], warping_factors=[warping_factor])[0]
         s16 = isinstance(pcm, np.ndarray) and pcm.dtype == np.int16
         pcm = np.ascontiguousarray(pcm, dtype=np.int16 if s16 else np.float32)
         out = np.zeros((self.n_frames(len(pcm)), self.n_ceps), np.float32)
@@ -365,9 +386,20 @@ class MfccExtractor:
         _lib.check(fn(self.h, pcm.ctypes.data, len(pcm), out.ctypes.data))
         return out
 
-    def run_batch(self, pcms):
+    def run_batch(self, pcms, warping_factors=None):
+        """host buffers, one output per segment; warping_factors: one of the handle's VTLN factors per segment (through a device
+        plan, amx_mfcc_plan_create_vtln)"""
         s16 = all(isinstance(p, np.ndarray) and p.dtype == np.int16 for p in pcms) and len(pcms) > 0
         pcms = [np.ascontiguousarray(p, dtype=np.int16 if s16 else np.float32) for p in pcms]
+        if warping_factors is not None:
+            import torch
+            off = np.concatenate([[0], np.cumsum([len(p) for p in pcms])]).astype(np.int64)
+            cat = np.concatenate(pcms) if len(pcms) else np.zeros(0, np.int16 if s16 else np.float32)
+            pcm_dev = torch.from_numpy(cat).to(torch.device("cuda", self.ctx.device)) if len(cat) else torch.zeros(1, dtype=torch.int16 if s16 else torch.float32,
+                                                                                             device=self.ctx.device)
+            ceps, fo = self.run_batch_dev(off, pcm_dev, warping_factors)
+            ceps = ceps.cpu().numpy()
+            return [ceps[fo[u]:fo[u + 1]].copy() for u in range(len(pcms))]
         outs = [np.zeros((self.n_frames(len(p)), self.n_ceps), np.float32) for p in pcms]
         n = len(pcms)
         ip = (C.c_void_p * n)(*[p.ctypes.data for p in pcms])
@@ -377,8 +409,19 @@ class MfccExtractor:
         _lib.check(fn(self.h, n, C.cast(ip, C.c_void_p), ln.ctypes.data, C.cast(op, C.c_void_p)))
         return outs
 
-    def plan(self, sample_offsets):
-        return _Plan(self, sample_offsets)
+    def plan(self, sample_offsets, warping_factors=None):
+        return _Plan(self, sample_offsets, warping_factors)
+
+    def run_batch_dev(self, sample_offsets, pcm_dev, warping_factors=None):
+        """device path in one call: concatenated PCM tensor (float32 or int16) with segment u at sample_offsets[u]..[u + 1] ->
+        ([total_frames, n_ceps] tensor, frame offsets [n_seg + 1]); warping_factors: one of the handle's VTLN factors per segment"""
+        import torch
+        plan = self.plan(sample_offsets, warping_factors)
+        ceps = torch.empty((max(plan.total_frames, 1), self.n_ceps), dtype=torch.float32, device=pcm_dev.device)
+        torch.cuda.synchronize(pcm_dev.device)   # the samples may still be in flight on torch's stream
+        self.run_plan(plan, pcm_dev, ceps)
+        torch.cuda.synchronize(pcm_dev.device)
+        return ceps[:plan.total_frames], plan.frame_offsets
 
     def run_plan(self, plan, pcm_dev, ceps_dev):
         """device path: concatenated PCM tensor (float32 or int16) -> [total_frames, n_ceps] tensor (both resident in HBM)"""

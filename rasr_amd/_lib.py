@@ -36,6 +36,13 @@ class MfccCfg(C.Structure):
                 ("filter_type", C.c_int), ("boundary", C.c_int), ("warping", C.c_int), ("tuning", C.c_char_p)]
 
 
+class MfccVtln(C.Structure):
+    _fields_ = [("limit", C.c_double), ("n_factors", C.c_int), ("factors", C.c_void_p)]
+
+
+AMX_MFCC_MAX_WARPING_FACTORS = 64
+
+
 class GammatoneCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("cascade", C.c_int), ("min_freq", C.c_double), ("max_freq", C.c_double), ("q", C.c_double),
                 ("channels", C.c_int), ("cf_mode", C.c_int), ("warp_freq_break", C.c_double), ("warping_factor", C.c_double),
@@ -124,6 +131,9 @@ SIGNATURES = {
     "amx_mfcc_plan_frame_offsets": (C.c_int, [_P, _P]),
     "amx_mfcc_run_plan_dev": (C.c_int, [_P, _P, _P, _P]),
     "amx_mfcc_run_plan_dev_s16": (C.c_int, [_P, _P, _P, _P]),
+    "amx_mfcc_create_vtln": (C.c_int, [_P, C.POINTER(MfccCfg), C.POINTER(MfccVtln), C.POINTER(_P)]),
+    "amx_mfcc_plan_create_vtln": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(_P)]),
+    "amx_mfcc_tables_vtln": (C.c_int, [_P, C.c_double] + [_P] * 6),
     "amx_context_window_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "amx_normalize_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "amx_normalize_ex_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),

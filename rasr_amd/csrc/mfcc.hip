@@ -27,6 +27,7 @@
 #include "mfcc_tables.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -39,7 +40,7 @@ struct MfccTile {
     int       n_samples;    // segment length
     int       frame0;       // first frame of the tile within the segment
     int       n_frames;     // frames in this tile
-    int       pad_;
+    int       pad_;         // kernel variant bit 32 (VTLN): the filter bank of the tile's segment, else 0
 };
 
 struct MfccParams {
@@ -50,7 +51,8 @@ struct MfccParams {
     const int*      fstart;
     const int*      fend;
     const int*      foff;
-    const float*    fweights;
+    const float*    fweights;  // variant bit 32: the banks, one record each of r4(n_weights) weights + start / end / offset [n_filters]
+                               // (the LDS layout from MfccLds::fw on), n_weights = the largest bank's
     const float*    dct_t;  // transposed [n_filters][n_ceps]
     const double*   eql;    // plp.flow: equal-loudness factor per cosine-transform input, else null
     const float2*   tw;     // [NC]  e^{+2 pi i k / NC}
@@ -194,6 +196,11 @@ __device__ __noinline__ float power_node(float v, float power) {
 // A complex product costs three real ones (P1 = Zr Fr, P2 = Zi Fi, P3 = (Zr + Zi)(Fr + Fi); re = P1 - P2, im = P3 - P1 - P2):
 // 24 MFMAs per frame on the otherwise idle matrix pipe replace ~160 of the frame's ~310 vector instructions and three of its four LDS
 // round trips; the f32 MFMA is an exact fma chain, the error class is that of the f32 butterflies.
+// bit 32 (VTLN plans that mix factors, amx_mfcc_plan_create_vtln): the filter bank per tile -- MfccTile::pad_ names it.  A workgroup
+// stages its first tile's bank; between the barrier behind phase C and the one that ends the tile (phase D reads neither weights nor
+// filter bounds) each wave copies its share of the next tile's bank if that differs, then does its phase-D work -- the copy
+// overlaps other waves' DCT, not its own.  No barrier more than the unwarped kernel's, and the prefetch of the next tile's samples
+// goes to registers, not to the LDS it overwrites.  The filter sums are the unwarped kernel's, operation for operation.
 // bit 4 (NC = 256; amx_mfcc_cfg.tuning prefetch=1): a wave fetches the samples of its NEXT frame while it transforms the current one
 // (12 more registers: 127 instead of 109, still four workgroups per CU).  Measured on config 2, one box, twice: 0.795 ms against
 // 0.743 ms -- SLOWER: the samples of a wave's next frame are the neighbours' current ones (60 % overlap, L1 / L2 hits), their
@@ -230,6 +237,7 @@ __global__ __launch_bounds__(mfcc_waves(NC) * 64, (NC >= 1024 ? 1 : ((VAR & 16) 
     constexpr bool MF  = (VAR & 1) != 0 && NC == 256 && !R16;
     constexpr bool S16 = (VAR & 2) != 0;
     constexpr bool PF  = (VAR & 4) != 0 && NC == 256;
+    constexpr bool BPT = (VAR & 32) != 0;  // bank per tile (VTLN)
     using Sample       = typename std::conditional<S16, short, float>::type;
     constexpr int MW = mfcc_waves(NC), MT = MW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -247,13 +255,40 @@ __global__ __launch_bounds__(mfcc_waves(NC) * 64, (NC >= 1024 ? 1 : ((VAR & 16) 
     int*    s_fo  = s_fe + p.n_filters;
     float2* s_z   = (float2*)(smem + L.fft) + wave * (zpad(NC) + 4);  // this wave's FFT work buffer (index via zpad)
 
-    // ---- tables: staged ONCE per workgroup (workgroups are persistent and loop over tiles)
-    for (int i = tid; i < p.n_weights; i += MT)
-        s_fw[i] = p.fweights[i];
-    for (int i = tid; i < p.n_filters; i += MT) {
-        s_fs[i] = p.fstart[i];
-        s_fe[i] = p.fend[i];
-        s_fo[i] = p.foff[i];
+    // ---- tables: staged ONCE per workgroup (workgroups are persistent and loop over tiles); VTLN: the bank when it changes
+    // bank record -> LDS from s_fw on, all loads of a round of four issued before their stores (one memory round trip per round)
+    [[maybe_unused]] auto stage_bank = [&](int bank) {
+        const int       rec = L.fidx - L.fw + 3 * p.n_filters;
+        const unsigned* src = (const unsigned*)p.fweights + (long long)bank * rec;
+        unsigned*       dst = (unsigned*)s_fw;
+        for (int i0 = 0; i0 < rec; i0 += 4 * MT) {
+            unsigned v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = i0 + e * MT + tid;
+                v[e]        = i < rec ? src[i] : 0u;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = i0 + e * MT + tid;
+                if (i < rec)
+                    dst[i] = v[e];
+            }
+        }
+    };
+    [[maybe_unused]] int cur_bank = 0;
+    if constexpr (BPT) {
+        cur_bank = __builtin_amdgcn_readfirstlane(p.tiles[blockIdx.x].pad_);  // (the grid is never larger than the plan's tiles)
+        stage_bank(cur_bank);
+    }
+    else {
+        for (int i = tid; i < p.n_weights; i += MT)
+            s_fw[i] = p.fweights[i];
+        for (int i = tid; i < p.n_filters; i += MT) {
+            s_fs[i] = p.fstart[i];
+            s_fe[i] = p.fend[i];
+            s_fo[i] = p.foff[i];
+        }
     }
     // DCT^T [kpad][dct_ld], zero padded (p.dct_t is [n_filters][n_ceps])
     for (int i = tid; i < L.kpad * L.dct_ld; i += MT) {
@@ -888,6 +923,16 @@ __global__ __launch_bounds__(mfcc_waves(NC) * 64, (NC >= 1024 ? 1 : ((VAR & 16) 
     MFCC_STAMP(3);
     __syncthreads();
     MFCC_STAMP(4);
+    if constexpr (BPT) {  // every wave is past phase C: the next tile's bank goes in now, the barrier behind phase D publishes it
+        const int next = tile_id + (int)gridDim.x;
+        if (next < p.n_tiles) {
+            const int nb = __builtin_amdgcn_readfirstlane(p.tiles[next].pad_);
+            if (nb != cur_bank) {
+                stage_bank(nb);
+                cur_bank = nb;
+            }
+        }
+    }
 
     // ================= phase D: DCT-II as a [FT x kpad] x [kpad x n_ceps] product on the f32 matrix
     // cores (Signal/CosineTransform.cc:76-83).  v_mfma_f32_16x16x4_f32 is an exact f32 fma chain in
@@ -971,11 +1016,19 @@ struct amx_mfcc {
     size_t  lds_bytes = 0;
     float*  d_ac   = nullptr;  // MF-PLP: autocorrelation coefficients of the current call [frames x n_transform]
     size_t  ac_cap = 0;
+    // VTLN (amx_mfcc_create_vtln): one bank per warping factor, tab = banks[0]; empty for amx_mfcc_create
+    std::vector<double>          vtln_factors;
+    std::vector<amx::MfccTables> banks;
+    int                          bank_weights = 0;        // the largest bank's weights (LDS is sized for it)
+    unsigned*                    d_banks      = nullptr;  // [n_banks] records, see MfccParams::fweights
+    size_t                       bank_rec = 0, bank_nw = 0;  // words per record, of which weights (padded)
 };
 
 struct amx_mfcc_plan {
     amx_mfcc*              owner = nullptr;
     int                    n_seg = 0;
+    bool                   vtln  = false;  // made by amx_mfcc_plan_create_vtln
+    int                    uniform_bank = 0;  // the bank of every tile, or -1 when the plan mixes banks (bank-per-tile variant)
     std::vector<long>      sample_off, frame_off;
     std::vector<amx::MfccTile> tiles;
     amx::MfccTile*         d_tiles     = nullptr;
@@ -992,9 +1045,23 @@ int upload(T** dst, const T* src, size_t n) {
     return AMX_OK;
 }
 
-size_t mfcc_lds_bytes(const amx::MfccTables& t, bool r16) {
-    amx::MfccLds L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, (int)t.filter_weights.size(), r16);
+size_t mfcc_lds_bytes(const amx::MfccTables& t, bool r16, int n_weights) {
+    amx::MfccLds L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, n_weights, r16);
     return (size_t)L.total * 4;
+}
+
+// the kernel walks the cosine-transform inputs: plp.flow's copies of the first and last filter output are two more entries
+// that point at the same weights (generic-vector-f32-split port 0 / reversed port 0 + generic-vector-f32-concat)
+void input_filters(const amx::MfccTables& t, std::vector<int>& in_start, std::vector<int>& in_end, std::vector<int>& in_off) {
+    in_start.assign((size_t)t.n_inputs, 0);
+    in_end.assign((size_t)t.n_inputs, 0);
+    in_off.assign((size_t)t.n_inputs, 0);
+    for (int i = 0; i < t.n_inputs; ++i) {
+        const int src = t.n_inputs == t.n_filters ? i : std::min(std::max(i - 1, 0), t.n_filters - 1);
+        in_start[(size_t)i] = t.filter_start[(size_t)src];
+        in_end[(size_t)i]   = t.filter_end[(size_t)src];
+        in_off[(size_t)i]   = t.filter_offset[(size_t)src];
+    }
 }
 
 // MF-PLP tail, one lane per frame: autocorrelation -> Levinson recursion in f64 (Math/LevinsonLse.cc:35-70; the first
@@ -1178,8 +1245,14 @@ int launch_mfcc_var(amx_mfcc* h, const amx::MfccParams& p, int n_tiles) {
     return AMX_OK;
 }
 
+// bpt: the bank-per-tile form of the same variant (VTLN handles)
+template<int NC, int VAR>
+int launch_mfcc_bank(amx_mfcc* h, const amx::MfccParams& p, int n_tiles, bool bpt) {
+    return bpt ? launch_mfcc_var<NC, VAR | 32>(h, p, n_tiles) : launch_mfcc_var<NC, VAR>(h, p, n_tiles);
+}
+
 template<int NC>
-int launch_mfcc(amx_mfcc* h, const amx::MfccParams& p, int n_tiles, bool s16) {
+int launch_mfcc(amx_mfcc* h, const amx::MfccParams& p, int n_tiles, bool s16, bool bpt) {
     if (n_tiles <= 0)
         return AMX_OK;
     // amx_mfcc_cfg.tuning fft=mfma: the 512-point transform as two 16x16x16 complex products on the f32 matrix cores (see mfcc_kernel).  Measured
@@ -1190,17 +1263,17 @@ int launch_mfcc(amx_mfcc* h, const amx::MfccParams& p, int n_tiles, bool s16) {
     const bool mfma = h->tune_fft_mfma;
     if constexpr (NC == 256) {
         if (h->fft_r16)
-            return s16 ? launch_mfcc_var<NC, 18>(h, p, n_tiles) : launch_mfcc_var<NC, 16>(h, p, n_tiles);
+            return s16 ? launch_mfcc_bank<NC, 18>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 16>(h, p, n_tiles, bpt);
     }
     if constexpr (NC == 256) {
         if (mfma)
-            return s16 ? launch_mfcc_var<NC, 3>(h, p, n_tiles) : launch_mfcc_var<NC, 1>(h, p, n_tiles);
+            return s16 ? launch_mfcc_bank<NC, 3>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 1>(h, p, n_tiles, bpt);
     }
     if constexpr (NC == 256) {
         if (h->tune_prefetch)
-            return s16 ? launch_mfcc_var<NC, 6>(h, p, n_tiles) : launch_mfcc_var<NC, 4>(h, p, n_tiles);
+            return s16 ? launch_mfcc_bank<NC, 6>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 4>(h, p, n_tiles, bpt);
     }
-    return s16 ? launch_mfcc_var<NC, 2>(h, p, n_tiles) : launch_mfcc_var<NC, 0>(h, p, n_tiles);
+    return s16 ? launch_mfcc_bank<NC, 2>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 0>(h, p, n_tiles, bpt);
 }
 
 }  // namespace
@@ -1258,7 +1331,30 @@ void amx_mfplp_default_cfg(amx_mfcc_cfg* c) {
     c->n_ceps            = 13;
 }
 
+static int mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out);
+
 int amx_mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, amx_mfcc** out) {
+    return mfcc_create(ctx, cfg, nullptr, out);
+}
+
+int amx_mfcc_create_vtln(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out) {
+    AMX_REQUIRE(cfg && vtln && out, AMX_ERR_INVALID, "amx_mfcc_create_vtln: NULL argument");
+    *out = nullptr;
+    AMX_REQUIRE(vtln->limit > 0 && vtln->limit < 1, AMX_ERR_INVALID, "amx_mfcc_create_vtln: limit (%g) has to lie in the interval (0, 1)",
+                vtln->limit);
+    AMX_REQUIRE(vtln->n_factors >= 1 && vtln->n_factors <= AMX_MFCC_MAX_WARPING_FACTORS, AMX_ERR_INVALID,
+                "amx_mfcc_create_vtln: n_factors (%d) must be in 1..%d", vtln->n_factors, AMX_MFCC_MAX_WARPING_FACTORS);
+    AMX_REQUIRE(vtln->factors, AMX_ERR_INVALID, "amx_mfcc_create_vtln: NULL factors");
+    for (int i = 0; i < vtln->n_factors; ++i) {
+        const double f = vtln->factors[i];
+        AMX_REQUIRE(std::isfinite(f) && f > 0, AMX_ERR_INVALID, "amx_mfcc_create_vtln: warping factor %d (%g) is not a finite number > 0", i, f);
+        for (int j = 0; j < i; ++j)
+            AMX_REQUIRE(vtln->factors[j] != f, AMX_ERR_INVALID, "amx_mfcc_create_vtln: warping factors %d and %d are both %g", j, i, f);
+    }
+    return mfcc_create(ctx, cfg, vtln, out);
+}
+
+static int mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out) {
     // ctx == NULL creates a host-only handle: geometry and tables are available
     // (amx_mfcc_describe / _n_frames / _tables), running it returns AMX_ERR_STATE.
     AMX_REQUIRE(cfg && out, AMX_ERR_INVALID, "amx_mfcc_create: NULL argument");
@@ -1289,12 +1385,31 @@ int amx_mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, amx_mfcc** out) {
     h->tune_lpc_lds  = t_lpc == "lds";
     h->tune_wgs      = t_wgs;
     h->tune_prefetch = t_prefetch != 0;  // default since the end of round 4 (0.753 -> 0.73 ms on config 2)
-    int r       = h->tab.build(*cfg, t_contract == "fma");
+    int r = AMX_OK;
+    if (!vtln)
+        r = h->tab.build(*cfg, t_contract == "fma");
+    else {
+        h->vtln_factors.assign(vtln->factors, vtln->factors + vtln->n_factors);
+        h->banks.resize((size_t)vtln->n_factors);
+        for (int i = 0; i < vtln->n_factors && r == AMX_OK; ++i) {
+            const amx::MfccTables::Vtln v{vtln->factors[i], vtln->limit};
+            r = h->banks[(size_t)i].build(*cfg, t_contract == "fma", &v);
+            if (r == AMX_OK && h->banks[(size_t)i].n_filters != h->banks[0].n_filters) {
+                amx::set_error("amx_mfcc_create_vtln: warping factor %g gives %d filters, warping factor %g gives %d", vtln->factors[0],
+                               h->banks[0].n_filters, vtln->factors[i], h->banks[(size_t)i].n_filters);
+                r = AMX_ERR_INVALID;
+            }
+            h->bank_weights = std::max(h->bank_weights, (int)h->banks[(size_t)i].filter_weights.size());
+        }
+        if (r == AMX_OK)
+            h->tab = h->banks[0];
+    }
     if (r != AMX_OK) {
         delete h;
         return r;
     }
     const amx::MfccTables& t = h->tab;
+    const int n_weights = vtln ? h->bank_weights : (int)t.filter_weights.size();
     if (t.fft_len < 8 || t.fft_len > 2048) {
         amx::set_error("amx_mfcc_create: FFT length %d not supported by the gfx950 kernel (8..2048)", t.fft_len);
         delete h;
@@ -1307,7 +1422,7 @@ int amx_mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, amx_mfcc** out) {
     AMX_HIP(hipSetDevice(ctx->device));
     h->frames_per_tile = amx::FT;
     h->fft_r16         = t_fft == "r16" && t.fft_len == 512 && cfg->front_end == AMX_FRONT_END_MFCC;  // (other lengths and front ends: the Stockham stages)
-    h->lds_bytes       = mfcc_lds_bytes(t, h->fft_r16);
+    h->lds_bytes       = mfcc_lds_bytes(t, h->fft_r16, n_weights);
     if (h->lds_bytes > 160 * 1024) {
         amx::set_error("amx_mfcc_create: configuration needs %zu bytes of LDS per workgroup (> 160 KiB)", h->lds_bytes);
         delete h;
@@ -1317,14 +1432,27 @@ int amx_mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, amx_mfcc** out) {
     for (int k = 0; k < t.n_transform; ++k)
         for (int n = 0; n < t.n_inputs; ++n)
             dct_t[(size_t)n * t.n_transform + k] = t.dct[(size_t)k * t.n_inputs + n];
-    // the kernel walks the cosine-transform inputs: plp.flow's copies of the first and last filter output are two more entries
-    // that point at the same weights (generic-vector-f32-split port 0 / reversed port 0 + generic-vector-f32-concat)
-    std::vector<int> in_start((size_t)t.n_inputs), in_end((size_t)t.n_inputs), in_off((size_t)t.n_inputs);
-    for (int i = 0; i < t.n_inputs; ++i) {
-        const int src = t.n_inputs == t.n_filters ? i : std::min(std::max(i - 1, 0), t.n_filters - 1);
-        in_start[(size_t)i] = t.filter_start[(size_t)src];
-        in_end[(size_t)i]   = t.filter_end[(size_t)src];
-        in_off[(size_t)i]   = t.filter_offset[(size_t)src];
+    std::vector<int> in_start, in_end, in_off;
+    input_filters(t, in_start, in_end, in_off);
+    if (vtln) {  // bank records in the kernel's LDS layout: weights padded to r4(n_weights), then start / end / offset per input
+        const amx::MfccLds L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, n_weights, h->fft_r16);
+        const size_t       nw = (size_t)(L.fidx - L.fw), rec = nw + 3 * (size_t)t.n_inputs;
+        h->bank_rec = rec, h->bank_nw = nw;
+        std::vector<unsigned> recs(rec * h->banks.size(), 0u);
+        for (size_t k = 0; k < h->banks.size(); ++k) {
+            const amx::MfccTables& b = h->banks[k];
+            unsigned*              o = recs.data() + k * rec;
+            std::vector<int>       bs, be, bo;
+            input_filters(b, bs, be, bo);
+            memcpy(o, b.filter_weights.data(), b.filter_weights.size() * 4);
+            memcpy(o + nw, bs.data(), bs.size() * 4);
+            memcpy(o + nw + bs.size(), be.data(), be.size() * 4);
+            memcpy(o + nw + 2 * bs.size(), bo.data(), bo.size() * 4);
+        }
+        if ((r = upload(&h->d_banks, recs.data(), recs.size())) != AMX_OK) {
+            amx_mfcc_destroy(h);
+            return r;
+        }
     }
     if ((r = upload(&h->d_window, t.window.data(), t.window.size())) != AMX_OK ||
         (r = upload(&h->d_fw, t.filter_weights.data(), t.filter_weights.size())) != AMX_OK ||
@@ -1360,6 +1488,7 @@ void amx_mfcc_destroy(amx_mfcc* h) {
     hipFree(h->d_stw);
     hipFree(h->d_eql);
     hipFree(h->d_ac);
+    hipFree(h->d_banks);
     delete h;
 }
 
@@ -1386,9 +1515,31 @@ double amx_mfcc_frame_start_time(const amx_mfcc* h, long frame) {
     return h ? h->tab.frame_start_time(frame) : 0.0;
 }
 
+static int mfcc_tables(const amx::MfccTables& t, float* window, int* fs, int* fe, int* fo, float* fw, float* dct);
+
 int amx_mfcc_tables(const amx_mfcc* h, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
     AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_mfcc_tables: NULL handle");
-    const amx::MfccTables& t = h->tab;
+    return mfcc_tables(h->tab, window, fs, fe, fo, fw, dct);
+}
+
+// the bank index of a warping factor (exact match), -1 if the handle has none such; a plain handle has the one factor 1
+static int mfcc_bank_of(const amx_mfcc* h, double factor) {
+    if (h->vtln_factors.empty())
+        return factor == 1.0 ? 0 : -1;
+    for (size_t k = 0; k < h->vtln_factors.size(); ++k)
+        if (h->vtln_factors[k] == factor)
+            return (int)k;
+    return -1;
+}
+
+int amx_mfcc_tables_vtln(const amx_mfcc* h, double warping_factor, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
+    AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_mfcc_tables_vtln: NULL handle");
+    const int k = mfcc_bank_of(h, warping_factor);
+    AMX_REQUIRE(k >= 0, AMX_ERR_INVALID, "amx_mfcc_tables_vtln: warping factor %.17g is not one of the handle's", warping_factor);
+    return mfcc_tables(h->banks.empty() ? h->tab : h->banks[(size_t)k], window, fs, fe, fo, fw, dct);
+}
+
+static int mfcc_tables(const amx::MfccTables& t, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
     if (window)
         memcpy(window, t.window.data(), t.window.size() * 4);
     if (fs)
@@ -1411,13 +1562,33 @@ int amx_mfcc_equal_loudness(const amx_mfcc* h, double* factors) {
     return AMX_OK;
 }
 
+static int mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, const std::vector<int>* bank, amx_mfcc_plan** out);
+
 int amx_mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, amx_mfcc_plan** out) {
+    return mfcc_plan_create(h, n_seg, sample_offsets, nullptr, out);
+}
+
+int amx_mfcc_plan_create_vtln(amx_mfcc* h, int n_seg, const long* sample_offsets, const double* warping_factor, amx_mfcc_plan** out) {
+    AMX_REQUIRE(h && out && n_seg >= 0 && (n_seg == 0 || (sample_offsets && warping_factor)), AMX_ERR_INVALID,
+                "amx_mfcc_plan_create_vtln: bad argument");
+    *out = nullptr;
+    std::vector<int> bank((size_t)n_seg, 0);
+    for (int u = 0; u < n_seg; ++u) {
+        bank[(size_t)u] = mfcc_bank_of(h, warping_factor[u]);
+        AMX_REQUIRE(bank[(size_t)u] >= 0, AMX_ERR_INVALID, "amx_mfcc_plan_create_vtln: segment %d: warping factor %.17g is not one of the handle's",
+                    u, warping_factor[u]);
+    }
+    return mfcc_plan_create(h, n_seg, sample_offsets, &bank, out);
+}
+
+static int mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, const std::vector<int>* bank, amx_mfcc_plan** out) {
     AMX_REQUIRE(h && out && n_seg >= 0 && (n_seg == 0 || sample_offsets), AMX_ERR_INVALID, "amx_mfcc_plan_create: bad argument");
     AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_mfcc_plan_create: host-only handle (created without a context)");
     *out             = nullptr;
     amx_mfcc_plan* p = new amx_mfcc_plan;
     p->owner         = h;
     p->n_seg         = n_seg;
+    p->vtln          = bank != nullptr;
     p->sample_off.assign(sample_offsets, sample_offsets + n_seg + (n_seg ? 1 : 0));
     if (n_seg == 0)
         p->sample_off.assign(1, 0);
@@ -1439,7 +1610,11 @@ int amx_mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, amx
             t.n_samples   = (int)len;
             t.frame0      = (int)f0;
             t.n_frames    = (int)std::min<long>(ft, T - f0);
-            t.pad_        = 0;
+            t.pad_        = bank ? (*bank)[(size_t)u] : 0;
+            if (!p->tiles.empty() && t.pad_ != p->tiles[0].pad_)
+                p->uniform_bank = -1;
+            else if (p->tiles.empty())
+                p->uniform_bank = t.pad_;
             p->tiles.push_back(t);
         }
     }
@@ -1498,10 +1673,21 @@ static int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_de
     k.ceps            = ceps_dev;
     k.tiles           = p->d_tiles;
     k.window          = h->d_window;
+    // a VTLN plan whose tiles mix banks runs the bank-per-tile variant; one whose tiles share one bank (one factor, or a one-factor
+    // handle) runs the unwarped kernel on that bank's record (weights padded to the largest bank's, then start / end / offset)
+    const bool vtln   = !h->banks.empty();
+    const bool bpt    = vtln && p->uniform_bank < 0;
     k.fstart          = h->d_fs;
     k.fend            = h->d_fe;
     k.foff            = h->d_fo;
-    k.fweights        = h->d_fw;
+    k.fweights        = bpt ? (const float*)h->d_banks : h->d_fw;
+    if (vtln && !bpt) {
+        const unsigned* rec = h->d_banks + (size_t)p->uniform_bank * h->bank_rec;
+        k.fweights          = (const float*)rec;
+        k.fstart            = (const int*)(rec + h->bank_nw);
+        k.fend              = k.fstart + t.n_inputs;
+        k.foff              = k.fend + t.n_inputs;
+    }
     k.dct_t           = h->d_dct_t;
     k.tw              = h->d_tw;
     k.stw             = h->d_stw;
@@ -1510,7 +1696,7 @@ static int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_de
     k.n_filters       = t.n_inputs;
     k.eql             = h->d_eql;
     k.n_ceps          = t.n_transform;
-    k.n_weights       = (int)t.filter_weights.size();
+    k.n_weights       = vtln ? h->bank_weights : (int)t.filter_weights.size();
     k.front_end       = t.cfg.front_end != AMX_FRONT_END_MFCC ? 1 : 0;
     k.norm_div        = t.norm_div;
     k.plp_power       = (float)t.cfg.plp_power;
@@ -1535,15 +1721,15 @@ static int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_de
     k.dct_normalize   = t.cfg.dct_normalize;
     int r;
     switch (t.fft_len / 2) {
-        case 4: r = launch_mfcc<4>(h, k, n_tiles_total, s16); break;
-        case 8: r = launch_mfcc<8>(h, k, n_tiles_total, s16); break;
-        case 16: r = launch_mfcc<16>(h, k, n_tiles_total, s16); break;
-        case 32: r = launch_mfcc<32>(h, k, n_tiles_total, s16); break;
-        case 64: r = launch_mfcc<64>(h, k, n_tiles_total, s16); break;
-        case 128: r = launch_mfcc<128>(h, k, n_tiles_total, s16); break;
-        case 256: r = launch_mfcc<256>(h, k, n_tiles_total, s16); break;
-        case 512: r = launch_mfcc<512>(h, k, n_tiles_total, s16); break;
-        case 1024: r = launch_mfcc<1024>(h, k, n_tiles_total, s16); break;
+        case 4: r = launch_mfcc<4>(h, k, n_tiles_total, s16, bpt); break;
+        case 8: r = launch_mfcc<8>(h, k, n_tiles_total, s16, bpt); break;
+        case 16: r = launch_mfcc<16>(h, k, n_tiles_total, s16, bpt); break;
+        case 32: r = launch_mfcc<32>(h, k, n_tiles_total, s16, bpt); break;
+        case 64: r = launch_mfcc<64>(h, k, n_tiles_total, s16, bpt); break;
+        case 128: r = launch_mfcc<128>(h, k, n_tiles_total, s16, bpt); break;
+        case 256: r = launch_mfcc<256>(h, k, n_tiles_total, s16, bpt); break;
+        case 512: r = launch_mfcc<512>(h, k, n_tiles_total, s16, bpt); break;
+        case 1024: r = launch_mfcc<1024>(h, k, n_tiles_total, s16, bpt); break;
         default:
             amx::set_error("amx_mfcc_run_plan_dev: no kernel for FFT length %d", t.fft_len);
             return AMX_ERR_UNSUPPORTED;

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 
 #include "common.hpp"
 
@@ -50,14 +51,78 @@ struct BarkWarp {  // nest(Scaling(6), nest(ArcSinh, Scaling(1/600))) in the con
     double inverse(double b) const { return inner.inverse()(std::sinh(outer.inverse()(b))); }
 };
 
-// the warping-function parameter: one of the two, behind one interface
+// Math::PiecewiseLinearFunction (Math/PiecewiseLinearFunction.cc, .hh): f(x) = a(x) * x + b(x) with a, b piecewise constant over
+// ascending limits; a segment is the first whose limit is >= x (PiecewiseConstantFunction::value, Math/SimpleAnalyticFunctions.hh)
+struct PiecewiseLinear {
+    std::vector<double> limit, a, b;
+    bool                fma = false;  // contract=fma: add()'s value - a * limit is one vfnmadd in the reference's default build; value()'s
+                                      // a(x) * x + b(x) is not fused there (the two table look-ups stand between product and sum)
+    double mad(double x, double y, double z) const { return fma ? std::fma(x, y, z) : x * y + z; }
+    size_t segment(double x) const {
+        size_t i = 0;
+        while (i + 1 < limit.size() && !(limit[i] >= x))
+            ++i;
+        return i;
+    }
+    double operator()(double x) const {
+        const size_t i = segment(x);
+        return a[i] * x + b[i];
+    }
+    double derivative(double x) const { return a[segment(x)]; }
+    void   add(double lim, double slope) {
+        if (limit.empty())
+            append(lim, slope, 0);
+        else {
+            const double last = limit.back();
+            append(lim, slope, mad(-slope, last, (*this)(last)));
+        }
+    }
+    void normalize(double lim) {  // the last segment maps `lim` onto itself
+        if (limit.empty())
+            add(std::numeric_limits<double>::max(), 1);
+        else {
+            const double last = limit.back();
+            add(std::numeric_limits<double>::max(), (lim - (*this)(last)) / (lim - last));
+        }
+    }
+    void append(double lim, double slope, double offset) {
+        limit.push_back(lim);
+        a.push_back(slope);
+        b.push_back(offset);
+    }
+    PiecewiseLinear inverse() const {
+        PiecewiseLinear r;
+        r.fma = fma;
+        for (size_t i = 0; i < limit.size(); ++i)
+            r.append((*this)(limit[i]), 1.0 / a[i], -b[i] / a[i]);
+        return r;
+    }
+};
+
+// linear-2(factor, limit) (Math/AnalyticFunctionFactory.cc, createTwoPieceLinearFunction): slope `factor` up to limit * max, then the
+// line through (max, max); a factor above 1 is the inverse of the function built for its reciprocal
+PiecewiseLinear two_piece_linear(double factor, double limit, double max, bool fma) {
+    PiecewiseLinear f;
+    f.fma = fma;
+    f.add(limit * max, factor <= 1 ? factor : 1 / factor);
+    f.normalize(max);
+    return factor <= 1 ? f : f.inverse();
+}
+
+// the warping-function parameter: mel or bark, optionally nested around linear-2 (VTLN): nest(linear-2(factor, limit), mel) is
+// mel(plf(f)), derivative mel'(plf(f)) * plf'(f), inverse plf^-1(mel^-1(w)) (Math::AnalyticNesting)
 struct Warp {
-    int      kind;  // AMX_WARP_MEL / AMX_WARP_BARK
-    MelWarp  mel;
-    BarkWarp bark;
-    double   operator()(double f) const { return kind == AMX_WARP_BARK ? bark(f) : mel(f); }
-    double   derivative(double f) const { return kind == AMX_WARP_BARK ? bark.derivative(f) : mel.derivative(f); }
-    double   inverse(double w) const { return kind == AMX_WARP_BARK ? bark.inverse(w) : mel.inverse(w); }
+    int             kind;  // AMX_WARP_MEL / AMX_WARP_BARK
+    MelWarp         mel;
+    BarkWarp        bark;
+    bool            vtln = false;
+    PiecewiseLinear plf, plf_inv;
+    double outer(double f) const { return kind == AMX_WARP_BARK ? bark(f) : mel(f); }
+    double outer_derivative(double f) const { return kind == AMX_WARP_BARK ? bark.derivative(f) : mel.derivative(f); }
+    double outer_inverse(double w) const { return kind == AMX_WARP_BARK ? bark.inverse(w) : mel.inverse(w); }
+    double operator()(double f) const { return vtln ? outer(plf(f)) : outer(f); }
+    double derivative(double f) const { return vtln ? outer_derivative(plf(f)) * plf.derivative(f) : outer_derivative(f); }
+    double inverse(double w) const { return vtln ? plf_inv(outer_inverse(w)) : outer_inverse(w); }
 };
 
 // Math::EqualLoudnessPreemphasis / EqualLoudnessPreemphasis4Khz
@@ -107,8 +172,13 @@ double through_attribute(double v) {
 
 }  // namespace
 
-int MfccTables::build(const amx_mfcc_cfg& c, bool fma) {
+int MfccTables::build(const amx_mfcc_cfg& c, bool fma, const Vtln* vtln) {
     cfg = c;
+    if (vtln) {
+        AMX_REQUIRE(vtln->limit > 0 && vtln->limit < 1, AMX_ERR_INVALID, "mfcc: VTLN limit (%g) has to lie in the interval (0, 1)", vtln->limit);
+        AMX_REQUIRE(std::isfinite(vtln->factor) && vtln->factor > 0, AMX_ERR_INVALID, "mfcc: warping factor %g is not a finite number > 0",
+                    vtln->factor);
+    }
     AMX_REQUIRE(c.sample_rate > 0, AMX_ERR_INVALID, "mfcc: sample rate (%f) is not positive", c.sample_rate);
     AMX_REQUIRE(c.win_len_s > 0 && c.win_shift_s > 0, AMX_ERR_INVALID, "mfcc: window length/shift must be positive");
     AMX_REQUIRE(c.n_ceps >= 1, AMX_ERR_INVALID, "mfcc: nr-outputs must be >= 1");
@@ -153,6 +223,11 @@ int MfccTables::build(const amx_mfcc_cfg& c, bool fma) {
         Warp          warp;
         warp.kind           = c.warping;
         warp.bark.fma       = fma;
+        if (vtln) {  // FilterBankNode::createAnalyticFunction: linear-2's maximal argument is d2c(n_bins - 1)
+            warp.vtln    = true;
+            warp.plf     = two_piece_linear(vtln->factor, vtln->limit, disc2cont((double)(n_bins - 1)), fma);
+            warp.plf_inv = warp.plf.inverse();
+        }
         // a * b + c at the sites the reference's default build contracts (f64: coverage, the
         // include-boundary count, stretch-to-cover's centres, setStart / setEnd)
         auto mad = [&](double a, double b, double c3) { return fma ? std::fma(a, b, c3) : a * b + c3; };

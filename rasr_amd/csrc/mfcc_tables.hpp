@@ -32,9 +32,15 @@ struct MfccTables {
     std::vector<float> twiddle;        // [fft_len/2][2] cos,sin of +2*pi*k/(fft_len/2)  (complex FFT)
     std::vector<float> split_twiddle;  // [fft_len/4][2] cos,sin of +pi*k/(fft_len/2)    (real split)
 
+    // VTLN: warping-function = nest(linear-2(factor, limit), mel | bark)
+    struct Vtln {
+        double factor, limit;
+    };
+
     // returns AMX_OK or an error status (message via set_error)
     // fma: the geometry (f64) as the reference's default build contracts it (amx_set_contract / tuning contract=fma)
-    int build(const amx_mfcc_cfg& c, bool fma = false);
+    // vtln: NULL for the plain mel / bark warping
+    int build(const amx_mfcc_cfg& c, bool fma = false, const Vtln* vtln = nullptr);
 
     long   n_frames(long n_samples) const;
     double frame_start_time(long frame) const;

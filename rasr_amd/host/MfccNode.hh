@@ -34,8 +34,75 @@ class MfccNode {
     std::vector<float>                 ceps_;
     long                               nFrames_, next_;
     std::map<std::string, std::string> outputAttributes_;
+    // VTLN: warping-function = nest(linear-2(<factor> | $(warping-factor), <limit>), mel | bark); the filter bank of the factor in
+    // force is rebuilt when a segment brings another one (Flow::StringExpressionNode)
+    bool        vtln_ = false, factorFromParameter_ = false;
+    double      vtlnLimit_ = 0, warpingFactor_ = 1, builtFactor_ = 0;
+    std::string error_;
 
 public:
+    /** The warping-function declarations this node accepts: "mel", "bark" and
+     *  "nest(linear-2(<factor>|$(warping-factor), <limit>), mel|bark)" (blanks ignored).  Anything else of
+     *  Math/AnalyticFunctionFactory's grammar (other nestings, mel(discretize-argument), linear-3, bilinear, ...) is refused:
+     *  false and a message in *error.  factor = 0 when it comes from $(warping-factor). */
+    static bool parseWarpingFunction(const std::string& declaration, int* warping, bool* vtln, double* factor, double* limit,
+                                     std::string* error) {
+        std::string d;
+        for (char c : declaration)
+            if (c != ' ' && c != '\t')
+                d += c;
+        *vtln   = false;
+        *factor = 1;
+        *limit  = 0;
+        auto outer = [&](const std::string& w) {
+            if (w == "mel")
+                *warping = AMX_WARP_MEL;
+            else if (w == "bark")
+                *warping = AMX_WARP_BARK;
+            else
+                return false;
+            return true;
+        };
+        if (outer(d))
+            return true;
+        const std::string head = "nest(linear-2(", param = "$(warping-factor)";
+        size_t            pos  = 0;
+        if (d.compare(0, head.size(), head) == 0) {
+            pos = head.size();
+            char* end = nullptr;
+            if (d.compare(pos, param.size(), param) == 0) {
+                *factor = 0;
+                pos += param.size();
+            }
+            else {
+                *factor = strtod(d.c_str() + pos, &end);
+                if (end == d.c_str() + pos || !(*factor > 0)) {
+                    *error = "warping-function \"" + declaration + "\": the warping factor must be a number > 0 or $(warping-factor)";
+                    return false;
+                }
+                pos = (size_t)(end - d.c_str());
+            }
+            if (pos < d.size() && d[pos] == ',') {
+                *limit = strtod(d.c_str() + pos + 1, &end);
+                if (end != d.c_str() + pos + 1 && *limit > 0 && *limit < 1) {
+                    pos = (size_t)(end - d.c_str());
+                    if (d.compare(pos, 2, "),") == 0 && d.size() > pos + 3 && d.back() == ')' && outer(d.substr(pos + 2, d.size() - pos - 3))) {
+                        *vtln = true;
+                        return true;
+                    }
+                }
+                else {
+                    *error = "warping-function \"" + declaration + "\": the limit of linear-2 has to lie in the interval (0, 1)";
+                    return false;
+                }
+            }
+        }
+        *error = "warping-function \"" + declaration + "\" is not supported: mel, bark or nest(linear-2(<factor>|$(warping-factor), <limit>), mel|bark)";
+        return false;
+    }
+    /** the message of the last refused setParameter / configure of this node */
+    const std::string& error() const { return error_; }
+
     static std::string filterName() { return "signal-mfcc-amx"; }
 
     explicit MfccNode(amx_ctx* ctx)
@@ -60,6 +127,28 @@ public:
         else if (name == "warp-differential-unit") cfg_.warp_differential_unit = b;
         else if (name == "nr-outputs") cfg_.n_ceps = atoi(value.c_str());
         else if (name == "normalize") cfg_.dct_normalize = b;
+        else if (name == "warping-function") {
+            int    w = cfg_.warping;
+            bool   vt;
+            double f, l;
+            if (!parseWarpingFunction(value, &w, &vt, &f, &l, &error_))
+                return false;
+            cfg_.warping = w, vtln_ = vt, vtlnLimit_ = l;
+            factorFromParameter_ = vt && f == 0;
+            if (vt && f != 0)
+                warpingFactor_ = f;
+        }
+        else if (name == "warping-factor") {  // per segment, e.g. from a corpus key map; takes effect at the next segment's eos()
+            if (!(v > 0)) {
+                error_ = "warping-factor \"" + value + "\" is not a number > 0";
+                return false;
+            }
+            if (!factorFromParameter_) {
+                error_ = "warping-factor is set, but warping-function does not name $(warping-factor)";
+                return false;
+            }
+            warpingFactor_ = v;
+        }
         else return false;
         return true;
     }
@@ -71,9 +160,8 @@ public:
         cfg_.sample_rate = it == inputAttributes.end() ? 0.0 : atof(it->second.c_str());
         amx_mfcc_destroy(h_);
         h_ = nullptr;
-        if (amx_mfcc_create(ctx_, &cfg_, &h_) != AMX_OK)
+        if (!createHandle())
             return false;
-        amx_mfcc_describe(h_, &info_);
         outputAttributes_                = inputAttributes;
         outputAttributes_["sample-rate"] = "1";
         outputAttributes_["datatype"]    = "vector-f32";
@@ -104,6 +192,17 @@ public:
     bool eos() {
         if (!h_)
             return false;
+        if (vtln_ && warpingFactor_ != builtFactor_) {  // a new warping factor: the filter bank of this one
+            amx_mfcc_destroy(h_);
+            h_ = nullptr;
+            if (!createHandle()) {
+                samples_.clear();
+                samples16_.clear();
+                nFrames_ = next_ = 0;
+                nSamples_ = 0;
+                return false;
+            }
+        }
         if (!samples_.empty() && !samples16_.empty()) {  // a segment is all-s16 or all-f32: drop it, the node stays usable for the next one
             samples_.clear();
             samples16_.clear();
@@ -137,6 +236,24 @@ public:
 
 private:
     long nSamples_ = 0;
+
+    bool createHandle() {
+        int r;
+        if (vtln_) {
+            const amx_mfcc_vtln v = {vtlnLimit_, 1, &warpingFactor_};
+            r            = amx_mfcc_create_vtln(ctx_, &cfg_, &v, &h_);
+            builtFactor_ = warpingFactor_;
+        }
+        else
+            r = amx_mfcc_create(ctx_, &cfg_, &h_);
+        if (r != AMX_OK) {
+            error_ = amx_last_error();
+            h_     = nullptr;
+            return false;
+        }
+        amx_mfcc_describe(h_, &info_);
+        return true;
+    }
 };
 
 }  // namespace AmxHost
