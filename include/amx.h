@@ -289,6 +289,66 @@ int amx_gammatone_run(amx_gammatone* h, const float* pcm_host, long n_samples, f
 int amx_gammatone_run_batch_dev(amx_gammatone* h, int n_seg, const long* sample_offsets, const float* pcm_dev, float* out_dev,
                                 float* filtered_dev);
 
+/* ------------------------------------------------------------------ voicedness front-end
+ * Tools/FeatureExtraction/share/voicedness.flow as one front end, PCM in, ONE f32 per 10 ms frame out: signal-window (rectangular;
+ * Signal/TimeWindowBuffer.cc:52-125, short last frame included) -> signal-vector-f32-resize (Signal/VectorResize.hh:93-113: the short
+ * frame padded with zeros to the window length) -> signal-vector-f32-mean-energy-normalization (Signal/VectorNormalization.hh:44-49)
+ * -> signal-cross-correlation with x = y (Signal/CrossCorrelation.cc:31-64, 111-127, 225-243; CrossCorrelation.hh:33-49: real FFT of
+ * length next-pow-2(size + end - 1), X conj(X), real inverse FFT, lags [0, end), unbiased estimate R[m] / (size - m)) ->
+ * signal-peak-detection, output maximal-peak-value (Signal/PeakDetection.cc:42-68, 92-98, 252-277).
+ * Built: sample rates whose 40 ms window needs a 1024- or 2048-point transform (8 kHz, 16 kHz), begin = 0, similarity-function =
+ * multiplication, use-fft = true, normalization none | unbiased-estimate.  Refused with AMX_ERR_UNSUPPORTED and a message naming the
+ * parameter: begin != 0 (negative or skipped lags), normalization = upper-bound, any other transform length.  Not expressible here, so
+ * an adapter refuses them itself: x != y, similarity-function = absolute-difference, use-fft = false, nr-coefficients, the other
+ * seven outputs of the peak node (INTEGRATION.md has the table).
+ * FRAME COUNT: the 40 ms window flushes later than mfcc.flow's 25 ms window, so a segment can yield a different number of frames than
+ * its cepstra (amx_voicedness_n_frames vs amx_mfcc_n_frames); the library trims nothing -- INTEGRATION.md says how the reference's
+ * timestamp synchronisation lines the two streams up.
+ * The normalisation is the same in both builds of the reference (its two builds give the same bits on the recorded frames,
+ * tests/golden/ref_voicedness.npz; the f32 product is converted before the f64 add) and the kernel's energy sum is the index-order
+ * sum bit for bit (amx_voicedness_energy_dev).  The two builds differ in X conj(X), an f32 site; the device transforms are f32 and
+ * agree with either build within the front-end bar (DESIGN.md sections 4.6 and 5). */
+typedef struct {
+    double sample_rate;     /* Hz */
+    double win_len_s;       /* signal-window length = signal-vector-f32-resize new-size (voicedness.flow: .040) */
+    double win_shift_s;     /* signal-window shift                                       (voicedness.flow: .010) */
+    double corr_begin_s;    /* signal-cross-correlation begin: 0 only                                           */
+    double corr_end_s;      /* signal-cross-correlation end                              (voicedness.flow: .040) */
+    int    normalization;   /* AMX_XCORR_NONE | AMX_XCORR_UNBIASED_ESTIMATE (voicedness.flow); _UPPER_BOUND is refused */
+    double min_position_s;  /* signal-peak-detection min-position                       (voicedness.flow: .0025) */
+    double max_position_s;  /* signal-peak-detection max-position                       (voicedness.flow: .0167) */
+    const char* tuning;     /* NULL; no keys yet (an unknown key fails amx_voicedness_create)                   */
+} amx_voicedness_cfg;
+enum { AMX_XCORR_NONE = 0, AMX_XCORR_UNBIASED_ESTIMATE = 1, AMX_XCORR_UPPER_BOUND = 2 };
+typedef struct {
+    int frame_len, frame_shift, fft_len;
+    int n_lags;                     /* end - begin: the length of the autocorrelation vector the peak node sees */
+    int min_position, max_position; /* as indices: (u32)rint(seconds * sample rate), PeakDetection::init         */
+} amx_voicedness_info;
+typedef struct amx_voicedness amx_voicedness;
+void amx_voicedness_default_cfg(amx_voicedness_cfg* cfg); /* voicedness.flow at 16 kHz */
+int  amx_voicedness_create(amx_ctx* ctx, const amx_voicedness_cfg* cfg, amx_voicedness** out); /* ctx NULL: host-only (geometry) */
+void amx_voicedness_destroy(amx_voicedness* h);
+int  amx_voicedness_describe(const amx_voicedness* h, amx_voicedness_info* info);
+/* frames of a segment of n_samples: the window node's framing and flush rule (Signal/WindowBuffer.cc:84-125) with the 40 ms window */
+long amx_voicedness_n_frames(const amx_voicedness* h, long n_samples);
+/* one segment, host buffers: pcm f32 -> out [n_frames] */
+int amx_voicedness_run(amx_voicedness* h, const float* pcm_host, long n_samples, float* out_host);
+/* a batch of segments resident in HBM: segment u = samples [sample_offsets[u], sample_offsets[u+1]) of pcm_dev (offsets on the
+ * host), its frames follow those of segment u - 1.  Frame t's measure is written to out_dev[t * out_ld] and nothing else is: out_ld
+ * is a row stride in floats, so out_dev may be one column of a wider feature matrix.  acf_dev (nullable, tests: [total frames x
+ * n_lags]) receives the normalised autocorrelation the peak detection saw.  _s16: the samples as the audio file holds them, widened
+ * without scaling (Flow/TypeConverter.hh:35-43); bit-identical to the f32 entry point on the same sample values. */
+int amx_voicedness_run_batch_dev(amx_voicedness* h, int n_seg, const long* sample_offsets, const float* pcm_dev, float* out_dev, int out_ld,
+                                 float* acf_dev);
+int amx_voicedness_run_batch_dev_s16(amx_voicedness* h, int n_seg, const long* sample_offsets, const int16_t* pcm_dev, float* out_dev,
+                                     int out_ld, float* acf_dev);
+
+/* Test-only: the energy sum of the normalisation (std::inner_product over the resized frame, VectorNormalization.hh:45) of every frame
+ * as the kernel forms it, [total frames] f64, and how it was added: ordered_dev[t] = 0 in lane order (proved exact in any order), 1 by
+ * one lane in index order. */
+int amx_voicedness_energy_dev(amx_voicedness* h, int n_seg, const long* sample_offsets, const float* pcm_dev, double* sum_dev, int* ordered_dev);
+
 /* Sliding-window concatenation of feature frames per segment (f1 "next" row:
  * signal-vector-f32-sequence-concatenation, Signal/SlidingWindow.hh:66-76 copy margin policy):
  * out[t] = [x[t-left] .. x[t+right]] with indices clamped to the segment.  out_dev is

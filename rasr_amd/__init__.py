@@ -6,6 +6,7 @@ adapters a RASR maintainer links are described in INTEGRATION.md; the classes be
 same reference interfaces for tests and benchmarks:
 
   MfccExtractor        mfcc.flow network (Tools/FeatureExtraction/share/mfcc.flow)
+  VoicednessExtractor  voicedness.flow network (autocorrelation by FFT, maximal peak value)
   GmmFeatureScorer     Mm::FeatureScorer over a Mm::MixtureSet (diagonal-maximum / diagonal-sum)
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
   FileArchive          Core::FileArchive + Flow cache entries (feature caches between jobs; host IO)
@@ -19,7 +20,7 @@ from . import _lib
 from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AMX_ACT_ELU, AMX_GMM_BATCH_FLOAT, AMX_GMM_BAUM_WELCH, AMX_GMM_MAX, AMX_GMM_SUM, AMX_GMM_VITERBI,  # noqa: F401
                    AMX_PREC_BF16, AMX_PREC_FP32, AmxError, MfccCfg)
 
-__all__ = ["Context", "MfccExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
+__all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
@@ -295,6 +296,64 @@ class GammatoneExtractor:
         off = np.ascontiguousarray(sample_offsets, dtype=np.int64)
         _lib.check(self.L.amx_gammatone_run_batch_dev(self.h, len(off) - 1, off.ctypes.data, pcm_dev.data_ptr(), out_dev.data_ptr(),
                                                       filtered_dev.data_ptr() if filtered_dev is not None else None))
+
+
+class VoicednessExtractor:
+    """voicedness.flow: signal-window (rectangular) -> signal-vector-f32-resize -> mean-energy normalisation -> signal-cross-correlation
+    (x = y, FFT) -> signal-peak-detection:maximal-peak-value, one f32 per frame.  Keyword names are the fields of amx_voicedness_cfg;
+    normalization takes the node's words."""
+    NORMALIZATIONS = {"none": _lib.AMX_XCORR_NONE, "unbiased-estimate": _lib.AMX_XCORR_UNBIASED_ESTIMATE, "upper-bound": _lib.AMX_XCORR_UPPER_BOUND}
+
+    def __init__(self, ctx, **kw):
+        self.ctx, self.L = ctx, (ctx.L if ctx is not None else _lib.lib())
+        cfg = _lib.VoicednessCfg()
+        self.L.amx_voicedness_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("unknown voicedness parameter %r" % k)
+            if k == "normalization" and isinstance(v, str):
+                v = self.NORMALIZATIONS[v]
+            setattr(cfg, k, _tuning(v) if k == "tuning" else v)
+        self.cfg = cfg
+        h = C.c_void_p()
+        _lib.check(self.L.amx_voicedness_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+        info = _lib.VoicednessInfo()
+        _lib.check(self.L.amx_voicedness_describe(h, C.byref(info)))
+        self.info, self.n_lags = info, info.n_lags
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.amx_voicedness_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def n_frames(self, n_samples):
+        return int(self.L.amx_voicedness_n_frames(self.h, n_samples))
+
+    def run(self, pcm):
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        out = np.zeros(self.n_frames(len(pcm)), np.float32)
+        _lib.check(self.L.amx_voicedness_run(self.h, pcm.ctypes.data, len(pcm), out.ctypes.data))
+        return out
+
+    def run_batch_dev(self, sample_offsets, pcm_dev, out_dev, out_ld=1, acf_dev=None):
+        """torch tensors on the device (pcm_dev float32 or int16); sample_offsets: host int64 [n_seg + 1].  Frame t's measure goes
+        to out_dev.data_ptr() + 4 * t * out_ld: pass a column view of a wider matrix and its row stride."""
+        off = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        fn = self.L.amx_voicedness_run_batch_dev_s16 if pcm_dev.element_size() == 2 else self.L.amx_voicedness_run_batch_dev
+        _lib.check(fn(self.h, len(off) - 1, off.ctypes.data, pcm_dev.data_ptr(), out_dev.data_ptr(), int(out_ld),
+                      acf_dev.data_ptr() if acf_dev is not None else None))
+
+
+    def energy_dev(self, sample_offsets, pcm_dev, sum_dev, ordered_dev):
+        """test-only (amx_voicedness_energy_dev): per frame the normalisation's energy sum (float64) and whether one lane added it
+        in index order (int32 1) or the wave in lane order (0)"""
+        off = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        _lib.check(self.L.amx_voicedness_energy_dev(self.h, len(off) - 1, off.ctypes.data, pcm_dev.data_ptr(), sum_dev.data_ptr(),
+                                                    ordered_dev.data_ptr()))
 
 
 class MfccExtractor:

@@ -56,6 +56,20 @@ class GammatoneInfo(C.Structure):
                 ("n_out", C.c_int)]
 
 
+class VoicednessCfg(C.Structure):
+    _fields_ = [("sample_rate", C.c_double), ("win_len_s", C.c_double), ("win_shift_s", C.c_double), ("corr_begin_s", C.c_double),
+                ("corr_end_s", C.c_double), ("normalization", C.c_int), ("min_position_s", C.c_double), ("max_position_s", C.c_double),
+                ("tuning", C.c_char_p)]
+
+
+class VoicednessInfo(C.Structure):
+    _fields_ = [("frame_len", C.c_int), ("frame_shift", C.c_int), ("fft_len", C.c_int), ("n_lags", C.c_int), ("min_position", C.c_int),
+                ("max_position", C.c_int)]
+
+
+AMX_XCORR_NONE, AMX_XCORR_UNBIASED_ESTIMATE, AMX_XCORR_UPPER_BOUND = 0, 1, 2
+
+
 class MfccInfo(C.Structure):
     _fields_ = [("frame_len", C.c_int), ("frame_shift", C.c_int), ("fft_len", C.c_int), ("n_bins", C.c_int),
                 ("n_filters", C.c_int), ("n_ceps", C.c_int), ("fft_output_sample_rate", C.c_double),
@@ -114,6 +128,15 @@ SIGNATURES = {
     "amx_gammatone_tables": (C.c_int, [_P, _P, _P]),
     "amx_gammatone_run": (C.c_int, [_P, _P, C.c_long, _P]),
     "amx_gammatone_run_batch_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "amx_voicedness_default_cfg": (None, [C.POINTER(VoicednessCfg)]),
+    "amx_voicedness_create": (C.c_int, [_P, C.POINTER(VoicednessCfg), C.POINTER(C.c_void_p)]),
+    "amx_voicedness_destroy": (None, [_P]),
+    "amx_voicedness_describe": (C.c_int, [_P, C.POINTER(VoicednessInfo)]),
+    "amx_voicedness_n_frames": (C.c_long, [_P, C.c_long]),
+    "amx_voicedness_run": (C.c_int, [_P, _P, C.c_long, _P]),
+    "amx_voicedness_run_batch_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "amx_voicedness_run_batch_dev_s16": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "amx_voicedness_energy_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "amx_mfcc_equal_loudness": (C.c_int, [_P, _P]),
     "amx_mfcc_create": (C.c_int, [_P, C.POINTER(MfccCfg), C.POINTER(_P)]),
     "amx_mfcc_destroy": (None, [_P]),
