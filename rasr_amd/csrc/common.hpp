@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,58 @@ void set_error(const char* fmt, ...);
             return (status);             \
         }                                \
     } while (0)
+
+#define AMX_TRY(expr)       \
+    do {                    \
+        int r__ = (expr);   \
+        if (r__ != AMX_OK)  \
+            return r__;     \
+    } while (0)
+
+// An owning device buffer: a pointer and its capacity in elements (Pinned: page-locked host memory instead).  Nothing is allocated
+// until upload / reserve, and the destructor of an empty buffer makes no HIP call (host-only handles).
+template<class T, bool Pinned = false>
+class DevBuf {
+    T*     p_   = nullptr;
+    size_t cap_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&)            = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    T*     get() const { return p_; }
+    size_t capacity() const { return cap_; }
+    void   release() {
+        if (p_)
+            Pinned ? hipHostFree(p_) : hipFree(p_);
+        p_   = nullptr;
+        cap_ = 0;
+    }
+    // AMX_OK at once when the capacity suffices; otherwise the old memory is freed (its contents are not kept) and exactly n
+    // elements are allocated -- the workspaces are sized to what a call needs.  On failure the buffer is empty.
+    int reserve(size_t n) {
+        if (n <= cap_)
+            return AMX_OK;
+        release();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, n * sizeof(T)) : hipMalloc((void**)&p_, n * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            amx::set_error("allocation of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
+            return AMX_ERR_DEVICE;
+        }
+        cap_ = n;
+        return AMX_OK;
+    }
+    // a fresh allocation of max(n, 1) elements holding host[0, n)
+    int upload(const T* host, size_t n) {
+        release();
+        AMX_TRY(reserve(n > 1 ? n : 1));
+        if (n)
+            AMX_HIP(hipMemcpy(p_, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return AMX_OK;
+    }
+};
 
 // Per-kernel event timing (amx_profile_*): pairs of events recorded around a launch on the
 // context's current stream; resolved lazily in amx_profile_get.

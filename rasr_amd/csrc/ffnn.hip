@@ -23,6 +23,7 @@
 //     scores are comparable with the CPU sgemm path at 1e-6.
 //   * activations stay in HBM as bf16 between layers (288 GB: no need to fuse layers).
 #include "common.hpp"
+#include "gmm_internal.hpp"
 
 #include <hip/hip_bf16.h>
 
@@ -2481,8 +2482,6 @@ int amx_ffnn_input_dim(const amx_ffnn* h) {
 int amx_ffnn_output_dim(const amx_ffnn* h) {
     return h ? h->out.back() : 0;
 }
-
-extern "C" int amx_stats_accumulate_dev(amx_ctx*, const float*, int, int, uint32_t*, unsigned long long*, double*);
 
 // internal (not in amx.h): combine per-tile arg-min partials [n_tiles x part_ld]; shared with the GMM scorer's fused statistics
 extern "C" int amx_internal_best_state_reduce(amx_ctx* ctx, const float* part_min, const unsigned* part_idx, int n_tiles, int part_ld, int T,

@@ -27,6 +27,7 @@
 // are therefore bit-identical to the reference built with -DMARCH=x86-64 (contract=off, the default) or to its default build
 // (contract=fma) -- INTEGRATION.md has the table.
 #include "common.hpp"
+#include "gmm_internal.hpp"
 #include "gmm_device.hpp"
 
 #include <cfloat>
@@ -1604,6 +1605,76 @@ __global__ __launch_bounds__(256) void gmm_combine_kernel(const float* __restric
 
 // ------------------------------------------------------------------------------------ ABI
 
+struct GraphKey {
+    const void *feats, *scores, *best;
+    hipStream_t stream;
+    int         T;
+    bool operator<(const GraphKey& o) const {
+        return std::tie(feats, scores, best, stream, T) < std::tie(o.feats, o.scores, o.best, o.stream, o.T);
+    }
+};
+
+// Small-batch passes on unchanged device buffers (the decoder's ring buffer), recorded once and replayed as HIP graphs: the
+// amx_gmm_model.tuning graph=1 option (default 0: every pass is launched plainly).  A recorded pass holds the addresses of the
+// handle's workspaces, so whoever moves one of those calls clear() first.
+struct GraphCache {
+    enum Ran { kPlain, kRecorded, kReplayed };
+    std::map<GraphKey, hipGraphExec_t> graphs;
+    int                                use_graphs = 0;
+    GraphCache() = default;
+    GraphCache(const GraphCache&)            = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() { clear(); }
+    void clear() {
+        for (auto& kv : graphs)
+            if (kv.second)
+                hipGraphExecDestroy(kv.second);
+        graphs.clear();
+    }
+    // pass(capturing) enqueues the launches.  First call with a key: plain (it sizes the workspaces) and remembered; second call:
+    // captured, instantiated and launched; later calls: launched.  A caller that never repeats a signature (64 of them) or a
+    // stream that cannot capture switches graphs off.  *ran tells the caller which statistics the pass itself has kept.
+    template<class Pass>
+    int run(const GraphKey& key, hipStream_t stream, Pass&& pass, Ran* ran) {
+        *ran    = kPlain;
+        auto it = graphs.find(key);
+        if (it == graphs.end()) {
+            if (graphs.size() >= 64) {
+                clear();
+                use_graphs = 0;
+            }
+            else
+                graphs[key] = nullptr;
+            return pass(false);
+        }
+        hipGraphExec_t ex = it->second;
+        if (ex)
+            *ran = kReplayed;
+        else {
+            hipGraph_t g = nullptr;
+            if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+                (void)hipGetLastError();
+                use_graphs = 0;
+                return pass(false);
+            }
+            const int  r  = pass(true);
+            const bool ok = hipStreamEndCapture(stream, &g) == hipSuccess && r == AMX_OK && g != nullptr;
+            if (!ok || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                if (g)
+                    hipGraphDestroy(g);
+                use_graphs = 0;
+                return pass(false);
+            }
+            hipGraphDestroy(g);
+            graphs[key] = ex;  // by key: a pass that had to grow a workspace has emptied the map
+            *ran        = kRecorded;
+        }
+        AMX_HIP(hipGraphLaunch(ex, stream));
+        return AMX_OK;
+    }
+};
+
 struct amx_gmm {
     amx_ctx* ctx = nullptr;
     int      dim = 0, n_mix = 0, n_dens = 0, n_mean = 0, n_cov = 0;
@@ -1612,56 +1683,51 @@ struct amx_gmm {
     std::vector<float>    m2lw, isr, lognorm;
     std::vector<uint32_t> mix_off, h_k_dens, h_d_mean, h_d_cov;  // topology (accumulator files)
     // device
-    uint32_t *d_mix_off = nullptr, *d_k_mean = nullptr, *d_k_cov = nullptr, *d_k_dens = nullptr;
-    float *   d_means_t = nullptr, *d_isr_t = nullptr;  // same models: means / inverse deviations in list order, [dim][Kpad] (gmm_dist_list_kernel)
-    uint32_t* d_dens_pos = nullptr;  // shared-list models whose list names every density at most once: density -> list position (~0: not listed)
-    uint32_t *d_d_mean = nullptr, *d_d_cov = nullptr;
-    double*   d_k_c64 = nullptr;
-    float *   d_k_c32 = nullptr, *d_means = nullptr, *d_isr = nullptr;
+    amx::DevBuf<uint32_t> d_mix_off, d_k_mean, d_k_cov, d_k_dens;
+    amx::DevBuf<float>    d_means_t, d_isr_t;  // same models: means / inverse deviations in list order, [dim][Kpad] (gmm_dist_list_kernel)
+    amx::DevBuf<uint32_t> d_dens_pos;  // shared-list models whose list names every density at most once: density -> list position (~0: not listed)
+    amx::DevBuf<uint32_t> d_d_mean, d_d_cov;
+    amx::DevBuf<double>   d_k_c64;
+    amx::DevBuf<float>    d_k_c32, d_means, d_isr;
     // batch-float mode tables (pooled covariance only)
-    float *   d_smeans = nullptr, *d_k_const = nullptr, *d_isr0 = nullptr;
+    amx::DevBuf<float>    d_smeans, d_k_const, d_isr0;
     bool      pooled = false;
     bool      tied    = false;  // use the two-stage path
     bool      uniform = false;  // tied AND every mixture lists the same densities: lane = mixture combine
     int       K = 0, mix_pad = 0;
-    float*    d_m2lw_t = nullptr;  // [K][mix_pad]
-    float *   d_ahat_t = nullptr, *d_amax = nullptr;  // screen tables: fl32(m2lw + logNorm) [K][mix_pad], max_k |.| [mix_pad]
+    amx::DevBuf<float>    d_m2lw_t;  // [K][mix_pad]
+    amx::DevBuf<float>    d_ahat_t, d_amax;  // screen tables: fl32(m2lw + logNorm) [K][mix_pad], max_k |.| [mix_pad]
     // pruned path (gmm_tied.hip): per-tile minima of a^, per-call workspace, survivor statistics of earlier calls
-    float*              d_amin       = nullptr;  // [mix_pad / 64 + 1][Kpad]
-    unsigned short*     d_aup        = nullptr;  // [K][mix_pad] bf16 image of a^, rounded up (bounds only)
-    void*               d_tied_ws    = nullptr;
-    size_t              tied_ws_cap  = 0;
-    unsigned long long* d_tied_surv  = nullptr;  // [256] survivors (density, frame, tile) of the calls so far, spread over 256 counters; [256] = triples examined
-    unsigned long long* h_tied_surv  = nullptr;  // pinned host copy, refreshed asynchronously after every 8th pruned call (tied_publish)
+    amx::DevBuf<float>              d_amin;       // [mix_pad / 64 + 1][Kpad]
+    amx::DevBuf<unsigned short>     d_aup;        // [K][mix_pad] bf16 image of a^, rounded up (bounds only)
+    amx::DevBuf<char>               d_tied_ws;    // (bytes)
+    amx::DevBuf<unsigned long long> d_tied_surv;  // [256] survivors (density, frame, tile) of the calls so far, spread over 256 counters; [256] = triples examined
+    amx::DevBuf<unsigned long long, true> h_tied_surv;  // pinned host copy, refreshed asynchronously after every 8th pruned call (tied_publish)
     unsigned            tied_copy_tick = 0;      // pruned calls since the handle was made
-    bool                tied_capturing = false;
-    bool                tied_keys_clean = false;  // the workspace's near keys are in their empty state (gmm_dist_list_kernel's atomics start from it)  // the pruned launches are being recorded: the copy stays outside the graph
+    bool                tied_capturing = false;  // the pruned launches are being recorded: the copy stays outside the graph
+    bool                tied_keys_clean = false;  // the workspace's near keys are in their empty state (gmm_dist_list_kernel's atomics start from it)
     unsigned long long  tied_seen    = 0;        // survivors / examined triples in the host copy at the previous decision
     unsigned long long  tied_triples = 0;
     int                 tied_dense_calls = 0;    // > 0: stay on gmm_tied_tile_kernel for that many calls, then probe again
     unsigned long long  tied_rep_seen = 0, tied_rep_triples = 0;  // amx_gmm_screen_counts: counter value / triples at the last report
-    int                 tied_forced = -1;        // set around a nested call: 1 = pruned path, 0 = dense kernel, -1 = decide
-    double *  d_ln64 = nullptr, *d_dist64 = nullptr;
-    float*    d_ln32 = nullptr;
-    size_t    dist64_cap = 0;
-    float*    d_dist  = nullptr;
-    size_t    dist_floats = 0;
+    amx::DevBuf<double> d_ln64, d_dist64;
+    amx::DevBuf<float>  d_ln32;
+    amx::DevBuf<float>  d_dist;
     // MFMA screen (private-density models, <= 16 densities per mixture; see gmm_screen_kernel)
     bool      screen = false;
     int       scr_Kp = 0, scr_Rpad = 0, scr_Mpad16 = 0;
     float     scr_rmax2 = 0.f, scr_na_all = 0.f;
-    _Float16* d_scr_A = nullptr;
-    _Float16* d_scr_A2 = nullptr;  // K = 64 only: the slot rows in gmm_screen_rows_kernel's order
-    float *   d_scr_c = nullptr, *d_scr_na = nullptr, *d_scr_cabs = nullptr;
-    // per-call workspace of the screen
-    _Float16* d_scr_X = nullptr;
-    float *   d_scr_nx = nullptr, *d_scr_q = nullptr;
-    uint16_t* d_scr_masks = nullptr;
+    amx::DevBuf<_Float16> d_scr_A;
+    amx::DevBuf<_Float16> d_scr_A2;  // K = 64 only: the slot rows in gmm_screen_rows_kernel's order
+    amx::DevBuf<float>    d_scr_c, d_scr_na, d_scr_cabs;
+    // per-call workspace of the screen, sized together for scr_cap_T frames
+    amx::DevBuf<_Float16> d_scr_X;
+    amx::DevBuf<float>    d_scr_nx, d_scr_q;
+    amx::DevBuf<uint16_t> d_scr_masks;
     int       scr_cap_T = 0;
     // staging buffers of the host-buffer entry point amx_gmm_score
-    float *   d_host_f = nullptr, *d_host_s = nullptr;
-    uint32_t* d_host_b = nullptr;
-    size_t    host_f_cap = 0, host_s_cap = 0, host_b_cap = 0;
+    amx::DevBuf<float>    d_host_f, d_host_s;
+    amx::DevBuf<uint32_t> d_host_b;
     void*     simd = nullptr;        // SIMD-diagonal-maximum tables and workspaces (gmm_simd.hip), built on first use
     std::vector<float>  h_means, h_vars;   // host copies of the model for that lazy build
     std::vector<double> h_logw;
@@ -1673,17 +1739,7 @@ struct amx_gmm {
     float     presel_backoff = 40000.f;
     std::vector<uint32_t> h_k_mean;
     std::vector<float>    h_smeans;
-    // small-batch passes of the screened scorer on unchanged device buffers (the decoder's ring buffer), replayed as HIP graphs
-    struct GraphKey {
-        const void *feats, *scores, *best;
-        hipStream_t stream;
-        int         T;
-        bool operator<(const GraphKey& o) const {
-            return std::tie(feats, scores, best, stream, T) < std::tie(o.feats, o.scores, o.best, o.stream, o.T);
-        }
-    };
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    int                                use_graphs = 1;
+    GraphCache graphs;  // recorded passes of the screened CART path and of the pruned tied path
     // amx_gmm_model.tuning (A/B runs, tests)
     int         tune_screen = 1, tune_fused = 1, tune_screen_all = 0, tune_tied_prune = -1, tune_chunk = 65536, tune_fused_waves = 0, tune_fr = 8,
                 tune_simd_mfma = 1, tune_dist_list = 1, tune_near_fused = 1, tune_fused_pack = 1;
@@ -1692,103 +1748,65 @@ struct amx_gmm {
     // (-march=native on an FMA host); off (default) = the reference built with -DMARCH=x86-64.  Not a speed switch: it selects WHICH
     // build of RASR the scores are bit-identical to.
     bool        contract_fma = false;
-    void*     d_fus_rec = nullptr;   // tile records of gmm_fused_kernel (pooled covariance, dim <= 40)
-    uint32_t* d_best32   = nullptr;  // u32 workspace of amx_gmm_score_stats_u8_dev on paths without a byte-writing kernel
-    size_t    best32_cap = 0;
-    unsigned long long* d_fus_surv = nullptr;  // [256] partial counts of the densities evaluated exactly (amx_gmm_screen_counts): one
-                                               // address for every wave's atomicAdd cost a quarter of a 256-frame pass
-    size_t    fus_rec_bytes = 0;
+    amx::DevBuf<char>     d_fus_rec;  // tile records of gmm_fused_kernel (pooled covariance, dim <= 40)
+    amx::DevBuf<uint32_t> d_best32;   // u32 workspace of amx_gmm_score_stats_u8_dev on paths without a byte-writing kernel
+    amx::DevBuf<unsigned long long> d_fus_surv;  // [256] partial counts of the densities evaluated exactly (amx_gmm_screen_counts): one
+                                                 // address for every wave's atomicAdd cost a quarter of a 256-frame pass
     bool      count_survivors = false;
     unsigned long long fus_pairs = 0;
-    float*    d_scr_pmin = nullptr;  // fused statistics: per-tile arg-min partials
-    unsigned* d_scr_pidx = nullptr;
-    size_t    scr_part_cap = 0;
+    // fused statistics: per-tile arg-min partials, sized together
+    amx::DevBuf<float>    d_scr_pmin;
+    amx::DevBuf<unsigned> d_scr_pidx;
 };
 
 namespace {
 
-template<class T>
-int gupload(T** dst, const T* src, size_t n) {
-    AMX_HIP(hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n)
-        AMX_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return AMX_OK;
-}
-
-bool screen_dim_supported(int d) {
-    switch (d) {
-        case 16: case 24: case 32: case 33: case 39: case 40: case 45: case 48: case 64: return true;
-        default: return false;
+// Run-time values as template arguments: with_dim calls f(std::integral_constant<int, D>) with D = dim where the kernels have instances
+// of their own (AMX_GMM_DIMS) and D = 0 otherwise, with_flag calls f(std::true_type / std::false_type).  A kernel family that lacks
+// an instance says so with `if constexpr` in f.  (Nested, they name a family's instances in a fixed order, which is the order of the
+// kernels in the code object.)
+template<class F>
+auto with_dim(int dim, F&& f) {
+    switch (dim) {
+#define X(D) \
+    case D: return f(std::integral_constant<int, D>{});
+        AMX_GMM_DIMS(X)
+#undef X
+        default: return f(std::integral_constant<int, 0>{});
     }
 }
+template<class F>
+auto with_flag(bool flag, F&& f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
 
-extern "C" int   amx_internal_gmm_presel_create(amx_ctx* ctx, int dim, size_t nk, const uint32_t* k_mean_host, const float* smeans_host,
-                                                const float* d_smeans, const uint32_t* d_k_mean, int n_clusters, int n_select, int iterations,
-                                                float backoff, int contract_fma, void** out);
-extern "C" void  amx_internal_gmm_presel_destroy(void* p);
-extern "C" int   amx_internal_gmm_presel_info(const void* p, int* n_clusters, uint32_t* cluster_of, float* cluster_means);
-extern "C" int   amx_internal_gmm_presel_score(void* p, amx_ctx* ctx, const float* feats_dev, int T, float* scores_dev, const uint32_t* d_mix_off,
-                                               const uint32_t* d_k_mean, const float* d_k_const, const float* d_smeans, const float* d_isr0,
-                                               int n_mix);
-extern "C" int   amx_internal_gmm_simd_create(const amx_gmm_model* m, int contract_fma, void** out, float* scaling_out);
-extern "C" void  amx_internal_gmm_simd_destroy(void* p);
-extern "C" float amx_internal_gmm_simd_scaling(const void* p);
-extern "C" int   amx_internal_gmm_simd_score(void* p, amx_ctx* ctx, int variant, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev);
-extern "C" int   amx_internal_gmm_simd_presel_build(void* p, amx_ctx* ctx, int n_clusters, int n_select, int iterations);
-extern "C" int   amx_internal_gmm_simd_presel_info(const void* p, int* n_clusters, uint32_t* cluster_of, float* cluster_means);
-extern "C" int   amx_internal_gmm_simd_presel_score(void* p, amx_ctx* ctx, const float* feats_dev, int T, float* scores_dev);
-
-extern "C" int    amx_internal_gmm_tied_create(int K, int n_mix, int mix_pad, const float* ahat_t_host, float** d_amin, unsigned short** d_aup);
-extern "C" size_t amx_internal_gmm_tied_workspace(int K, int T, int mix_pad);
-extern "C" int    amx_internal_gmm_tied_score(amx_ctx* ctx, const float* dist_dev, const uint32_t* k_dens_dev, int K, int T, int Tpad, int n_mix,
-                                              int mix_pad, const unsigned short* aup, const float* amax, const float* m2lw_t, const float* ahat_t,
-                                              const double* ln64, const float* ln32, const float* amin, void* workspace, float* scores,
-                                              uint32_t* best, unsigned long long* survivors_dev, int dt_written, int near_written);
-extern "C" float* amx_internal_gmm_tied_dt(void* workspace, int K, int T, int have_positions);
-extern "C" unsigned long long* amx_internal_gmm_tied_near(void* workspace);
-extern "C" int                 amx_internal_gmm_tied_near_init(amx_ctx* ctx, void* workspace);
-extern "C" int amx_internal_gmm_fused_supported(int dim, int pooled, int Kp);
-extern "C" int amx_internal_gmm_fused_create(int dim, int n_mix, int n_tiles, const void* A2_host, const uint32_t* mix_off, const uint32_t* k_mean,
-                                             const double* c64, const float* means, const float* p1, const float* p2, void** rec_dev,
-                                             size_t* rec_bytes);
-extern "C" int amx_internal_gmm_fused_split(int n_cu, int Tpad, int n_tiles, int forced_waves);
-extern "C" int amx_internal_gmm_fused_score(amx_ctx* ctx, int dim, const void* rec_dev, const float* isr_dev, const float* feats, const void* X,
-                                            const float* nx, const float* q, int T, int Tpad, int n_mix, int n_tiles, int split, float* scores,
-                                            uint32_t* best, float* pmin, unsigned* pidx, int part_ld, unsigned long long* survivors, int forced_waves,
-                                            int best_bytes, int contract_fma, float na_all);
-extern "C" int amx_internal_gmm_fused_waves(int Tpad, int forced_waves);
+bool screen_dim_supported(int dim) {
+    return with_dim(dim, [](auto d) { return d.value != 0; });
+}
 
 // maximum approximation through the MFMA screen (see gmm_screen_kernel); frames in chunks that bound the mask workspace
-extern "C" int amx_internal_best_state_reduce(amx_ctx*, const float*, const unsigned*, int, int, int, uint32_t*, unsigned long long*, double*);
-
 // best_bytes = 1 (fused path only, see fused_bytes_ok): best_dev is a byte matrix [T x n_mix] (amx_gmm_score_stats_u8_dev)
 int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev, bool stats, uint32_t* best_state_dev,
                    unsigned long long* counts_dev, double* score_sum_dev, int best_bytes = 4) {
     hipStream_t st = h->ctx->stream;
     const int   chunk = h->tune_chunk;  // frames per pass: the workspace (survivor masks, 2 B per frame and mixture slot) grows to what a call needs
     // one fused kernel (gmm_fused.hip) where its tile records exist; tuning fused=0 keeps the two-kernel path (A/B runs, tests)
-    const bool fused = h->d_fus_rec && h->tune_fused && !h->tune_screen_all;
+    const bool fused = h->d_fus_rec.get() && h->tune_fused && !h->tune_screen_all;
     AMX_REQUIRE(best_bytes == 4 || (best_bytes == 1 && fused), AMX_ERR_STATE, "score_screened: byte-sized best densities exist on the fused path only");
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int Tc = std::min(chunk, T - t0), Tpad = (Tc + 255) / 256 * 256;
-        if (Tpad > h->scr_cap_T || (!fused && !h->d_scr_masks)) {
-            for (auto& kv : h->graphs)  // captured passes hold the old workspace addresses: drop them before the buffers move
-                if (kv.second)
-                    hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            hipFree(h->d_scr_X);
-            hipFree(h->d_scr_nx);
-            hipFree(h->d_scr_q);
-            hipFree(h->d_scr_masks);
-            h->d_scr_X = nullptr;
-            h->d_scr_nx = h->d_scr_q = nullptr;
-            h->d_scr_masks = nullptr;
+        if (Tpad > h->scr_cap_T || (!fused && !h->d_scr_masks.get())) {
+            h->graphs.clear();  // captured passes hold the old workspace addresses: drop them before the buffers move
+            h->d_scr_X.release();
+            h->d_scr_nx.release();
+            h->d_scr_q.release();
+            h->d_scr_masks.release();
             h->scr_cap_T = 0;
-            AMX_HIP(hipMalloc((void**)&h->d_scr_X, (size_t)Tpad * h->scr_Kp * sizeof(_Float16)));
-            AMX_HIP(hipMalloc((void**)&h->d_scr_nx, (size_t)Tpad * 4));
-            AMX_HIP(hipMalloc((void**)&h->d_scr_q, (size_t)Tpad * 4));
+            AMX_TRY(h->d_scr_X.reserve((size_t)Tpad * h->scr_Kp));
+            AMX_TRY(h->d_scr_nx.reserve((size_t)Tpad));
+            AMX_TRY(h->d_scr_q.reserve((size_t)Tpad));
             if (!fused)
-                AMX_HIP(hipMalloc((void**)&h->d_scr_masks, (size_t)Tpad * h->scr_Mpad16 * 2));
+                AMX_TRY(h->d_scr_masks.reserve((size_t)Tpad * h->scr_Mpad16));
             h->scr_cap_T = Tpad;
         }
         const float*       x = feats_dev + (size_t)t0 * h->dim;
@@ -1798,7 +1816,7 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
         const bool own_pack = fused && h->tune_fused_pack && h->tune_fused_waves != 13;
         if (!own_pack) {
             amx::ScopedKernelTimer timer(h->ctx, "gmm_screen_pack");
-            hipLaunchKernelGGL(amx::gmm_screen_pack_kernel, dim3(Tpad / 4), dim3(256), 0, st, x, h->d_isr, h->d_scr_X, h->d_scr_nx, h->d_scr_q, d);
+            hipLaunchKernelGGL(amx::gmm_screen_pack_kernel, dim3(Tpad / 4), dim3(256), 0, st, x, h->d_isr.get(), h->d_scr_X.get(), h->d_scr_nx.get(), h->d_scr_q.get(), d);
         }
         if (fused) {
             const int n_tiles = h->scr_Rpad / 256;
@@ -1806,26 +1824,18 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
             float*    pmin    = nullptr;
             unsigned* pidx    = nullptr;
             if (stats) {
-                const size_t need = (size_t)split * Tpad;
-                if (need > h->scr_part_cap) {
-                    hipFree(h->d_scr_pmin);
-                    hipFree(h->d_scr_pidx);
-                    h->d_scr_pmin   = nullptr;
-                    h->d_scr_pidx   = nullptr;
-                    h->scr_part_cap = 0;
-                    AMX_HIP(hipMalloc((void**)&h->d_scr_pmin, need * 4));
-                    AMX_HIP(hipMalloc((void**)&h->d_scr_pidx, need * 4));
-                    h->scr_part_cap = need;
-                }
-                pmin = h->d_scr_pmin;
-                pidx = h->d_scr_pidx;
+                const size_t need = (size_t)split * Tpad;  // (recorded passes never use the partials: the graphs stay)
+                AMX_TRY(h->d_scr_pmin.reserve(need));
+                AMX_TRY(h->d_scr_pidx.reserve(need));
+                pmin = h->d_scr_pmin.get();
+                pidx = h->d_scr_pidx.get();
             }
             {
                 amx::ScopedKernelTimer timer(h->ctx, "gmm");
-                int r = amx_internal_gmm_fused_score(h->ctx, h->dim, h->d_fus_rec, h->d_isr, x, own_pack ? nullptr : h->d_scr_X, h->d_scr_nx, h->d_scr_q, Tc, Tpad,
+                int r = amx_internal_gmm_fused_score(h->ctx, h->dim, h->d_fus_rec.get(), h->d_isr.get(), x, own_pack ? nullptr : h->d_scr_X.get(), h->d_scr_nx.get(), h->d_scr_q.get(), Tc, Tpad,
                                                      h->n_mix, n_tiles, split, scores_dev + (size_t)t0 * h->n_mix,
                                                      best_dev ? (uint32_t*)((char*)best_dev + (size_t)t0 * h->n_mix * best_bytes) : nullptr, pmin,
-                                                     pidx, Tpad, h->count_survivors ? h->d_fus_surv : nullptr, h->tune_fused_waves, best_bytes,
+                                                     pidx, Tpad, h->count_survivors ? h->d_fus_surv.get() : nullptr, h->tune_fused_waves, best_bytes,
                                                      h->contract_fma ? 1 : 0, h->scr_na_all);
                 if (r != AMX_OK)
                     return r;
@@ -1851,8 +1861,8 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
                 hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
                 // two workgroups per CU, each a frame tile x a contiguous range of slot tiles
                 const int split = std::max(1, std::min(ntr, (2 * std::max(h->ctx->n_cu, 8) + ntt - 1) / ntt));
-                hipLaunchKernelGGL(k, dim3(ntt * split), dim3(512), lds, st, h->d_scr_A2, h->d_scr_X, h->d_scr_na, h->d_scr_cabs, h->d_scr_nx,
-                                   h->d_scr_q, h->d_scr_masks, ntr, split, h->scr_Mpad16);
+                hipLaunchKernelGGL(k, dim3(ntt * split), dim3(512), lds, st, h->d_scr_A2.get(), h->d_scr_X.get(), h->d_scr_na.get(), h->d_scr_cabs.get(), h->d_scr_nx.get(),
+                                   h->d_scr_q.get(), h->d_scr_masks.get(), ntr, split, h->scr_Mpad16);
             }
             else if (h->scr_Kp == 64 && strcmp(variant, "simple")) {
                 auto      k   = amx::gmm_screen_persist_kernel;
@@ -1860,40 +1870,32 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
                 hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
                 // one workgroup per CU, each a frame tile x a contiguous range of slot tiles
                 const int split = std::max(1, std::min(ntr, (std::max(h->ctx->n_cu, 8) + ntt - 1) / ntt));
-                hipLaunchKernelGGL(k, dim3(ntt * split), dim3(512), lds, st, h->d_scr_A, h->d_scr_X, h->d_scr_c, h->d_scr_na, h->d_scr_cabs,
-                                   h->d_scr_nx, h->d_scr_q, h->d_scr_masks, ntr, split, d);
+                hipLaunchKernelGGL(k, dim3(ntt * split), dim3(512), lds, st, h->d_scr_A.get(), h->d_scr_X.get(), h->d_scr_c.get(), h->d_scr_na.get(), h->d_scr_cabs.get(),
+                                   h->d_scr_nx.get(), h->d_scr_q.get(), h->d_scr_masks.get(), ntr, split, d);
             }
             else if (h->scr_Kp == 64) {
                 auto k = amx::gmm_screen_kernel<1>;
                 hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 + 1024);
-                hipLaunchKernelGGL(k, dim3(ntr * ntt), dim3(512), 64 * 1024 + 1024, st, h->d_scr_A, h->d_scr_X, h->d_scr_c, h->d_scr_na,
-                                   h->d_scr_cabs, h->d_scr_nx, h->d_scr_q, h->d_scr_masks, ntr, d);
+                hipLaunchKernelGGL(k, dim3(ntr * ntt), dim3(512), 64 * 1024 + 1024, st, h->d_scr_A.get(), h->d_scr_X.get(), h->d_scr_c.get(), h->d_scr_na.get(),
+                                   h->d_scr_cabs.get(), h->d_scr_nx.get(), h->d_scr_q.get(), h->d_scr_masks.get(), ntr, d);
             }
             else {
                 auto k = amx::gmm_screen_kernel<2>;
                 hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024 + 1024);
-                hipLaunchKernelGGL(k, dim3(ntr * ntt), dim3(512), 128 * 1024 + 1024, st, h->d_scr_A, h->d_scr_X, h->d_scr_c, h->d_scr_na,
-                                   h->d_scr_cabs, h->d_scr_nx, h->d_scr_q, h->d_scr_masks, ntr, d);
+                hipLaunchKernelGGL(k, dim3(ntr * ntt), dim3(512), 128 * 1024 + 1024, st, h->d_scr_A.get(), h->d_scr_X.get(), h->d_scr_c.get(), h->d_scr_na.get(),
+                                   h->d_scr_cabs.get(), h->d_scr_nx.get(), h->d_scr_q.get(), h->d_scr_masks.get(), ntr, d);
             }
         }
         if (h->tune_screen_all)  // debugging aid: every slot survives (the exact stage then evaluates all densities)
-            hipMemsetAsync(h->d_scr_masks, 0xff, (size_t)Tpad * h->scr_Mpad16 * 2, st);
+            hipMemsetAsync(h->d_scr_masks.get(), 0xff, (size_t)Tpad * h->scr_Mpad16 * 2, st);
         float*    pmin = nullptr;
         unsigned* pidx = nullptr;
         if (stats) {
             const size_t need = (size_t)(h->scr_Mpad16 / 16) * Tpad;
-            if (need > h->scr_part_cap) {
-                hipFree(h->d_scr_pmin);
-                hipFree(h->d_scr_pidx);
-                h->d_scr_pmin = nullptr;
-                h->d_scr_pidx = nullptr;
-                h->scr_part_cap = 0;
-                AMX_HIP(hipMalloc((void**)&h->d_scr_pmin, need * 4));
-                AMX_HIP(hipMalloc((void**)&h->d_scr_pidx, need * 4));
-                h->scr_part_cap = need;
-            }
-            pmin = h->d_scr_pmin;
-            pidx = h->d_scr_pidx;
+            AMX_TRY(h->d_scr_pmin.reserve(need));
+            AMX_TRY(h->d_scr_pidx.reserve(need));
+            pmin = h->d_scr_pmin.get();
+            pidx = h->d_scr_pidx.get();
         }
         {
             amx::ScopedKernelTimer timer(h->ctx, "gmm");
@@ -1903,35 +1905,20 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
             dim3      grid(h->scr_Mpad16 / 16, (Tpad / 256 + FG - 1) / FG);
             float*    sc = scores_dev + (size_t)t0 * h->n_mix;
             uint32_t* bd = best_dev ? best_dev + (size_t)t0 * h->n_mix : nullptr;
-#define AMX_EXACT(D)                                                                                                                \
-    case D: {                                                                                                                       \
-        const size_t lds = (size_t)256 * amx::gmm_exact_ld(D, h->pooled) * 4 * (h->pooled ? 1 : 2) + 2048 + 2112 + 256 * 17 * 4 + 256 * 20 + 256 * amx::gmm_list_cap(D, h->pooled); \
-        if (h->pooled) {                                                                                                            \
-            auto k = h->contract_fma ? amx::gmm_screen_exact_kernel<D, true, true> : amx::gmm_screen_exact_kernel<D, true, false>;  \
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-            hipLaunchKernelGGL(k, grid, dim3(256), lds, st, x, h->d_scr_masks, h->d_mix_off, h->d_k_mean, h->d_k_cov, h->d_k_c64,   \
-                               h->d_means, h->d_isr, sc, bd, Tc, h->n_mix, h->scr_Mpad16, pmin, pidx, Tpad, FG);                                          \
-        }                                                                                                                           \
-        else {                                                                                                                      \
-            auto k = h->contract_fma ? amx::gmm_screen_exact_kernel<D, false, true> : amx::gmm_screen_exact_kernel<D, false, false>; \
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-            hipLaunchKernelGGL(k, grid, dim3(256), lds, st, x, h->d_scr_masks, h->d_mix_off, h->d_k_mean, h->d_k_cov, h->d_k_c64,   \
-                               h->d_means, h->d_isr, sc, bd, Tc, h->n_mix, h->scr_Mpad16, pmin, pidx, Tpad, FG);                                          \
-        }                                                                                                                           \
-    } break;
-            switch (h->dim) {
-                AMX_EXACT(16)
-                AMX_EXACT(24)
-                AMX_EXACT(32)
-                AMX_EXACT(33)
-                AMX_EXACT(39)
-                AMX_EXACT(40)
-                AMX_EXACT(45)
-                AMX_EXACT(48)
-                AMX_EXACT(64)
-                default: break;
-            }
-#undef AMX_EXACT
+            with_dim(h->dim, [&](auto dc) {
+                constexpr int D = decltype(dc)::value;
+                if constexpr (D != 0) {  // (the screen tables exist for the listed dimensions only: screen_dim_supported)
+                    const size_t lds = (size_t)256 * amx::gmm_exact_ld(D, h->pooled) * 4 * (h->pooled ? 1 : 2) + 2048 + 2112 + 256 * 17 * 4 + 256 * 20 + 256 * amx::gmm_list_cap(D, h->pooled);
+                    with_flag(h->pooled, [&](auto pc) {
+                        with_flag(h->contract_fma, [&](auto fc) {
+                            auto k = amx::gmm_screen_exact_kernel<D, decltype(pc)::value, decltype(fc)::value>;
+                            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                            hipLaunchKernelGGL(k, grid, dim3(256), lds, st, x, h->d_scr_masks.get(), h->d_mix_off.get(), h->d_k_mean.get(), h->d_k_cov.get(),
+                                               h->d_k_c64.get(), h->d_means.get(), h->d_isr.get(), sc, bd, Tc, h->n_mix, h->scr_Mpad16, pmin, pidx, Tpad, FG);
+                        });
+                    });
+                }
+            });
         }
         AMX_HIP(hipGetLastError());
         if (stats) {
@@ -1947,66 +1934,33 @@ int score_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev,
 
 template<class State>
 int launch_direct(amx_gmm* h, const amx::GmmParams& p, dim3 grid) {
-    hipStream_t  st  = h->ctx->stream;
-    size_t       lds = 0;
     amx::GmmDims dims{p.T, p.dim, p.n_mix, p.mix_tile};
-    switch (h->dim) {
-#define AMX_GMM_CASE(D)                                                                                  \
-    case D: {                                                                                            \
-        auto k = h->contract_fma ? amx::gmm_direct_kernel<D, State, true> : amx::gmm_direct_kernel<D, State, false>; \
-        hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p.feats, p.scores, p.best,                          \
-                               p.mix_off, p.k_mean, p.k_cov, p.k_c64, p.k_c32, p.means, p.isr, dims);       \
-    } break;
-        AMX_GMM_CASE(16)
-        AMX_GMM_CASE(24)
-        AMX_GMM_CASE(32)
-        AMX_GMM_CASE(33)
-        AMX_GMM_CASE(39)
-        AMX_GMM_CASE(40)
-        AMX_GMM_CASE(45)
-        AMX_GMM_CASE(48)
-        AMX_GMM_CASE(64)
-#undef AMX_GMM_CASE
-        default:
-            lds = (size_t)4 * 64 * h->dim * sizeof(float);
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_direct_kernel<0, State, true> : amx::gmm_direct_kernel<0, State, false>), grid, dim3(256),
-                               lds, st, p.feats, p.scores, p.best, p.mix_off, p.k_mean, p.k_cov, p.k_c64, p.k_c32, p.means, p.isr, dims);
-    }
+    with_dim(h->dim, [&](auto dc) {
+        constexpr int D   = decltype(dc)::value;
+        const size_t  lds = D ? 0 : (size_t)4 * 64 * h->dim * sizeof(float);
+        with_flag(h->contract_fma, [&](auto fc) {
+            hipLaunchKernelGGL((amx::gmm_direct_kernel<D, State, decltype(fc)::value>), grid, dim3(256), lds, h->ctx->stream, p.feats, p.scores, p.best,
+                               p.mix_off, p.k_mean, p.k_cov, p.k_c64, p.k_c32, p.means, p.isr, dims);
+        });
+    });
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
 
 int launch_dist(amx_gmm* h, const amx::GmmDistParams& p, dim3 grid, double* dist64, bool stage, float* dt = nullptr, int dt_ld = 0) {
-    hipStream_t      st  = h->ctx->stream;
-    size_t           lds = 0;
     amx::GmmDistDims dims{p.T, p.Tpad, p.dim, p.n_dens, p.dens_tile};
-    switch (h->dim) {
-#define AMX_GMM_CASE(D)                                                                                                                   \
-    case D:                                                                                                                               \
-        if (stage)                                                                                                                        \
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_dist_kernel<D, true, true> : amx::gmm_dist_kernel<D, true, false>), grid, dim3(256), \
-                               (size_t)256 * (D + 1) * sizeof(float), st, p.feats, p.dist,                                               \
-                               dist64, p.d_mean, p.d_cov, p.means, p.isr, dims, dt, (const uint32_t*)h->d_dens_pos, dt_ld);               \
-        else                                                                                                                              \
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_dist_kernel<D, false, true> : amx::gmm_dist_kernel<D, false, false>), grid,    \
-                               dim3(256), 0, st, p.feats, p.dist, dist64, p.d_mean, p.d_cov, p.means,                                    \
-                               p.isr, dims, dt, (const uint32_t*)h->d_dens_pos, dt_ld);                                                   \
-        break;
-        AMX_GMM_CASE(16)
-        AMX_GMM_CASE(24)
-        AMX_GMM_CASE(32)
-        AMX_GMM_CASE(33)
-        AMX_GMM_CASE(39)
-        AMX_GMM_CASE(40)
-        AMX_GMM_CASE(45)
-        AMX_GMM_CASE(48)
-        AMX_GMM_CASE(64)
-#undef AMX_GMM_CASE
-        default:
-            lds = (size_t)4 * 64 * h->dim * sizeof(float);
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_dist_kernel<0, false, true> : amx::gmm_dist_kernel<0, false, false>), grid, dim3(256), lds, st, p.feats, p.dist, dist64, p.d_mean, p.d_cov, p.means,
-                               p.isr, dims, dt, (const uint32_t*)h->d_dens_pos, dt_ld);
-    }
+    with_dim(h->dim, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        auto launch = [&](auto k, size_t lds) {
+            hipLaunchKernelGGL(k, grid, dim3(256), lds, h->ctx->stream, p.feats, p.dist, dist64, p.d_mean, p.d_cov, p.means, p.isr, dims, dt,
+                               (const uint32_t*)h->d_dens_pos.get(), dt_ld);
+        };
+        if constexpr (D != 0) {  // (the fallback has no staging form)
+            if (stage)
+                return with_flag(h->contract_fma, [&](auto fc) { launch(amx::gmm_dist_kernel<D, true, decltype(fc)::value>, (size_t)256 * (D + 1) * sizeof(float)); });
+        }
+        with_flag(h->contract_fma, [&](auto fc) { launch(amx::gmm_dist_kernel<D, false, decltype(fc)::value>, D ? 0 : (size_t)4 * 64 * h->dim * sizeof(float)); });
+    });
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -2021,40 +1975,34 @@ int launch_dist_list(amx_gmm* h, const float* feats, int T, float* dt, unsigned 
     if (h->tune_dist_list > 1)
         frames = h->tune_dist_list;
     const dim3 grid(amx::ceil_div(Kpad, 256), amx::ceil_div(T, frames));
-    switch (h->dim) {
-#define AMX_GMM_CASE(D)                                                                                                                         \
-    case D:                                                                                                                                     \
-        if (near)                                                                                                                               \
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_dist_list_kernel<D, true, true> : amx::gmm_dist_list_kernel<D, false, true>), grid,  \
-                               dim3(256), 0, h->ctx->stream, feats, h->d_means_t, h->d_isr_t, h->K, Kpad, T, frames, dt, near);                 \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((h->contract_fma ? amx::gmm_dist_list_kernel<D, true, false> : amx::gmm_dist_list_kernel<D, false, false>), grid,\
-                               dim3(256), 0, h->ctx->stream, feats, h->d_means_t, h->d_isr_t, h->K, Kpad, T, frames, dt, near);                 \
-        break;
-        AMX_GMM_CASE(16)
-        AMX_GMM_CASE(24)
-        AMX_GMM_CASE(32)
-        AMX_GMM_CASE(33)
-        AMX_GMM_CASE(39)
-        AMX_GMM_CASE(40)
-        AMX_GMM_CASE(45)
-        AMX_GMM_CASE(48)
-#undef AMX_GMM_CASE
-        default:
-            return AMX_ERR_STATE;
-    }
+    const int r = with_dim(h->dim, [&](auto dc) {
+        constexpr int D = decltype(dc)::value;
+        if constexpr (D == 0 || D == 64)  // the kernel keeps 2 x D table values in registers: no such instances
+            return (int)AMX_ERR_STATE;
+        else {
+            with_flag(near != nullptr, [&](auto nc) {
+                with_flag(h->contract_fma, [&](auto fc) {
+                    hipLaunchKernelGGL((amx::gmm_dist_list_kernel<D, decltype(fc)::value, decltype(nc)::value>), grid, dim3(256), 0, h->ctx->stream, feats,
+                                       h->d_means_t.get(), h->d_isr_t.get(), h->K, Kpad, T, frames, dt, near);
+                });
+            });
+            return (int)AMX_OK;
+        }
+    });
+    if (r != AMX_OK)
+        return r;
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
 
-}  // namespace
+// the per-entry tables amx_gmm_create prepares on the host for the uploads and the screen tables
+struct HostTables {
+    std::vector<uint32_t> k_mean, k_cov, k_dens;
+    std::vector<double>   c64;
+    std::vector<float>    c32;
+};
 
-extern "C" {
-
-int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
-    // ctx == NULL creates a host-only handle (prepared tables only; scoring returns AMX_ERR_STATE)
-    AMX_REQUIRE(m && out, AMX_ERR_INVALID, "amx_gmm_create: NULL argument");
-    *out = nullptr;
+int check_model(const amx_gmm_model* m) {
     AMX_REQUIRE(m->dim > 0 && m->n_mix > 0 && m->n_dens > 0 && m->n_mean > 0 && m->n_cov > 0, AMX_ERR_INVALID,
                 "amx_gmm_create: empty mixture set");
     AMX_REQUIRE(m->dim <= 1024, AMX_ERR_UNSUPPORTED, "amx_gmm_create: feature dimension %d > 1024", m->dim);
@@ -2071,45 +2019,240 @@ int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
     // CovarianceFeatureScorerElement::checkDiagonal: require(all variances > 0)
     for (size_t i = 0; i < (size_t)m->n_cov * m->dim; ++i)
         AMX_REQUIRE(m->variances[i] > 0, AMX_ERR_INVALID, "amx_gmm_create: non-positive variance");
+    return AMX_OK;
+}
 
+// amx_gmm_model.tuning: values are checked like keys -- a typo must not silently select the default kernel (or the other arithmetic)
+int parse_tuning(amx_gmm* h, const amx_ctx* ctx, const char* tuning) {
     amx::Tuning tune;
-    if (!tune.parse(m->tuning, amx::gmm_tuning_keys, "amx_gmm_create"))
+    const char* who = "amx_gmm_create";
+    if (!tune.parse(tuning, amx::gmm_tuning_keys, who))
         return AMX_ERR_INVALID;
-    // values are checked like keys: a typo must not silently select the default kernel (or the other arithmetic)
-    int         t_screen, t_fused, t_screen_all, t_tied_prune, t_chunk, t_fused_waves, t_fr, t_simd_mfma, t_graph, t_dist_list, t_near_fused, t_fused_pack;
-    std::string t_screen_kernel, t_contract;
     static const char* const screen_kernels[] = {"rows", "persist", "simple", nullptr};
     static const char* const contracts[]      = {"off", "fma", nullptr};
-    const char*              who              = "amx_gmm_create";
-    if (!tune.get_int("screen", 1, 0, 1, &t_screen, who) || !tune.get_int("fused", 1, 0, 1, &t_fused, who) ||
-        !tune.get_int("screen_all", 0, 0, 1, &t_screen_all, who) || !tune.get_int("tied_prune", -1, -1, 1, &t_tied_prune, who) ||
-        !tune.get_int("chunk", 65536, 256, 1 << 24, &t_chunk, who) || !tune.get_int("fused_waves", 0, 0, 16, &t_fused_waves, who) ||
-        !tune.get_int("fr", 8, 2, 16, &t_fr, who) || !tune.get_int("simd_mfma", 1, 0, 1, &t_simd_mfma, who) ||
-        !tune.get_int("graph", 0, 0, 1, &t_graph, who) || !tune.get_int("dist_list", 1, 0, 64, &t_dist_list, who) ||
-        !tune.get_int("near_fused", 1, 0, 1, &t_near_fused, who) || !tune.get_int("fused_pack", 1, 0, 1, &t_fused_pack, who) || !tune.get_word("screen_kernel", "rows", screen_kernels, &t_screen_kernel, who) ||
-        !tune.get_word("contract", ctx && ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", contracts, &t_contract, who))   // no key: the context's arithmetic (amx_set_contract)
+    std::string              contract;
+    if (!tune.get_int("screen", 1, 0, 1, &h->tune_screen, who) || !tune.get_int("fused", 1, 0, 1, &h->tune_fused, who) ||
+        !tune.get_int("screen_all", 0, 0, 1, &h->tune_screen_all, who) || !tune.get_int("tied_prune", -1, -1, 1, &h->tune_tied_prune, who) ||
+        !tune.get_int("chunk", 65536, 256, 1 << 24, &h->tune_chunk, who) || !tune.get_int("fused_waves", 0, 0, 16, &h->tune_fused_waves, who) ||
+        !tune.get_int("fr", 8, 2, 16, &h->tune_fr, who) || !tune.get_int("simd_mfma", 1, 0, 1, &h->tune_simd_mfma, who) ||
+        !tune.get_int("graph", 0, 0, 1, &h->graphs.use_graphs, who) || !tune.get_int("dist_list", 1, 0, 64, &h->tune_dist_list, who) ||
+        !tune.get_int("near_fused", 1, 0, 1, &h->tune_near_fused, who) || !tune.get_int("fused_pack", 1, 0, 1, &h->tune_fused_pack, who) ||
+        !tune.get_word("screen_kernel", "rows", screen_kernels, &h->tune_screen_kernel, who) ||
+        !tune.get_word("contract", ctx && ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", contracts, &contract, who))  // no key: the context's arithmetic (amx_set_contract)
         return AMX_ERR_INVALID;
-    AMX_REQUIRE(t_fused_waves == 0 || t_fused_waves == 8 || t_fused_waves == 12 || t_fused_waves == 13 || t_fused_waves == 16, AMX_ERR_INVALID,
-                "amx_gmm_create: tuning fused_waves=%d: expected 8 | 12 | 13 | 16", t_fused_waves);
-    AMX_REQUIRE(t_fr == 2 || t_fr == 4 || t_fr == 8 || t_fr == 16, AMX_ERR_INVALID, "amx_gmm_create: tuning fr=%d: expected 2 | 4 | 8 | 16", t_fr);
+    h->contract_fma = contract == "fma";
+    AMX_REQUIRE(h->tune_fused_waves == 0 || h->tune_fused_waves == 8 || h->tune_fused_waves == 12 || h->tune_fused_waves == 13 || h->tune_fused_waves == 16,
+                AMX_ERR_INVALID, "amx_gmm_create: tuning fused_waves=%d: expected 8 | 12 | 13 | 16", h->tune_fused_waves);
+    AMX_REQUIRE(h->tune_fr == 2 || h->tune_fr == 4 || h->tune_fr == 8 || h->tune_fr == 16, AMX_ERR_INVALID,
+                "amx_gmm_create: tuning fr=%d: expected 2 | 4 | 8 | 16", h->tune_fr);
     // contract=fma exists for the specialised-wave experiment's kernel neither (fused_waves=13): a measured-slower lab form
-    AMX_REQUIRE(!(t_contract == "fma" && t_fused_waves == 13), AMX_ERR_UNSUPPORTED,
+    AMX_REQUIRE(!(h->contract_fma && h->tune_fused_waves == 13), AMX_ERR_UNSUPPORTED,
                 "amx_gmm_create: tuning contract=fma has no fused_waves=13 kernel (the specialised-wave form exists for contract=off only)");
-    amx_gmm* h = new amx_gmm;
-    h->tune_screen        = t_screen;
-    h->tune_fused         = t_fused;
-    h->tune_screen_all    = t_screen_all;
-    h->tune_tied_prune    = t_tied_prune;
-    h->tune_chunk         = t_chunk;
-    h->tune_fused_waves   = t_fused_waves;
-    h->tune_fr            = t_fr;
-    h->tune_simd_mfma     = t_simd_mfma;
-    h->tune_dist_list     = t_dist_list;
-    h->tune_near_fused    = t_near_fused;
-    h->tune_fused_pack    = t_fused_pack;
-    h->tune_screen_kernel = t_screen_kernel;
-    h->use_graphs         = t_graph;
-    h->contract_fma       = t_contract == "fma";
+    return AMX_OK;
+}
+
+// batch-float mode tables (pooled covariance)
+int upload_pooled_tables(amx_gmm* h, const amx_gmm_model* m, const HostTables& t) {
+    const size_t nk = h->nk;
+    int          r;
+    // BatchFloatFeatureScorer::init: unscaled covariance element, c = logNormFactor - 2 * logWeight
+    std::vector<float> isr0(m->dim), smeans((size_t)m->n_mean * m->dim), kc(nk);
+    double             lsum = 0;
+    for (int i = 0; i < m->dim; ++i) {
+        isr0[i] = (float)1 / (float)std::sqrt((double)m->variances[i]);
+        lsum += std::log((double)std::fabs(m->variances[i]));
+    }
+    const float ln = (float)(h->contract_fma ? std::fma((double)m->dim, std::log((double)2 * M_PI), lsum) : (double)m->dim * std::log((double)2 * M_PI) + lsum);
+    for (int j = 0; j < m->n_mean; ++j)
+        for (int i = 0; i < m->dim; ++i)
+            smeans[(size_t)j * m->dim + i] = m->means[(size_t)j * m->dim + i] * isr0[i];
+    for (size_t k = 0; k < nk; ++k)
+        kc[k] = (float)((double)ln - 2 * m->log_weight[k]);
+    h->h_smeans = smeans;  // host copies for the density clustering of preselection-batch-float
+    h->h_k_mean = t.k_mean;
+    if ((r = h->d_isr0.upload(isr0.data(), isr0.size())) != AMX_OK || (r = h->d_smeans.upload(smeans.data(), smeans.size())) != AMX_OK ||
+        (r = h->d_k_const.upload(kc.data(), kc.size())) != AMX_OK)
+        return r;
+    return AMX_OK;
+}
+
+// shared-list tied model: the transposed tables of the combine kernels and of the pruned path (gmm_tied.hip)
+int upload_tied_tables(amx_gmm* h, const amx_gmm_model* m, const HostTables& t) {
+    const auto &k_mean = t.k_mean, &k_cov = t.k_cov, &k_dens = t.k_dens;
+    int r;
+    h->mix_pad = (h->n_mix + 63) & ~63;
+    std::vector<float>  wt((size_t)h->K * h->mix_pad, 0.f);
+    std::vector<double> ln64(h->K);
+    std::vector<float>  ln32(h->K);
+    for (int i = 0; i < h->n_mix; ++i)
+        for (int k = 0; k < h->K; ++k)
+            wt[(size_t)k * h->mix_pad + i] = h->m2lw[(size_t)i * h->K + k];
+    for (int k = 0; k < h->K; ++k) {
+        ln32[k] = h->lognorm[k_cov[k]];
+        ln64[k] = (double)ln32[k];
+    }
+    {  // density -> list position, when that is a function (gmm_dist_kernel then writes the pruned scorer's frame-major image itself)
+        std::vector<uint32_t> pos((size_t)h->n_dens, 0xffffffffu);
+        bool                  once = true;
+        for (int k = 0; k < h->K && once; ++k) {
+            once = k_dens[k] < (uint32_t)h->n_dens && pos[k_dens[k]] == 0xffffffffu;
+            if (once)
+                pos[k_dens[k]] = (uint32_t)k;
+        }
+        if (once && (r = h->d_dens_pos.upload(pos.data(), pos.size())) != AMX_OK)
+            return r;
+        if (once) {  // the list's means and inverse deviations, transposed: lane = list position reads them coalesced
+            const int          Kpad = (h->K + 63) & ~63, dim = m->dim;
+            std::vector<float> mt((size_t)dim * Kpad, 0.f), it((size_t)dim * Kpad, 0.f);
+            for (int k = 0; k < h->K; ++k)
+                for (int i = 0; i < dim; ++i) {
+                    mt[(size_t)i * Kpad + k] = m->means[(size_t)k_mean[k] * dim + i];
+                    it[(size_t)i * Kpad + k] = h->isr[(size_t)k_cov[k] * dim + i];
+                }
+            if ((r = h->d_means_t.upload(mt.data(), mt.size())) != AMX_OK || (r = h->d_isr_t.upload(it.data(), it.size())) != AMX_OK)
+                return r;
+        }
+    }
+    // screen tables (gmm_tied_tile_kernel): an f32 image of the per-entry constant and its largest magnitude per mixture
+    std::vector<float> ahat((size_t)h->K * h->mix_pad, 0.f), amax(h->mix_pad, 0.f);
+    for (int k = 0; k < h->K; ++k)
+        for (int i = 0; i < h->n_mix; ++i) {
+            const float a                    = wt[(size_t)k * h->mix_pad + i] + ln32[k];
+            ahat[(size_t)k * h->mix_pad + i] = a;
+            amax[i]                          = std::max(amax[i], std::fabs(a));
+        }
+    if ((r = h->d_m2lw_t.upload(wt.data(), wt.size())) != AMX_OK || (r = h->d_ln64.upload(ln64.data(), ln64.size())) != AMX_OK ||
+        (r = h->d_ln32.upload(ln32.data(), ln32.size())) != AMX_OK || (r = h->d_ahat_t.upload(ahat.data(), ahat.size())) != AMX_OK ||
+        (r = h->d_amax.upload(amax.data(), amax.size())) != AMX_OK ||
+        (r = amx_internal_gmm_tied_create(h->K, h->n_mix, h->mix_pad, ahat.data(), h->d_amin, h->d_aup)) != AMX_OK)
+        return r;
+    if (h->d_tied_surv.reserve(257) != AMX_OK || hipMemset(h->d_tied_surv.get(), 0, 257 * 8) != hipSuccess || h->h_tied_surv.reserve(257) != AMX_OK) {
+        amx::set_error("amx_gmm_create: out of memory (tied-model statistics)");
+        return AMX_ERR_DEVICE;
+    }
+    memset(h->h_tied_surv.get(), 0, 257 * 8);
+    return AMX_OK;
+}
+
+// MFMA screen tables (gmm_screen_kernel): private densities, <= 16 per mixture, operand fits f16
+int build_screen_tables(amx_gmm* h, const amx_gmm_model* m, const HostTables& t) {
+    const auto &k_mean = t.k_mean, &k_cov = t.k_cov;
+    const auto& c64 = t.c64;
+    int         r;
+    uint32_t kmax = 0;
+    for (int i = 0; i < m->n_mix; ++i)
+        kmax = std::max(kmax, m->mix_offsets[i + 1] - m->mix_offsets[i]);
+    const int d = m->dim, Kd = h->pooled ? d : 2 * d;
+    if (kmax >= 1 && kmax <= 16 && Kd + 2 <= 128) {  // two more K columns carry the per-density constant as c_hi + c_lo
+        const int Kp = Kd + 2 <= 64 ? 64 : 128, Rpad = (m->n_mix * 16 + 255) / 256 * 256, Mp = Rpad / 16;
+        std::vector<_Float16> A((size_t)Rpad * Kp, (_Float16)0.f);
+        std::vector<size_t>   row2(Kp == 64 ? (size_t)Rpad : 0);  // row of the old order -> row of gmm_screen_rows_kernel's order
+        std::vector<float>    c((size_t)Rpad, std::numeric_limits<float>::infinity()), na(Mp, 0.f), cabs(Mp, 0.f), ra(Mp, 0.f);
+        double                na_all = 0;
+        bool                  fits = true;
+        double                rmax2 = 0;
+        for (size_t i = 0; i < h->isr.size(); ++i)
+            rmax2 = std::max(rmax2, (double)h->isr[i] * (double)h->isr[i]);
+        for (int i = 0; i < m->n_mix && fits; ++i)
+            for (uint32_t k = m->mix_offsets[i]; k < m->mix_offsets[i + 1]; ++k) {
+                const uint32_t slot = k - m->mix_offsets[i];  // row inside the mixture's 16: see gmm_screen_epilogue
+                const size_t   row  = (size_t)i * 16 + (((slot >> 2) & 1) * 8 + (slot >> 3) * 4 + (slot & 3));
+                if (Kp == 64)
+                    row2[row] = (size_t)(i >> 4) * 256 + (size_t)((i & 15) >> 1) * 32 + (slot >> 2) * 8 + (i & 1) * 4 + (slot & 3) + 1;
+                const float* mu  = m->means + (size_t)k_mean[k] * d;
+                const float* is  = h->isr.data() + (size_t)k_cov[k] * d;
+                double       cc = c64[k], n2 = 0, res2 = 0, true2 = 0;  // squared norms: rounded row, its f16 residual, the exact row
+                for (int x = 0; x < d; ++x) {
+                    const double mr = (double)mu[x] * (double)is[x];
+                    cc += mr * mr;
+                    double a0, a1 = 0;
+                    if (h->pooled)
+                        a0 = -2.0 * mr;
+                    else {
+                        a0 = -2.0 * mr * (double)is[x];
+                        a1 = (double)is[x] * (double)is[x];
+                    }
+                    if (!(std::fabs(a0) <= 65504.0 && a1 <= 65504.0))
+                        fits = false;
+                    const _Float16 h0 = (_Float16)(float)a0, h1 = (_Float16)(float)a1;
+                    A[row * Kp + x]   = h0;
+                    n2 += (double)(float)h0 * (double)(float)h0;
+                    res2 += (a0 - (double)(float)h0) * (a0 - (double)(float)h0);
+                    true2 += a0 * a0;
+                    if (!h->pooled) {
+                        A[row * Kp + d + x] = h1;
+                        n2 += (double)(float)h1 * (double)(float)h1;
+                        res2 += (a1 - (double)(float)h1) * (a1 - (double)(float)h1);
+                        true2 += a1 * a1;
+                    }
+                }
+                c[row]  = (float)cc;
+                na[i]   = std::max(na[i], (float)(std::sqrt(n2) * 1.0000001));
+                ra[i]   = std::max(ra[i], (float)(std::sqrt(res2) * 1.000001));
+                na_all  = std::max(na_all, std::sqrt(true2) * 1.000001);
+                cabs[i] = std::max(cabs[i], std::fabs((float)cc));
+                if (!std::isfinite(cc) || std::fabs(cc) > 65000.0)
+                    fits = false;
+                const _Float16 chi = (_Float16)(float)cc;
+                A[row * Kp + Kd]     = chi;
+                A[row * Kp + Kd + 1] = (_Float16)(float)(cc - (double)(float)chi);
+            }
+        for (size_t row = 0; row < (size_t)Rpad; ++row)  // empty slots: +inf (never a survivor unless the frame keeps all)
+            if (!std::isfinite(c[row]))
+                A[row * Kp + Kd] = (_Float16)std::numeric_limits<float>::infinity();
+        const float sK = std::sqrt((float)Kd);
+        for (int i = 0; i < Mp; ++i) {  // na -> p1, cabs -> p2 (see gmm_screen_epilogue)
+            const float a = na[i], cb = cabs[i];
+            na[i]   = 2.05f * ra[i] + 1.3e-4f * sK;
+            cabs[i] = 1.3e-4f * sK * a + 1.6e-5f * cb;
+        }
+        if (fits) {
+            h->scr_Kp = Kp;
+            h->scr_Rpad = Rpad;
+            h->scr_Mpad16 = Mp;
+            h->scr_rmax2 = (float)(rmax2 * 1.000001);
+            h->scr_na_all = (float)(2.05 * na_all * 1.000001);
+            if (Kp == 64) {  // the same rows in the second kernel's order; rows that hold no density keep the +inf constant
+                std::vector<_Float16> A2((size_t)Rpad * Kp, (_Float16)0.f);
+                for (size_t row = 0; row < (size_t)Rpad; ++row)
+                    A2[row * Kp + Kd] = (_Float16)std::numeric_limits<float>::infinity();
+                for (size_t row = 0; row < (size_t)Rpad; ++row)
+                    if (row2[row])
+                        memcpy(&A2[(row2[row] - 1) * Kp], &A[row * Kp], (size_t)Kp * sizeof(_Float16));
+                if ((r = h->d_scr_A2.upload(A2.data(), A2.size())) != AMX_OK)
+                    return r;
+                if (amx_internal_gmm_fused_supported(d, h->pooled ? 1 : 0, Kp) &&
+                    (r = amx_internal_gmm_fused_create(d, m->n_mix, Rpad / 256, A2.data(), m->mix_offsets, k_mean.data(), c64.data(), m->means,
+                                                       na.data(), cabs.data(), h->d_fus_rec)) != AMX_OK)
+                    return r;
+                if (h->d_fus_rec.get()) {
+                    const std::vector<unsigned long long> zero(256, 0ull);
+                    if ((r = h->d_fus_surv.upload(zero.data(), zero.size())) != AMX_OK)
+                        return r;
+                }
+            }
+            if ((r = h->d_scr_A.upload(A.data(), A.size())) != AMX_OK || (r = h->d_scr_c.upload(c.data(), c.size())) != AMX_OK ||
+                (r = h->d_scr_na.upload(na.data(), na.size())) != AMX_OK || (r = h->d_scr_cabs.upload(cabs.data(), cabs.size())) != AMX_OK)
+                return r;
+            h->screen = true;
+        }
+    }
+    return AMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
+    // ctx == NULL creates a host-only handle (prepared tables only; scoring returns AMX_ERR_STATE)
+    AMX_REQUIRE(m && out, AMX_ERR_INVALID, "amx_gmm_create: NULL argument");
+    *out = nullptr;
+    AMX_TRY(check_model(m));
+    const size_t nk = m->mix_offsets[m->n_mix];
+    std::unique_ptr<amx_gmm, void (*)(amx_gmm*)> owner(new amx_gmm, amx_gmm_destroy);
+    amx_gmm* const                               h = owner.get();
+    AMX_TRY(parse_tuning(h, ctx, m->tuning));
     h->ctx     = ctx;
     h->dim     = m->dim;
     h->n_mix   = m->n_mix;
@@ -2144,16 +2287,14 @@ int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
         float ln      = (float)(h->contract_fma ? std::fma((double)m->dim, std::log((double)2 * M_PI), lsum) : (double)m->dim * std::log((double)2 * M_PI) + lsum);
         h->lognorm[c] = ln * (gs * gs);
     }
-    std::vector<uint32_t> k_mean(nk), k_cov(nk), k_dens(nk);
-    std::vector<double>   c64(nk);
-    std::vector<float>    c32(nk);
+    HostTables t{std::vector<uint32_t>(nk), std::vector<uint32_t>(nk), std::vector<uint32_t>(nk), std::vector<double>(nk), std::vector<float>(nk)};
     for (size_t k = 0; k < nk; ++k) {
-        uint32_t d = m->dens_index[k];
-        k_dens[k]  = d;
-        k_mean[k]  = m->dens_mean[d];
-        k_cov[k]   = m->dens_cov[d];
-        c64[k]     = (double)h->m2lw[k] + (double)h->lognorm[k_cov[k]];
-        c32[k]     = h->m2lw[k] + h->lognorm[k_cov[k]];
+        uint32_t d  = m->dens_index[k];
+        t.k_dens[k] = d;
+        t.k_mean[k] = m->dens_mean[d];
+        t.k_cov[k]  = m->dens_cov[d];
+        t.c64[k]    = (double)h->m2lw[k] + (double)h->lognorm[t.k_cov[k]];
+        t.c32[k]    = h->m2lw[k] + h->lognorm[t.k_cov[k]];
     }
     // tied model: each density is referenced by several mixtures -> compute distances once
     h->tied = nk >= (size_t)4 * (size_t)m->n_dens;
@@ -2167,216 +2308,28 @@ int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
         h->K       = (int)K;
     }
 
-    int r = AMX_OK;
     if (!ctx) {
-        *out = h;
+        *out = owner.release();
         return AMX_OK;
     }
     hipSetDevice(ctx->device);
-    if ((r = gupload(&h->d_mix_off, h->mix_off.data(), h->mix_off.size())) != AMX_OK ||
-        (r = gupload(&h->d_k_mean, k_mean.data(), nk)) != AMX_OK || (r = gupload(&h->d_k_cov, k_cov.data(), nk)) != AMX_OK ||
-        (r = gupload(&h->d_k_dens, k_dens.data(), nk)) != AMX_OK ||
-        (r = gupload(&h->d_d_mean, m->dens_mean, (size_t)m->n_dens)) != AMX_OK ||
-        (r = gupload(&h->d_d_cov, m->dens_cov, (size_t)m->n_dens)) != AMX_OK ||
-        (r = gupload(&h->d_k_c64, c64.data(), nk)) != AMX_OK || (r = gupload(&h->d_k_c32, c32.data(), nk)) != AMX_OK ||
-        (r = gupload(&h->d_means, m->means, (size_t)m->n_mean * m->dim)) != AMX_OK ||
-        (r = gupload(&h->d_isr, h->isr.data(), h->isr.size())) != AMX_OK) {
-        amx_gmm_destroy(h);
+    int r;
+    if ((r = h->d_mix_off.upload(h->mix_off.data(), h->mix_off.size())) != AMX_OK ||
+        (r = h->d_k_mean.upload(t.k_mean.data(), nk)) != AMX_OK || (r = h->d_k_cov.upload(t.k_cov.data(), nk)) != AMX_OK ||
+        (r = h->d_k_dens.upload(t.k_dens.data(), nk)) != AMX_OK ||
+        (r = h->d_d_mean.upload(m->dens_mean, (size_t)m->n_dens)) != AMX_OK ||
+        (r = h->d_d_cov.upload(m->dens_cov, (size_t)m->n_dens)) != AMX_OK ||
+        (r = h->d_k_c64.upload(t.c64.data(), nk)) != AMX_OK || (r = h->d_k_c32.upload(t.c32.data(), nk)) != AMX_OK ||
+        (r = h->d_means.upload(m->means, (size_t)m->n_mean * m->dim)) != AMX_OK ||
+        (r = h->d_isr.upload(h->isr.data(), h->isr.size())) != AMX_OK)
         return r;
-    }
     h->pooled = (m->n_cov == 1);
-    if (h->pooled) {
-        // BatchFloatFeatureScorer::init: unscaled covariance element, c = logNormFactor - 2 * logWeight
-        std::vector<float> isr0(m->dim), smeans((size_t)m->n_mean * m->dim), kc(nk);
-        double             lsum = 0;
-        for (int i = 0; i < m->dim; ++i) {
-            isr0[i] = (float)1 / (float)std::sqrt((double)m->variances[i]);
-            lsum += std::log((double)std::fabs(m->variances[i]));
-        }
-        const float ln = (float)(h->contract_fma ? std::fma((double)m->dim, std::log((double)2 * M_PI), lsum) : (double)m->dim * std::log((double)2 * M_PI) + lsum);
-        for (int j = 0; j < m->n_mean; ++j)
-            for (int i = 0; i < m->dim; ++i)
-                smeans[(size_t)j * m->dim + i] = m->means[(size_t)j * m->dim + i] * isr0[i];
-        for (size_t k = 0; k < nk; ++k)
-            kc[k] = (float)((double)ln - 2 * m->log_weight[k]);
-        h->h_smeans = smeans;  // host copies for the density clustering of preselection-batch-float
-        h->h_k_mean = k_mean;
-        if ((r = gupload(&h->d_isr0, isr0.data(), isr0.size())) != AMX_OK || (r = gupload(&h->d_smeans, smeans.data(), smeans.size())) != AMX_OK ||
-            (r = gupload(&h->d_k_const, kc.data(), kc.size())) != AMX_OK) {
-            amx_gmm_destroy(h);
-            return r;
-        }
-    }
-    if (h->uniform) {
-        h->mix_pad = (h->n_mix + 63) & ~63;
-        std::vector<float>  wt((size_t)h->K * h->mix_pad, 0.f);
-        std::vector<double> ln64(h->K);
-        std::vector<float>  ln32(h->K);
-        for (int i = 0; i < h->n_mix; ++i)
-            for (int k = 0; k < h->K; ++k)
-                wt[(size_t)k * h->mix_pad + i] = h->m2lw[(size_t)i * h->K + k];
-        for (int k = 0; k < h->K; ++k) {
-            ln32[k] = h->lognorm[k_cov[k]];
-            ln64[k] = (double)ln32[k];
-        }
-        {  // density -> list position, when that is a function (gmm_dist_kernel then writes the pruned scorer's frame-major image itself)
-            std::vector<uint32_t> pos((size_t)h->n_dens, 0xffffffffu);
-            bool                  once = true;
-            for (int k = 0; k < h->K && once; ++k) {
-                once = k_dens[k] < (uint32_t)h->n_dens && pos[k_dens[k]] == 0xffffffffu;
-                if (once)
-                    pos[k_dens[k]] = (uint32_t)k;
-            }
-            if (once && (r = gupload(&h->d_dens_pos, pos.data(), pos.size())) != AMX_OK) {
-                amx_gmm_destroy(h);
-                return r;
-            }
-            if (once) {  // the list's means and inverse deviations, transposed: lane = list position reads them coalesced
-                const int          Kpad = (h->K + 63) & ~63, dim = m->dim;
-                std::vector<float> mt((size_t)dim * Kpad, 0.f), it((size_t)dim * Kpad, 0.f);
-                for (int k = 0; k < h->K; ++k)
-                    for (int i = 0; i < dim; ++i) {
-                        mt[(size_t)i * Kpad + k] = m->means[(size_t)k_mean[k] * dim + i];
-                        it[(size_t)i * Kpad + k] = h->isr[(size_t)k_cov[k] * dim + i];
-                    }
-                if ((r = gupload(&h->d_means_t, mt.data(), mt.size())) != AMX_OK || (r = gupload(&h->d_isr_t, it.data(), it.size())) != AMX_OK) {
-                    amx_gmm_destroy(h);
-                    return r;
-                }
-            }
-        }
-        // screen tables (gmm_tied_tile_kernel): an f32 image of the per-entry constant and its largest magnitude per mixture
-        std::vector<float> ahat((size_t)h->K * h->mix_pad, 0.f), amax(h->mix_pad, 0.f);
-        for (int k = 0; k < h->K; ++k)
-            for (int i = 0; i < h->n_mix; ++i) {
-                const float a                    = wt[(size_t)k * h->mix_pad + i] + ln32[k];
-                ahat[(size_t)k * h->mix_pad + i] = a;
-                amax[i]                          = std::max(amax[i], std::fabs(a));
-            }
-        if ((r = gupload(&h->d_m2lw_t, wt.data(), wt.size())) != AMX_OK || (r = gupload(&h->d_ln64, ln64.data(), ln64.size())) != AMX_OK ||
-            (r = gupload(&h->d_ln32, ln32.data(), ln32.size())) != AMX_OK || (r = gupload(&h->d_ahat_t, ahat.data(), ahat.size())) != AMX_OK ||
-            (r = gupload(&h->d_amax, amax.data(), amax.size())) != AMX_OK ||
-            (r = amx_internal_gmm_tied_create(h->K, h->n_mix, h->mix_pad, ahat.data(), &h->d_amin, &h->d_aup)) != AMX_OK) {
-            amx_gmm_destroy(h);
-            return r;
-        }
-        if (hipMalloc((void**)&h->d_tied_surv, 257 * 8) != hipSuccess || hipMemset(h->d_tied_surv, 0, 257 * 8) != hipSuccess ||
-            hipHostMalloc((void**)&h->h_tied_surv, 257 * 8) != hipSuccess) {
-            amx::set_error("amx_gmm_create: out of memory (tied-model statistics)");
-            amx_gmm_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
-        memset(h->h_tied_surv, 0, 257 * 8);
-    }
-    // ---- MFMA screen tables (gmm_screen_kernel): private densities, <= 16 per mixture, operand fits f16
-    if (!h->tied && screen_dim_supported(m->dim) && h->tune_screen) {
-        uint32_t kmax = 0;
-        for (int i = 0; i < m->n_mix; ++i)
-            kmax = std::max(kmax, m->mix_offsets[i + 1] - m->mix_offsets[i]);
-        const int d = m->dim, Kd = h->pooled ? d : 2 * d;
-        if (kmax >= 1 && kmax <= 16 && Kd + 2 <= 128) {  // two more K columns carry the per-density constant as c_hi + c_lo
-            const int Kp = Kd + 2 <= 64 ? 64 : 128, Rpad = (m->n_mix * 16 + 255) / 256 * 256, Mp = Rpad / 16;
-            std::vector<_Float16> A((size_t)Rpad * Kp, (_Float16)0.f);
-            std::vector<size_t>   row2(Kp == 64 ? (size_t)Rpad : 0);  // row of the old order -> row of gmm_screen_rows_kernel's order
-            std::vector<float>    c((size_t)Rpad, std::numeric_limits<float>::infinity()), na(Mp, 0.f), cabs(Mp, 0.f), ra(Mp, 0.f);
-            double                na_all = 0;
-            bool                  fits = true;
-            double                rmax2 = 0;
-            for (size_t i = 0; i < h->isr.size(); ++i)
-                rmax2 = std::max(rmax2, (double)h->isr[i] * (double)h->isr[i]);
-            for (int i = 0; i < m->n_mix && fits; ++i)
-                for (uint32_t k = m->mix_offsets[i]; k < m->mix_offsets[i + 1]; ++k) {
-                    const uint32_t slot = k - m->mix_offsets[i];  // row inside the mixture's 16: see gmm_screen_epilogue
-                    const size_t   row  = (size_t)i * 16 + (((slot >> 2) & 1) * 8 + (slot >> 3) * 4 + (slot & 3));
-                    if (Kp == 64)
-                        row2[row] = (size_t)(i >> 4) * 256 + (size_t)((i & 15) >> 1) * 32 + (slot >> 2) * 8 + (i & 1) * 4 + (slot & 3) + 1;
-                    const float* mu  = m->means + (size_t)k_mean[k] * d;
-                    const float* is  = h->isr.data() + (size_t)k_cov[k] * d;
-                    double       cc = c64[k], n2 = 0, res2 = 0, true2 = 0;  // squared norms: rounded row, its f16 residual, the exact row
-                    for (int x = 0; x < d; ++x) {
-                        const double mr = (double)mu[x] * (double)is[x];
-                        cc += mr * mr;
-                        double a0, a1 = 0;
-                        if (h->pooled)
-                            a0 = -2.0 * mr;
-                        else {
-                            a0 = -2.0 * mr * (double)is[x];
-                            a1 = (double)is[x] * (double)is[x];
-                        }
-                        if (!(std::fabs(a0) <= 65504.0 && a1 <= 65504.0))
-                            fits = false;
-                        const _Float16 h0 = (_Float16)(float)a0, h1 = (_Float16)(float)a1;
-                        A[row * Kp + x]   = h0;
-                        n2 += (double)(float)h0 * (double)(float)h0;
-                        res2 += (a0 - (double)(float)h0) * (a0 - (double)(float)h0);
-                        true2 += a0 * a0;
-                        if (!h->pooled) {
-                            A[row * Kp + d + x] = h1;
-                            n2 += (double)(float)h1 * (double)(float)h1;
-                            res2 += (a1 - (double)(float)h1) * (a1 - (double)(float)h1);
-                            true2 += a1 * a1;
-                        }
-                    }
-                    c[row]  = (float)cc;
-                    na[i]   = std::max(na[i], (float)(std::sqrt(n2) * 1.0000001));
-                    ra[i]   = std::max(ra[i], (float)(std::sqrt(res2) * 1.000001));
-                    na_all  = std::max(na_all, std::sqrt(true2) * 1.000001);
-                    cabs[i] = std::max(cabs[i], std::fabs((float)cc));
-                    if (!std::isfinite(cc) || std::fabs(cc) > 65000.0)
-                        fits = false;
-                    const _Float16 chi = (_Float16)(float)cc;
-                    A[row * Kp + Kd]     = chi;
-                    A[row * Kp + Kd + 1] = (_Float16)(float)(cc - (double)(float)chi);
-                }
-            for (size_t row = 0; row < (size_t)Rpad; ++row)  // empty slots: +inf (never a survivor unless the frame keeps all)
-                if (!std::isfinite(c[row]))
-                    A[row * Kp + Kd] = (_Float16)std::numeric_limits<float>::infinity();
-            const float sK = std::sqrt((float)Kd);
-            for (int i = 0; i < Mp; ++i) {  // na -> p1, cabs -> p2 (see gmm_screen_epilogue)
-                const float a = na[i], cb = cabs[i];
-                na[i]   = 2.05f * ra[i] + 1.3e-4f * sK;
-                cabs[i] = 1.3e-4f * sK * a + 1.6e-5f * cb;
-            }
-            if (fits) {
-                h->scr_Kp = Kp;
-                h->scr_Rpad = Rpad;
-                h->scr_Mpad16 = Mp;
-                h->scr_rmax2 = (float)(rmax2 * 1.000001);
-                h->scr_na_all = (float)(2.05 * na_all * 1.000001);
-                if (Kp == 64) {  // the same rows in the second kernel's order; rows that hold no density keep the +inf constant
-                    std::vector<_Float16> A2((size_t)Rpad * Kp, (_Float16)0.f);
-                    for (size_t row = 0; row < (size_t)Rpad; ++row)
-                        A2[row * Kp + Kd] = (_Float16)std::numeric_limits<float>::infinity();
-                    for (size_t row = 0; row < (size_t)Rpad; ++row)
-                        if (row2[row])
-                            memcpy(&A2[(row2[row] - 1) * Kp], &A[row * Kp], (size_t)Kp * sizeof(_Float16));
-                    if ((r = gupload(&h->d_scr_A2, A2.data(), A2.size())) != AMX_OK) {
-                        amx_gmm_destroy(h);
-                        return r;
-                    }
-                    if (amx_internal_gmm_fused_supported(d, h->pooled ? 1 : 0, Kp) &&
-                        (r = amx_internal_gmm_fused_create(d, m->n_mix, Rpad / 256, A2.data(), m->mix_offsets, k_mean.data(), c64.data(), m->means,
-                                                           na.data(), cabs.data(), &h->d_fus_rec, &h->fus_rec_bytes)) != AMX_OK) {
-                        amx_gmm_destroy(h);
-                        return r;
-                    }
-                    if (h->d_fus_rec) {
-                        const std::vector<unsigned long long> zero(256, 0ull);
-                        if ((r = gupload(&h->d_fus_surv, zero.data(), zero.size())) != AMX_OK) {
-                            amx_gmm_destroy(h);
-                            return r;
-                        }
-                    }
-                }
-                if ((r = gupload(&h->d_scr_A, A.data(), A.size())) != AMX_OK || (r = gupload(&h->d_scr_c, c.data(), c.size())) != AMX_OK ||
-                    (r = gupload(&h->d_scr_na, na.data(), na.size())) != AMX_OK || (r = gupload(&h->d_scr_cabs, cabs.data(), cabs.size())) != AMX_OK) {
-                    amx_gmm_destroy(h);
-                    return r;
-                }
-                h->screen = true;
-            }
-        }
-    }
+    if (h->pooled)
+        AMX_TRY(upload_pooled_tables(h, m, t));
+    if (h->uniform)
+        AMX_TRY(upload_tied_tables(h, m, t));
+    if (!h->tied && screen_dim_supported(h->dim) && h->tune_screen)
+        AMX_TRY(build_screen_tables(h, m, t));
     // ---- SIMD-diagonal-maximum / batch-int tables (quantised means, integer constants; gmm_simd.hip) are built on the first
     // call of those scorers (ensure_simd): most handles never use them, and a model they cannot represent must not keep the
     // float scorers from being created.  Host copies of the model for that build:
@@ -2385,69 +2338,19 @@ int amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* m, amx_gmm** out) {
     h->h_logw.assign(m->log_weight, m->log_weight + nk);
     h->mws = m->mixture_weight_scale;
     h->gsc = m->gaussian_scale;
-    *out = h;
+    *out = owner.release();
     return AMX_OK;
 }
 
 void amx_gmm_destroy(amx_gmm* h) {
     if (!h)
         return;
-    if (!h->ctx) {
-        delete h;
-        return;
+    if (h->ctx) {  // (a host-only handle owns nothing on a device: no HIP call is made for it)
+        hipSetDevice(h->ctx->device);
+        h->graphs.clear();
+        amx_internal_gmm_simd_destroy(h->simd);
+        amx_internal_gmm_presel_destroy(h->presel);
     }
-    hipSetDevice(h->ctx->device);
-    for (auto& kv : h->graphs)
-        if (kv.second)
-            hipGraphExecDestroy(kv.second);
-    amx_internal_gmm_simd_destroy(h->simd);
-    amx_internal_gmm_presel_destroy(h->presel);
-    hipFree(h->d_mix_off);
-    hipFree(h->d_k_mean);
-    hipFree(h->d_k_cov);
-    hipFree(h->d_k_dens);
-    hipFree(h->d_dens_pos);
-    hipFree(h->d_means_t);
-    hipFree(h->d_isr_t);
-    hipFree(h->d_d_mean);
-    hipFree(h->d_d_cov);
-    hipFree(h->d_k_c64);
-    hipFree(h->d_k_c32);
-    hipFree(h->d_means);
-    hipFree(h->d_isr);
-    hipFree(h->d_smeans);
-    hipFree(h->d_k_const);
-    hipFree(h->d_isr0);
-    hipFree(h->d_dist);
-    hipFree(h->d_dist64);
-    hipFree(h->d_scr_A);
-    hipFree(h->d_scr_A2);
-    hipFree(h->d_fus_rec);
-    hipFree(h->d_fus_surv);
-    hipFree(h->d_best32);
-    hipFree(h->d_scr_c);
-    hipFree(h->d_scr_na);
-    hipFree(h->d_scr_cabs);
-    hipFree(h->d_scr_X);
-    hipFree(h->d_scr_nx);
-    hipFree(h->d_scr_q);
-    hipFree(h->d_scr_masks);
-    hipFree(h->d_scr_pmin);
-    hipFree(h->d_scr_pidx);
-    hipFree(h->d_host_f);
-    hipFree(h->d_host_s);
-    hipFree(h->d_host_b);
-    hipFree(h->d_m2lw_t);
-    hipFree(h->d_ahat_t);
-    hipFree(h->d_amax);
-    hipFree(h->d_amin);
-    hipFree(h->d_aup);
-    hipFree(h->d_tied_ws);
-    hipFree(h->d_tied_surv);
-    if (h->h_tied_surv)
-        hipHostFree(h->h_tied_surv);
-    hipFree(h->d_ln64);
-    hipFree(h->d_ln32);
     delete h;
 }
 
@@ -2498,6 +2401,14 @@ static int ensure_simd(amx_gmm* h) {
     h->simd_status = r == AMX_OK ? 1 : r;
     return r;
 }
+// the density clustering of preselection-batch-float, built on first use and after amx_gmm_set_preselection
+static int ensure_presel(amx_gmm* h) {
+    if (h->presel)
+        return AMX_OK;
+    return amx_internal_gmm_presel_create(h->ctx, h->dim, h->nk, h->h_k_mean.data(), h->h_smeans.data(), h->d_smeans.get(), h->d_k_mean.get(),
+                                          h->presel_clusters, h->presel_select, h->presel_iterations, h->presel_backoff, h->contract_fma ? 1 : 0,
+                                          &h->presel);
+}
 }  // extern "C++"
 
 // dense or pruned for this call of a shared-list tied model: amx_gmm_model.tuning tied_prune=0 forces the dense kernel, =1 the pruned path,
@@ -2508,7 +2419,7 @@ static int ensure_simd(amx_gmm* h) {
 static int tied_publish(amx_gmm* h) {
     if ((++h->tied_copy_tick & 7u) != 0)
         return AMX_OK;
-    AMX_HIP(hipMemcpyAsync(h->h_tied_surv, h->d_tied_surv, 257 * 8, hipMemcpyDeviceToHost, h->ctx->stream));
+    AMX_HIP(hipMemcpyAsync(h->h_tied_surv.get(), h->d_tied_surv.get(), 257 * 8, hipMemcpyDeviceToHost, h->ctx->stream));
     return AMX_OK;
 }
 
@@ -2520,8 +2431,8 @@ static bool tied_decide_prune(amx_gmm* h) {
     // the host runs ahead
     unsigned long long seen = 0;
     for (int i = 0; i < 256; ++i)
-        seen += ((volatile unsigned long long*)h->h_tied_surv)[i];
-    const unsigned long long examined = ((volatile unsigned long long*)h->h_tied_surv)[256];
+        seen += ((volatile unsigned long long*)h->h_tied_surv.get())[i];
+    const unsigned long long examined = ((volatile unsigned long long*)h->h_tied_surv.get())[256];
     if (h->tied_dense_calls > 0) {
         --h->tied_dense_calls;
         return false;
@@ -2538,238 +2449,112 @@ static bool tied_decide_prune(amx_gmm* h) {
     return true;
 }
 
-int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
-    AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_gmm_score_dev: NULL handle");
-    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_gmm_score_dev: host-only handle (created without a context)");
-    AMX_REQUIRE(mode == AMX_GMM_MAX || mode == AMX_GMM_SUM || mode == AMX_GMM_BATCH_FLOAT || mode == AMX_GMM_SIMD || mode == AMX_GMM_BATCH_INT ||
-                        mode == AMX_GMM_PRESELECTION_FLOAT || mode == AMX_GMM_PRESELECTION_INT,
-                AMX_ERR_INVALID,
-                "amx_gmm_score_dev: unknown mode %d", mode);
-    AMX_REQUIRE(T >= 0, AMX_ERR_INVALID, "amx_gmm_score_dev: negative frame count");
-    if (T == 0)
-        return AMX_OK;
-    AMX_REQUIRE(feats_dev && scores_dev, AMX_ERR_INVALID, "amx_gmm_score_dev: NULL buffer");
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    const int fblocks = amx::ceil_div(T, 256);
-    // contract=fma covers every mode (round 6): the float scorers fuse the distance's accumulate, the preselection scorer also its
-    // clustering distances (Mm::unrolledVectorDistance: one vfmadd231ss per term in the default build); the quantised scorers' arithmetic
-    // is integer -- their one f64 site, gaussLogNormFactor's N * log(2 pi) + logNorm, follows the contract on the host (gmm_simd.hip)
-    if (mode == AMX_GMM_SIMD || mode == AMX_GMM_BATCH_INT || mode == AMX_GMM_PRESELECTION_INT) {
-        const int r = ensure_simd(h);
-        if (r != AMX_OK)
-            return r;
-    }
+// the quantised scorers (gmm_simd.hip): SIMD-diagonal-maximum, batch-diagonal-maximum-int, preselection-batch-int
+static int score_quantised(amx_gmm* h, int mode, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    AMX_TRY(ensure_simd(h));
     if (mode == AMX_GMM_PRESELECTION_INT) {
         AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: preselection-batch-int does not assign densities");
-        const int r = amx_internal_gmm_simd_presel_build(h->simd, h->ctx, h->presel_clusters, h->presel_select, h->presel_iterations);
-        if (r != AMX_OK)
-            return r;
+        AMX_TRY(amx_internal_gmm_simd_presel_build(h->simd, h->ctx, h->presel_clusters, h->presel_select, h->presel_iterations));
         return amx_internal_gmm_simd_presel_score(h->simd, h->ctx, feats_dev, T, scores_dev);
     }
     if (mode == AMX_GMM_SIMD)
         return amx_internal_gmm_simd_score(h->simd, h->ctx, 0, feats_dev, T, scores_dev, best_dev);
-    if (mode == AMX_GMM_BATCH_INT) {
-        AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: batch-diagonal-maximum-int does not assign densities");
-        return amx_internal_gmm_simd_score(h->simd, h->ctx, 1, feats_dev, T, scores_dev, nullptr);
-    }
-    if (mode == AMX_GMM_PRESELECTION_FLOAT) {
-        AMX_REQUIRE(h->pooled, AMX_ERR_INVALID, "amx_gmm_score_dev: feature scorer supports only globally pooled covariance");
-        AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: preselection-batch-float does not assign densities");
-        if (!h->presel) {
-            const int r = amx_internal_gmm_presel_create(h->ctx, h->dim, h->nk, h->h_k_mean.data(), h->h_smeans.data(), h->d_smeans, h->d_k_mean,
-                                                         h->presel_clusters, h->presel_select, h->presel_iterations, h->presel_backoff, h->contract_fma ? 1 : 0, &h->presel);
-            if (r != AMX_OK)
-                return r;
-        }
-        return amx_internal_gmm_presel_score(h->presel, h->ctx, feats_dev, T, scores_dev, h->d_mix_off, h->d_k_mean, h->d_k_const, h->d_smeans,
-                                             h->d_isr0, h->n_mix);
-    }
-    if (mode == AMX_GMM_BATCH_FLOAT) {
-        // Mm::BatchFloatFeatureScorer::init: criticalError("feature scorer supports only globally pooled covariance")
-        AMX_REQUIRE(h->pooled, AMX_ERR_INVALID, "amx_gmm_score_dev: feature scorer supports only globally pooled covariance");
-        AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: batch-diagonal-maximum-float does not assign densities");
-        int mt = 16;
-        while (mt > 4 && (long)amx::ceil_div(h->n_mix, mt) * fblocks < 2048)
-            mt /= 2;
-        amx::GmmDims           dims{T, h->dim, h->n_mix, mt};
-        dim3                   grid(amx::ceil_div(h->n_mix, mt), fblocks);
-        amx::ScopedKernelTimer timer(h->ctx, "gmm");
-        switch (h->dim) {
-#define AMX_GMM_CASE(D)                                                                                                   \
-    case D:                                                                                                               \
-        hipLaunchKernelGGL((h->contract_fma ? amx::gmm_batch_float_kernel<D, true> : amx::gmm_batch_float_kernel<D, false>), grid, dim3(256), 0, h->ctx->stream, feats_dev, scores_dev,    \
-                           h->d_mix_off, h->d_k_mean, h->d_k_const, h->d_smeans, h->d_isr0, dims);                         \
-        break;
-            AMX_GMM_CASE(16)
-            AMX_GMM_CASE(24)
-            AMX_GMM_CASE(32)
-            AMX_GMM_CASE(33)
-            AMX_GMM_CASE(39)
-            AMX_GMM_CASE(40)
-            AMX_GMM_CASE(45)
-            AMX_GMM_CASE(48)
-            AMX_GMM_CASE(64)
-#undef AMX_GMM_CASE
-            default:  // any other dimension: the same arithmetic with the feature row re-read from memory
-                hipLaunchKernelGGL((h->contract_fma ? amx::gmm_batch_float_kernel<0, true> : amx::gmm_batch_float_kernel<0, false>), grid, dim3(256), 0, h->ctx->stream, feats_dev, scores_dev, h->d_mix_off,
-                                   h->d_k_mean, h->d_k_const, h->d_smeans, h->d_isr0, dims);
-                break;
-        }
-        AMX_HIP(hipGetLastError());
-        return AMX_OK;
-    }
-    if (!h->tied && h->screen && mode == AMX_GMM_MAX) {
-        // three launches and their gaps are a fifth of a 256-frame pass: replay them as a graph (not while profiling: the
-        // per-launch events are not part of the graph).  First call plain (sizes the workspaces), second call captures.
-        // (a pass that IS one launch -- the fused kernel packing its own operand rows, one chunk -- is cheaper launched than replayed:
-        // 0.0316 against 0.0369 ms per 256 frames, round 6)
-        const bool one_launch = h->d_fus_rec && h->tune_fused && !h->tune_screen_all && h->tune_fused_pack && h->tune_fused_waves != 13 &&
-                                T <= h->tune_chunk;
-        if (!(h->use_graphs && !h->ctx->profiling && T <= 4096) || one_launch)
-            return score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr);
-        const amx_gmm::GraphKey key{feats_dev, scores_dev, best_dev, h->ctx->stream, T};
-        auto                    it = h->graphs.find(key);
-        if (it == h->graphs.end()) {
-            if (h->graphs.size() >= 64) {  // a caller that never repeats a signature: stop caching instead of growing the map
-                for (auto& kv : h->graphs)
-                    if (kv.second)
-                        hipGraphExecDestroy(kv.second);
-                h->graphs.clear();
-                h->use_graphs = 0;
-            }
-            else
-                h->graphs[key] = nullptr;
-            return score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr);
-        }
-        if (it->second == nullptr) {
-            hipGraph_t g = nullptr;
-            if (h->graphs.size() > 64 || hipStreamBeginCapture(h->ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                (void)hipGetLastError();
-                h->use_graphs = 0;  // a caller that keeps changing buffers, or a stream that cannot capture
-                return score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr);
-            }
-            const int      r  = score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr);
-            const bool     ok = hipStreamEndCapture(h->ctx->stream, &g) == hipSuccess && r == AMX_OK && g != nullptr;
-            hipGraphExec_t ex = nullptr;
-            if (!ok || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                if (g)
-                    hipGraphDestroy(g);
-                h->use_graphs = 0;
-                return score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr);
-            }
-            hipGraphDestroy(g);
-            it->second = ex;
-        }
-        else if (h->count_survivors && h->d_fus_rec)  // a replay runs the counting kernel without passing score_screened's bookkeeping
-            h->fus_pairs += (unsigned long long)T * (unsigned long long)h->n_mix;
-        AMX_HIP(hipGraphLaunch(it->second, h->ctx->stream));
-        return AMX_OK;
-    }
-    if (!h->tied) {
-        amx::GmmParams p;
-        p.feats   = feats_dev;
-        p.scores  = scores_dev;
-        p.best    = best_dev;
-        p.mix_off = h->d_mix_off;
-        p.k_mean  = h->d_k_mean;
-        p.k_cov   = h->d_k_cov;
-        p.k_c64   = h->d_k_c64;
-        p.k_c32   = h->d_k_c32;
-        p.means   = h->d_means;
-        p.isr     = h->d_isr;
-        p.T       = T;
-        p.dim     = h->dim;
-        p.n_mix   = h->n_mix;
-        // enough workgroups to fill 256 CUs several times over, but >= 64 B of scores per row
-        int mt = 16;
-        while (mt > 4 && (long)amx::ceil_div(h->n_mix, mt) * fblocks < 2048)
-            mt /= 2;
-        p.mix_tile = mt;
-        dim3                   grid(amx::ceil_div(h->n_mix, mt), fblocks);
-        amx::ScopedKernelTimer timer(h->ctx, "gmm");
-        return mode == AMX_GMM_MAX ? launch_direct<amx::MaxState>(h, p, grid) : launch_direct<amx::SumState>(h, p, grid);
-    }
-    // ---- tied: chunk frames so the distance scratch stays <= 256 MB
-    const int chunk_max = (int)std::max<size_t>(256, std::min<size_t>(16384, ((size_t)64 << 20) / (size_t)h->n_dens / 256 * 256));
-    // The pruned path of a shared-list model is six launches (and, every 8th call, a 2 KB copy): at the decoder's batch sizes their gaps are a seventh
-    // of the pass, so repeated passes on unchanged buffers are replayed as one HIP graph like the screened CART path above (the
-    // dense / pruned decision stays outside: a graph is only recorded and replayed for the pruned path).
-    if (h->uniform && mode == AMX_GMM_MAX && h->tied_forced < 0 && T <= chunk_max && T <= 4096 && h->tune_screen) {
-        const bool prune = tied_decide_prune(h);
-        auto       nested = [&](int forced) {
-            h->tied_forced = forced;
-            const int r    = amx_gmm_score_dev(h, mode, feats_dev, T, scores_dev, best_dev);
-            h->tied_forced = -1;
-            return r;
-        };
-        if (!prune || !h->use_graphs || h->ctx->profiling)
-            return nested(prune ? 1 : 0);
-        const amx_gmm::GraphKey key{feats_dev, scores_dev, best_dev, h->ctx->stream, T};
-        auto                    it = h->graphs.find(key);
-        if (it == h->graphs.end()) {  // first pass with this signature: plain launches (they size the workspaces)
-            if (h->graphs.size() >= 64) {
-                for (auto& kv : h->graphs)
-                    if (kv.second)
-                        hipGraphExecDestroy(kv.second);
-                h->graphs.clear();
-                h->use_graphs = 0;
-            }
-            else
-                h->graphs[key] = nullptr;
-            return nested(1);
-        }
-        if (it->second == nullptr) {
-            hipGraph_t gr = nullptr;
-            if (hipStreamBeginCapture(h->ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                (void)hipGetLastError();
-                h->use_graphs = 0;
-                return nested(1);
-            }
-            h->tied_capturing = true;
-            const int r       = nested(1);
-            h->tied_capturing = false;
-            const bool     ok = hipStreamEndCapture(h->ctx->stream, &gr) == hipSuccess && r == AMX_OK && gr != nullptr;
-            hipGraphExec_t ex = nullptr;
-            if (!ok || hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                if (gr)
-                    hipGraphDestroy(gr);
-                h->use_graphs = 0;
-                return nested(1);
-            }
-            hipGraphDestroy(gr);
-            h->graphs[key] = ex;  // (by key: a nested call that had to grow a scratch buffer empties the map)
-            it             = h->graphs.find(key);
-        }
-        else {  // replay: the statistics the nested call would have kept
-            h->tied_rep_triples += (unsigned long long)h->K * (unsigned long long)T * (unsigned long long)(h->mix_pad / 64);
-        }
-        AMX_HIP(hipGraphLaunch(it->second, h->ctx->stream));
-        return tied_publish(h);
-    }
+    AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: batch-diagonal-maximum-int does not assign densities");
+    return amx_internal_gmm_simd_score(h->simd, h->ctx, 1, feats_dev, T, scores_dev, nullptr);
+}
+
+static int score_presel_float(amx_gmm* h, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    AMX_REQUIRE(h->pooled, AMX_ERR_INVALID, "amx_gmm_score_dev: feature scorer supports only globally pooled covariance");
+    AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: preselection-batch-float does not assign densities");
+    AMX_TRY(ensure_presel(h));
+    return amx_internal_gmm_presel_score(h->presel, h->ctx, feats_dev, T, scores_dev, h->d_mix_off.get(), h->d_k_mean.get(), h->d_k_const.get(),
+                                         h->d_smeans.get(), h->d_isr0.get(), h->n_mix);
+}
+
+// mixtures per workgroup: enough workgroups to fill 256 CUs several times over, but >= 64 B of scores per row
+static int mix_tile(const amx_gmm* h, int fblocks) {
+    int mt = 16;
+    while (mt > 4 && (long)amx::ceil_div(h->n_mix, mt) * fblocks < 2048)
+        mt /= 2;
+    return mt;
+}
+
+static int score_batch_float(amx_gmm* h, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    // Mm::BatchFloatFeatureScorer::init: criticalError("feature scorer supports only globally pooled covariance")
+    AMX_REQUIRE(h->pooled, AMX_ERR_INVALID, "amx_gmm_score_dev: feature scorer supports only globally pooled covariance");
+    AMX_REQUIRE(best_dev == nullptr, AMX_ERR_UNSUPPORTED, "amx_gmm_score_dev: batch-diagonal-maximum-float does not assign densities");
+    const int              fblocks = amx::ceil_div(T, 256), mt = mix_tile(h, fblocks);
+    amx::GmmDims           dims{T, h->dim, h->n_mix, mt};
+    dim3                   grid(amx::ceil_div(h->n_mix, mt), fblocks);
+    amx::ScopedKernelTimer timer(h->ctx, "gmm");
+    with_dim(h->dim, [&](auto dc) {  // (D = 0: the same arithmetic with the feature row re-read from memory)
+        with_flag(h->contract_fma, [&](auto fc) {
+            hipLaunchKernelGGL((amx::gmm_batch_float_kernel<decltype(dc)::value, decltype(fc)::value>), grid, dim3(256), 0, h->ctx->stream, feats_dev,
+                               scores_dev, h->d_mix_off.get(), h->d_k_mean.get(), h->d_k_const.get(), h->d_smeans.get(), h->d_isr0.get(), dims);
+        });
+    });
+    AMX_HIP(hipGetLastError());
+    return AMX_OK;
+}
+
+// maximum approximation of a private-density model through the MFMA screen.  With tuning graph=1, the launches of a small pass and
+// their gaps (a fifth of a 256-frame pass) are replayed as a graph (not while profiling: the per-launch events are not part of it).
+static int score_cart_screened(amx_gmm* h, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    auto pass = [&](bool) { return score_screened(h, feats_dev, T, scores_dev, best_dev, false, nullptr, nullptr, nullptr); };
+    // (a pass that IS one launch -- the fused kernel packing its own operand rows, one chunk -- is cheaper launched than replayed:
+    // 0.0316 against 0.0369 ms per 256 frames, round 6)
+    const bool one_launch = h->d_fus_rec.get() && h->tune_fused && !h->tune_screen_all && h->tune_fused_pack && h->tune_fused_waves != 13 &&
+                            T <= h->tune_chunk;
+    if (!(h->graphs.use_graphs && !h->ctx->profiling && T <= 4096) || one_launch)
+        return pass(false);
+    GraphCache::Ran ran;
+    AMX_TRY(h->graphs.run(GraphKey{feats_dev, scores_dev, best_dev, h->ctx->stream, T}, h->ctx->stream, pass, &ran));
+    if (ran == GraphCache::kReplayed && h->count_survivors && h->d_fus_rec.get())  // a replay runs the counting kernel without passing score_screened's bookkeeping
+        h->fus_pairs += (unsigned long long)T * (unsigned long long)h->n_mix;
+    return AMX_OK;
+}
+
+static int score_direct(amx_gmm* h, int mode, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    const int fblocks = amx::ceil_div(T, 256);
+    amx::GmmParams p;
+    p.feats   = feats_dev;
+    p.scores  = scores_dev;
+    p.best    = best_dev;
+    p.mix_off = h->d_mix_off.get();
+    p.k_mean  = h->d_k_mean.get();
+    p.k_cov   = h->d_k_cov.get();
+    p.k_c64   = h->d_k_c64.get();
+    p.k_c32   = h->d_k_c32.get();
+    p.means   = h->d_means.get();
+    p.isr     = h->d_isr.get();
+    p.T       = T;
+    p.dim     = h->dim;
+    p.n_mix   = h->n_mix;
+    const int mt = mix_tile(h, fblocks);
+    p.mix_tile   = mt;
+    dim3                   grid(amx::ceil_div(h->n_mix, mt), fblocks);
+    amx::ScopedKernelTimer timer(h->ctx, "gmm");
+    return mode == AMX_GMM_MAX ? launch_direct<amx::MaxState>(h, p, grid) : launch_direct<amx::SumState>(h, p, grid);
+}
+
+// tied model: distances once per density, then the combine; frames in chunks so that the distance scratch stays <= 256 MB.
+// forced: 1 = pruned path, 0 = dense kernel, -1 = decide per chunk (tied_decide_prune)
+static int score_tied(amx_gmm* h, int mode, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev, int chunk_max, int forced) {
     for (int t0 = 0; t0 < T; t0 += chunk_max) {
         const int Tc   = std::min(chunk_max, T - t0);
         const int Tpad = (Tc + 63) & ~63;
         size_t    need = (size_t)h->n_dens * Tpad;
-        if (need > h->dist_floats) {
-            for (auto& kv : h->graphs)  // recorded passes hold the old scratch addresses
-                if (kv.second)
-                    hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            hipFree(h->d_dist);
-            h->d_dist      = nullptr;
-            h->dist_floats = 0;
-            AMX_HIP(hipMalloc((void**)&h->d_dist, need * sizeof(float)));
-            h->dist_floats = need;
+        if (need > h->d_dist.capacity()) {
+            h->graphs.clear();  // recorded passes hold the old scratch addresses
+            AMX_TRY(h->d_dist.reserve(need));
         }
         amx::GmmDistParams dp;
         dp.feats     = feats_dev + (size_t)t0 * h->dim;
-        dp.dist      = h->d_dist;
-        dp.d_mean    = h->d_d_mean;
-        dp.d_cov     = h->d_d_cov;
-        dp.means     = h->d_means;
-        dp.isr       = h->d_isr;
+        dp.dist      = h->d_dist.get();
+        dp.d_mean    = h->d_d_mean.get();
+        dp.d_cov     = h->d_d_cov.get();
+        dp.means     = h->d_means.get();
+        dp.isr       = h->d_isr.get();
         dp.T         = Tc;
         dp.Tpad      = Tpad;
         dp.dim       = h->dim;
@@ -2782,42 +2567,30 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
         const bool use_uni = h->uniform;
         const int screen = h->tune_screen;  // 0: plain f64 kernel (A/B runs, tests)
         const bool need64  = use_uni && mode == AMX_GMM_MAX && !screen;
-        if (need64 && need > h->dist64_cap) {
-            hipFree(h->d_dist64);
-            h->d_dist64   = nullptr;
-            h->dist64_cap = 0;
-            AMX_HIP(hipMalloc((void**)&h->d_dist64, need * sizeof(double)));
-            h->dist64_cap = need;
-        }
+        if (need64)  // (screen=0 passes are never recorded: the graphs stay)
+            AMX_TRY(h->d_dist64.reserve(need));
         // pruned exact path of a shared-list model (gmm_tied.hip) unless the survivor statistics of earlier calls say that this model /
         // these features leave too much standing (tied_decide_prune); decided here because the distance kernel then also writes the
         // frame-major image that path works on
-        const bool prune = use_uni && mode == AMX_GMM_MAX && screen && (h->tied_forced >= 0 ? h->tied_forced == 1 : tied_decide_prune(h));
+        const bool prune = use_uni && mode == AMX_GMM_MAX && screen && (forced >= 0 ? forced == 1 : tied_decide_prune(h));
         float*              dt   = nullptr;
         unsigned long long* near = nullptr;
         if (prune) {
             const size_t need_ws = amx_internal_gmm_tied_workspace(h->K, Tc, h->mix_pad);
-            if (need_ws > h->tied_ws_cap) {
-                for (auto& kv : h->graphs)
-                    if (kv.second)
-                        hipGraphExecDestroy(kv.second);
+            if (need_ws > h->d_tied_ws.capacity()) {
                 h->graphs.clear();
-                hipFree(h->d_tied_ws);
-                h->d_tied_ws   = nullptr;
-                h->tied_ws_cap = 0;
-                AMX_HIP(hipMalloc(&h->d_tied_ws, need_ws));
-                h->tied_ws_cap     = need_ws;
+                AMX_TRY(h->d_tied_ws.reserve(need_ws));
                 h->tied_keys_clean = false;
             }
-            dt = amx_internal_gmm_tied_dt(h->d_tied_ws, h->K, Tc, h->d_dens_pos != nullptr);
+            dt = amx_internal_gmm_tied_dt(h->d_tied_ws.get(), h->K, Tc, h->d_dens_pos.get() != nullptr);
         }
         {
             amx::ScopedKernelTimer timer(h->ctx, "gmm_dist");
-            const bool list_order = dt && !need64 && h->d_means_t && h->tune_dist_list;
+            const bool list_order = dt && !need64 && h->d_means_t.get() && h->tune_dist_list;
             if (list_order && h->tune_near_fused && !(h->tied_capturing && !h->tied_keys_clean)) {
-                near = amx_internal_gmm_tied_near(h->d_tied_ws);
+                near = amx_internal_gmm_tied_near(h->d_tied_ws.get());
                 if (near && !h->tied_keys_clean) {  // a new workspace, or a call that did not get as far as putting the keys back
-                    int ri = amx_internal_gmm_tied_near_init(h->ctx, h->d_tied_ws);
+                    int ri = amx_internal_gmm_tied_near_init(h->ctx, h->d_tied_ws.get());
                     if (ri != AMX_OK)
                         return ri;
                 }
@@ -2830,7 +2603,7 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
                 near = nullptr;
             }
             if (r == AMX_ERR_STATE)  // (a dimension without an instance, or not the pruned one-pass path)
-                r = launch_dist(h, dp, dim3(amx::ceil_div(h->n_dens, dp.dens_tile), fb), need64 ? h->d_dist64 : nullptr, stage, dt,
+                r = launch_dist(h, dp, dim3(amx::ceil_div(h->n_dens, dp.dens_tile), fb), need64 ? h->d_dist64.get() : nullptr, stage, dt,
                                 (h->K + 63) & ~63);
             if (r != AMX_OK)
                 return r;
@@ -2843,13 +2616,13 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
             uint32_t*              bd = best_dev ? best_dev + (size_t)t0 * h->n_mix : nullptr;
             amx::ScopedKernelTimer timer(h->ctx, "gmm_combine");
 #define AMX_UNI(STATE, F)                                                                                                        \
-    hipLaunchKernelGGL((amx::gmm_combine_uniform_kernel<amx::STATE, F>), grid, dim3(256), 0, h->ctx->stream, h->d_dist, h->d_dist64, \
-                       sc, bd, h->d_m2lw_t, h->d_k_dens, h->d_ln64, h->d_ln32, ud)
+    hipLaunchKernelGGL((amx::gmm_combine_uniform_kernel<amx::STATE, F>), grid, dim3(256), 0, h->ctx->stream, h->d_dist.get(), h->d_dist64.get(), \
+                       sc, bd, h->d_m2lw_t.get(), h->d_k_dens.get(), h->d_ln64.get(), h->d_ln32.get(), ud)
             if (mode == AMX_GMM_MAX && screen) {
                 if (prune) {
-                    int r = amx_internal_gmm_tied_score(h->ctx, h->d_dist, h->d_k_dens, h->K, Tc, Tpad, h->n_mix, h->mix_pad, h->d_aup,
-                                                        h->d_amax, h->d_m2lw_t, h->d_ahat_t, h->d_ln64, h->d_ln32, h->d_amin, h->d_tied_ws, sc, bd,
-                                                        h->d_tied_surv, dt != nullptr, near != nullptr);
+                    int r = amx_internal_gmm_tied_score(h->ctx, h->d_dist.get(), h->d_k_dens.get(), h->K, Tc, Tpad, h->n_mix, h->mix_pad, h->d_aup.get(),
+                                                        h->d_amax.get(), h->d_m2lw_t.get(), h->d_ahat_t.get(), h->d_ln64.get(), h->d_ln32.get(), h->d_amin.get(), h->d_tied_ws.get(), sc, bd,
+                                                        h->d_tied_surv.get(), dt != nullptr, near != nullptr);
                     if (r != AMX_OK)
                         return r;
                     if (near)
@@ -2859,8 +2632,8 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
                     h->tied_rep_triples += (unsigned long long)h->K * (unsigned long long)Tc * (unsigned long long)(h->mix_pad / 64);
                 }
                 else
-                    hipLaunchKernelGGL(amx::gmm_tied_tile_kernel, dim3(h->mix_pad / 64, Tpad / 64), dim3(256), 0, h->ctx->stream, h->d_dist, sc,
-                                       bd, h->d_m2lw_t, h->d_ahat_t, h->d_amax, h->d_k_dens, h->d_ln64, ud);
+                    hipLaunchKernelGGL(amx::gmm_tied_tile_kernel, dim3(h->mix_pad / 64, Tpad / 64), dim3(256), 0, h->ctx->stream, h->d_dist.get(), sc,
+                                       bd, h->d_m2lw_t.get(), h->d_ahat_t.get(), h->d_amax.get(), h->d_k_dens.get(), h->d_ln64.get(), ud);
             }
             else if (mode == AMX_GMM_MAX) {
                 if (FR == 4) AMX_UNI(MaxState, 4);
@@ -2878,13 +2651,13 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
             continue;
         }
         amx::GmmCombineParams cp;
-        cp.dist     = h->d_dist;
+        cp.dist     = h->d_dist.get();
         cp.scores   = scores_dev + (size_t)t0 * h->n_mix;
         cp.best     = best_dev ? best_dev + (size_t)t0 * h->n_mix : nullptr;
-        cp.mix_off  = h->d_mix_off;
-        cp.k_dens   = h->d_k_dens;
-        cp.k_c64    = h->d_k_c64;
-        cp.k_c32    = h->d_k_c32;
+        cp.mix_off  = h->d_mix_off.get();
+        cp.k_dens   = h->d_k_dens.get();
+        cp.k_c64    = h->d_k_c64.get();
+        cp.k_c32    = h->d_k_c32.get();
         cp.T        = Tc;
         cp.Tpad     = Tpad;
         cp.n_mix    = h->n_mix;
@@ -2903,7 +2676,54 @@ int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float
     return AMX_OK;
 }
 
-extern "C" int amx_stats_accumulate_dev(amx_ctx*, const float*, int, int, uint32_t*, unsigned long long*, double*);
+
+int amx_gmm_score_dev(amx_gmm* h, int mode, const float* feats_dev, int T, float* scores_dev, uint32_t* best_dev) {
+    AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_gmm_score_dev: NULL handle");
+    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_gmm_score_dev: host-only handle (created without a context)");
+    AMX_REQUIRE(mode == AMX_GMM_MAX || mode == AMX_GMM_SUM || mode == AMX_GMM_BATCH_FLOAT || mode == AMX_GMM_SIMD || mode == AMX_GMM_BATCH_INT ||
+                        mode == AMX_GMM_PRESELECTION_FLOAT || mode == AMX_GMM_PRESELECTION_INT,
+                AMX_ERR_INVALID,
+                "amx_gmm_score_dev: unknown mode %d", mode);
+    AMX_REQUIRE(T >= 0, AMX_ERR_INVALID, "amx_gmm_score_dev: negative frame count");
+    if (T == 0)
+        return AMX_OK;
+    AMX_REQUIRE(feats_dev && scores_dev, AMX_ERR_INVALID, "amx_gmm_score_dev: NULL buffer");
+    AMX_HIP(hipSetDevice(h->ctx->device));
+    // contract=fma covers every mode (round 6): the float scorers fuse the distance's accumulate, the preselection scorer also its
+    // clustering distances (Mm::unrolledVectorDistance: one vfmadd231ss per term in the default build); the quantised scorers' arithmetic
+    // is integer -- their one f64 site, gaussLogNormFactor's N * log(2 pi) + logNorm, follows the contract on the host (gmm_simd.hip)
+    switch (mode) {
+        case AMX_GMM_SIMD:
+        case AMX_GMM_BATCH_INT:
+        case AMX_GMM_PRESELECTION_INT: return score_quantised(h, mode, feats_dev, T, scores_dev, best_dev);
+        case AMX_GMM_PRESELECTION_FLOAT: return score_presel_float(h, feats_dev, T, scores_dev, best_dev);
+        case AMX_GMM_BATCH_FLOAT: return score_batch_float(h, feats_dev, T, scores_dev, best_dev);
+        default: break;
+    }
+    if (!h->tied)
+        return h->screen && mode == AMX_GMM_MAX ? score_cart_screened(h, feats_dev, T, scores_dev, best_dev)
+                                                : score_direct(h, mode, feats_dev, T, scores_dev, best_dev);
+    const int chunk_max = (int)std::max<size_t>(256, std::min<size_t>(16384, ((size_t)64 << 20) / (size_t)h->n_dens / 256 * 256));
+    if (!(h->uniform && mode == AMX_GMM_MAX && T <= chunk_max && T <= 4096 && h->tune_screen))
+        return score_tied(h, mode, feats_dev, T, scores_dev, best_dev, chunk_max, -1);
+    // A decoder-sized pass of a shared-list model: decided once, dense or pruned.  The pruned path is six launches (and, every 8th
+    // call, a 2 KB copy) whose gaps are a seventh of the pass, so with tuning graph=1 repeated passes on unchanged buffers are
+    // replayed as one HIP graph like the screened CART path (the decision stays outside: only the pruned path is recorded).
+    const bool prune = tied_decide_prune(h);
+    auto       pass  = [&](bool capturing) {
+        h->tied_capturing = capturing;
+        const int r       = score_tied(h, mode, feats_dev, T, scores_dev, best_dev, chunk_max, prune ? 1 : 0);
+        h->tied_capturing = false;
+        return r;
+    };
+    if (!prune || !h->graphs.use_graphs || h->ctx->profiling)
+        return pass(false);
+    GraphCache::Ran ran;
+    AMX_TRY(h->graphs.run(GraphKey{feats_dev, scores_dev, best_dev, h->ctx->stream, T}, h->ctx->stream, pass, &ran));
+    if (ran == GraphCache::kReplayed)  // the statistics the pass would have kept
+        h->tied_rep_triples += (unsigned long long)h->K * (unsigned long long)T * (unsigned long long)(h->mix_pad / 64);
+    return ran == GraphCache::kPlain ? AMX_OK : tied_publish(h);  // (the copy is never recorded in the graph)
+}
 
 int amx_gmm_score_stats_dev(amx_gmm* h, const float* feats_dev, int T, float* scores_dev, uint32_t* best_density_dev, uint32_t* best_state_dev,
                             unsigned long long* state_counts_dev, double* score_sum_dev) {
@@ -2939,7 +2759,7 @@ int amx_gmm_score_stats_u8_dev(amx_gmm* h, const float* feats_dev, int T, float*
         return AMX_OK;
     AMX_REQUIRE(feats_dev && scores_dev && best_density_dev, AMX_ERR_INVALID, "amx_gmm_score_stats_u8_dev: NULL buffer");
     AMX_HIP(hipSetDevice(h->ctx->device));
-    const bool fused = !h->tied && h->screen && h->d_fus_rec && h->tune_fused && !h->tune_screen_all;
+    const bool fused = !h->tied && h->screen && h->d_fus_rec.get() && h->tune_fused && !h->tune_screen_all;
     bool       direct = fused;
     for (int t0 = 0; t0 < T && direct; t0 += h->tune_chunk) {  // every chunk of the pass on an 8- or 12-wave kernel
         const int nw = amx_internal_gmm_fused_waves((std::min(h->tune_chunk, T - t0) + 255) / 256 * 256, h->tune_fused_waves);
@@ -2948,18 +2768,12 @@ int amx_gmm_score_stats_u8_dev(amx_gmm* h, const float* feats_dev, int T, float*
     if (direct)
         return score_screened(h, feats_dev, T, scores_dev, (uint32_t*)best_density_dev, true, best_state_dev, state_counts_dev, score_sum_dev, 1);
     const size_t need = (size_t)T * h->n_mix;
-    if (need > h->best32_cap) {
-        hipFree(h->d_best32);
-        h->d_best32   = nullptr;
-        h->best32_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_best32, need * 4));
-        h->best32_cap = need;
-    }
-    int r = amx_gmm_score_stats_dev(h, feats_dev, T, scores_dev, h->d_best32, best_state_dev, state_counts_dev, score_sum_dev);
+    AMX_TRY(h->d_best32.reserve(need));  // (no recorded pass writes it: the graphs stay)
+    int r = amx_gmm_score_stats_dev(h, feats_dev, T, scores_dev, h->d_best32.get(), best_state_dev, state_counts_dev, score_sum_dev);
     if (r != AMX_OK)
         return r;
     hipLaunchKernelGGL(amx::best_narrow_kernel, dim3((unsigned)std::min<size_t>((need + 1023) / 1024, 65536)), dim3(256), 0, h->ctx->stream,
-                       h->d_best32, best_density_dev, need);
+                       h->d_best32.get(), best_density_dev, need);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -2970,11 +2784,11 @@ int amx_gmm_screen_counts(amx_gmm* h, int enable, unsigned long long* survivors,
         *survivors = 0;
     if (pairs)
         *pairs = 0;
-    if (h->d_tied_surv) {  // tied model on the pruned path: (density, frame, 64-mixture tile) triples that survived / were submitted
+    if (h->d_tied_surv.get()) {  // tied model on the pruned path: (density, frame, 64-mixture tile) triples that survived / were submitted
         AMX_HIP(hipSetDevice(h->ctx->device));
         AMX_HIP(hipStreamSynchronize(h->ctx->stream));
         unsigned long long c[256], v = 0;
-        AMX_HIP(hipMemcpy(c, h->d_tied_surv, sizeof c, hipMemcpyDeviceToHost));
+        AMX_HIP(hipMemcpy(c, h->d_tied_surv.get(), sizeof c, hipMemcpyDeviceToHost));
         for (int i = 0; i < 256; ++i)
             v += c[i];
         if (survivors)
@@ -2985,26 +2799,22 @@ int amx_gmm_screen_counts(amx_gmm* h, int enable, unsigned long long* survivors,
         h->tied_rep_triples = 0;
         return AMX_OK;
     }
-    if (!h->d_fus_surv)  // not the fused screened path: nothing is counted
+    if (!h->d_fus_surv.get())  // not the fused screened path: nothing is counted
         return AMX_OK;
     AMX_HIP(hipSetDevice(h->ctx->device));
     AMX_HIP(hipStreamSynchronize(h->ctx->stream));
     unsigned long long v = 0, part[256];
-    AMX_HIP(hipMemcpy(part, h->d_fus_surv, sizeof part, hipMemcpyDeviceToHost));
+    AMX_HIP(hipMemcpy(part, h->d_fus_surv.get(), sizeof part, hipMemcpyDeviceToHost));
     for (int i = 0; i < 256; ++i)
         v += part[i];
     if (survivors)
         *survivors = v;
     if (pairs)
         *pairs = h->fus_pairs;
-    AMX_HIP(hipMemset(h->d_fus_surv, 0, 256 * 8));
+    AMX_HIP(hipMemset(h->d_fus_surv.get(), 0, 256 * 8));
     h->fus_pairs = 0;
-    if (h->count_survivors != (enable != 0)) {  // captured passes carry the counter argument they were recorded with
-        for (auto& kv : h->graphs)
-            if (kv.second)
-                hipGraphExecDestroy(kv.second);
+    if (h->count_survivors != (enable != 0))  // captured passes carry the counter argument they were recorded with
         h->graphs.clear();
-    }
     h->count_survivors = enable != 0;
     return AMX_OK;
 }
@@ -3025,13 +2835,7 @@ int amx_gmm_set_preselection(amx_gmm* h, int clusters, int select_clusters, int 
 int amx_gmm_preselection_clustering(amx_gmm* h, int* n_clusters, uint32_t* cluster_of, float* cluster_means) {
     AMX_REQUIRE(h && h->ctx, AMX_ERR_INVALID, "amx_gmm_preselection_clustering: NULL / host-only handle");
     AMX_REQUIRE(h->pooled, AMX_ERR_INVALID, "amx_gmm_preselection_clustering: feature scorer supports only globally pooled covariance");
-    if (!h->presel) {
-        AMX_HIP(hipSetDevice(h->ctx->device));
-        const int r = amx_internal_gmm_presel_create(h->ctx, h->dim, h->nk, h->h_k_mean.data(), h->h_smeans.data(), h->d_smeans, h->d_k_mean,
-                                                     h->presel_clusters, h->presel_select, h->presel_iterations, h->presel_backoff, h->contract_fma ? 1 : 0, &h->presel);
-        if (r != AMX_OK)
-            return r;
-    }
+    AMX_TRY(ensure_presel(h));
     return amx_internal_gmm_presel_info(h->presel, n_clusters, cluster_of, cluster_means);
 }
 
@@ -3168,7 +2972,7 @@ int amx_gmm_best_density_dev(amx_gmm* h, const float* feats_dev, int T, const ui
     AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_gmm_best_density_dev: NULL handle");
     AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_gmm_best_density_dev: host-only handle (created without a context)");
     AMX_REQUIRE(T >= 0, AMX_ERR_INVALID, "amx_gmm_best_density_dev: negative frame count");
-    AMX_REQUIRE(h->d_k_mean && h->d_k_cov && h->d_k_c64 && h->d_means && h->d_isr, AMX_ERR_UNSUPPORTED,
+    AMX_REQUIRE(h->d_k_mean.get() && h->d_k_cov.get() && h->d_k_c64.get() && h->d_means.get() && h->d_isr.get(), AMX_ERR_UNSUPPORTED,
                 "amx_gmm_best_density_dev: the model's scorer keeps no diagonal-maximum tables on the device");
     if (T == 0)
         return AMX_OK;
@@ -3176,7 +2980,7 @@ int amx_gmm_best_density_dev(amx_gmm* h, const float* feats_dev, int T, const ui
     AMX_HIP(hipSetDevice(h->ctx->device));
     amx::ScopedKernelTimer timer(h->ctx, "gmm_best_density");
     hipLaunchKernelGGL((h->contract_fma ? amx::gmm_best_density_kernel<true> : amx::gmm_best_density_kernel<false>), dim3((T + 255) / 256), dim3(256), 0, h->ctx->stream, feats_dev, mixture_dev, best_density_dev,
-                       scores_dev, h->d_mix_off, h->d_k_mean, h->d_k_cov, h->d_k_c64, h->d_means, h->d_isr, T, h->dim, h->n_mix);
+                       scores_dev, h->d_mix_off.get(), h->d_k_mean.get(), h->d_k_cov.get(), h->d_k_c64.get(), h->d_means.get(), h->d_isr.get(), T, h->dim, h->n_mix);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -3190,14 +2994,13 @@ int amx_gmm_accumulate_dev(amx_gmm* h, const float* feats_dev, int T, const uint
         return AMX_OK;
     AMX_REQUIRE(feats_dev && mixture_dev && best_density_dev && acc_dev, AMX_ERR_INVALID, "amx_gmm_accumulate_dev: NULL buffer");
     AMX_HIP(hipSetDevice(h->ctx->device));
-    const long long off_mw = (long long)h->nk, off_ms = off_mw + h->n_mean, off_cw = off_ms + (long long)h->n_mean * h->dim,
-                    off_cs = off_cw + h->n_cov;
+    const AccLayout        l = acc_layout(h);
     const int              pooled = (h->n_cov == 1 && h->dim <= 256) ? 1 : 0;
     const int              blocks = (T + 255) / 256;
     amx::ScopedKernelTimer timer(h->ctx, "gmm_accumulate");
     hipLaunchKernelGGL(amx::gmm_accumulate_kernel, dim3(blocks), dim3(256), 0, h->ctx->stream, feats_dev, mixture_dev, best_density_dev,
-                       (const unsigned char*)nullptr, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off, h->d_k_dens, h->d_d_mean, h->d_d_cov, acc_dev,
-                       off_mw, off_ms, off_cw, off_cs, pooled);
+                       (const unsigned char*)nullptr, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off.get(), h->d_k_dens.get(), h->d_d_mean.get(), h->d_d_cov.get(), acc_dev,
+                       l.off_mw, l.off_ms, l.off_cw, l.off_cs, pooled);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -3211,14 +3014,13 @@ int amx_gmm_accumulate_u8_dev(amx_gmm* h, const float* feats_dev, int T, const u
         return AMX_OK;
     AMX_REQUIRE(feats_dev && mixture_dev && best_density_dev && acc_dev, AMX_ERR_INVALID, "amx_gmm_accumulate_u8_dev: NULL buffer");
     AMX_HIP(hipSetDevice(h->ctx->device));
-    const long long off_mw = (long long)h->nk, off_ms = off_mw + h->n_mean, off_cw = off_ms + (long long)h->n_mean * h->dim,
-                    off_cs = off_cw + h->n_cov;
+    const AccLayout        l = acc_layout(h);
     const int              pooled = (h->n_cov == 1 && h->dim <= 256) ? 1 : 0;
     const int              blocks = (T + 255) / 256;
     amx::ScopedKernelTimer timer(h->ctx, "gmm_accumulate");
     hipLaunchKernelGGL(amx::gmm_accumulate_kernel, dim3(blocks), dim3(256), 0, h->ctx->stream, feats_dev, mixture_dev, (const uint32_t*)nullptr,
-                       (const unsigned char*)best_density_dev, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off, h->d_k_dens, h->d_d_mean, h->d_d_cov,
-                       acc_dev, off_mw, off_ms, off_cw, off_cs, pooled);
+                       (const unsigned char*)best_density_dev, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off.get(), h->d_k_dens.get(), h->d_d_mean.get(), h->d_d_cov.get(),
+                       acc_dev, l.off_mw, l.off_ms, l.off_cw, l.off_cs, pooled);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -3242,15 +3044,14 @@ int amx_gmm_accumulate_weighted_dev(amx_gmm* h, int mode, const float* feats_dev
                     amx::kBwMaxDens, kmax);
     }
     AMX_HIP(hipSetDevice(h->ctx->device));
-    const long long off_mw = (long long)h->nk, off_ms = off_mw + h->n_mean, off_cw = off_ms + (long long)h->n_mean * h->dim,
-                    off_cs = off_cw + h->n_cov;
+    const AccLayout        l = acc_layout(h);
     const int              pooled = (h->n_cov == 1) ? 1 : 0;
     const int              per_block = 4 * amx::kBwFramesPerWave;
     const int              blocks = (T + per_block - 1) / per_block;
     amx::ScopedKernelTimer timer(h->ctx, "gmm_accumulate_weighted");
     hipLaunchKernelGGL((h->contract_fma ? amx::gmm_accumulate_weighted_kernel<true> : amx::gmm_accumulate_weighted_kernel<false>), dim3(blocks), dim3(256), 0, h->ctx->stream, mode, feats_dev, mixture_dev,
-                       weight_dev, best_density_dev, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off, h->d_k_dens, h->d_d_mean, h->d_d_cov,
-                       h->d_k_c32, h->d_means, h->d_isr, acc_dev, off_mw, off_ms, off_cw, off_cs, pooled);
+                       weight_dev, best_density_dev, best_density_ld, T, h->dim, h->n_mix, h->d_mix_off.get(), h->d_k_dens.get(), h->d_d_mean.get(), h->d_d_cov.get(),
+                       h->d_k_c32.get(), h->d_means.get(), h->d_isr.get(), acc_dev, l.off_mw, l.off_ms, l.off_cw, l.off_cs, pooled);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -3267,30 +3068,16 @@ int amx_gmm_score(amx_gmm* h, int mode, const float* feats_host, int T, float* s
     // hipMalloc / hipFree pair per call costs more than scoring a small batch
     hipStream_t  st = h->ctx->stream;
     const size_t nf = (size_t)T * h->dim, ns = (size_t)T * h->n_mix;
-    auto grow = [h](void** p, size_t* cap, size_t need) {
-        if (need <= *cap)
-            return true;
-        for (auto& kv : h->graphs)  // captured passes may hold the old staging addresses
-            if (kv.second)
-                hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-        hipFree(*p);
-        *p   = nullptr;
-        *cap = 0;
-        if (hipMalloc(p, need) != hipSuccess)
-            return false;
-        *cap = need;
-        return true;
-    };
-    if (!grow((void**)&h->d_host_f, &h->host_f_cap, nf * 4) || !grow((void**)&h->d_host_s, &h->host_s_cap, ns * 4) ||
-        (best_host && !grow((void**)&h->d_host_b, &h->host_b_cap, ns * 4))) {
+    if (nf > h->d_host_f.capacity() || ns > h->d_host_s.capacity() || (best_host && ns > h->d_host_b.capacity()))
+        h->graphs.clear();  // captured passes may hold the old staging addresses
+    if (h->d_host_f.reserve(nf) != AMX_OK || h->d_host_s.reserve(ns) != AMX_OK || (best_host && h->d_host_b.reserve(ns) != AMX_OK)) {
         (void)hipGetLastError();
         amx::set_error("amx_gmm_score: out of device memory");
         return AMX_ERR_DEVICE;
     }
-    float*    d_f = h->d_host_f;
-    float*    d_s = h->d_host_s;
-    uint32_t* d_b = best_host ? h->d_host_b : nullptr;
+    float*    d_f = h->d_host_f.get();
+    float*    d_s = h->d_host_s.get();
+    uint32_t* d_b = best_host ? h->d_host_b.get() : nullptr;
     if (hipMemcpyAsync(d_f, feats_host, nf * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
         amx::set_error("amx_gmm_score: H2D copy failed");
         return AMX_ERR_DEVICE;

@@ -22,6 +22,7 @@
 //     partials of round 1 (320 MB per pass) shrink to one (min, state) pair per frame and workgroup.
 // HBM traffic per pass = scores + best densities (8 B per frame and mixture) + the model records once per XCD.
 #include "common.hpp"
+#include "gmm_internal.hpp"
 #include "gmm_device.hpp"
 
 #include <cfloat>
@@ -786,7 +787,7 @@ extern "C" int amx_internal_gmm_fused_supported(int dim, int pooled, int Kp) {
 //   [33792, +256 LD 4)    f32 mean rows, row = mixture * 16 + slot, the density's (f64) m2lw + logNorm in the last two floats
 extern "C" int amx_internal_gmm_fused_create(int dim, int n_mix, int n_tiles, const void* A2_host, const uint32_t* mix_off,
                                              const uint32_t* k_mean, const double* c64, const float* means, const float* p1, const float* p2,
-                                             void** rec_dev, size_t* rec_bytes) {
+                                             amx::DevBuf<char>& rec_dev) {
     const int    LD = amx::fused_ld(dim), REC = amx::fused_rec_bytes(dim);
     const size_t total = (size_t)n_tiles * REC;
     std::vector<char> rec(total, 0);
@@ -815,16 +816,7 @@ extern "C" int amx_internal_gmm_fused_create(int dim, int n_mix, int n_tiles, co
             ((int*)pp)[32 + j] = nd;
         }
     }
-    void* d = nullptr;
-    AMX_HIP(hipMalloc(&d, total));
-    if (hipMemcpy(d, rec.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(d);
-        amx::set_error("amx_gmm_create: upload of the fused tile records failed");
-        return AMX_ERR_DEVICE;
-    }
-    *rec_dev   = d;
-    *rec_bytes = total;
-    return AMX_OK;
+    return rec_dev.upload(rec.data(), total);
 }
 
 // waves per workgroup: 12 (three per SIMD, 384 frames; the kernel uses 158 VGPRs) for long passes -- measured 5.1 ms against 5.9 ms

@@ -16,6 +16,7 @@
 //              presel_score_kernel: gmm_batch_float_kernel's arithmetic with the wave's lane mask of the density's cluster read
 //              through the scalar cache -- a density whose cluster no frame of the wave selected is skipped altogether.
 #include "common.hpp"
+#include "gmm_internal.hpp"
 
 #include <algorithm>
 #include "gmm_device.hpp"
@@ -206,11 +207,11 @@ struct GmmPresel {
     int       dim = 0, n_clusters = 0, n_select = 0;
     size_t    nk = 0;
     float     backoff = 40000.f;
-    float*    d_cm = nullptr;          // [n_clusters x dim]
-    uint32_t* d_cluster_of = nullptr;  // [nk]
-    float*    d_dist = nullptr;        // per-call scratch [n_clusters x Tpad]
-    unsigned long long* d_masks = nullptr;
-    int       cap_T = 0;
+    DevBuf<float>    d_cm;          // [n_clusters x dim]
+    DevBuf<uint32_t> d_cluster_of;  // [nk]
+    DevBuf<float>    d_dist;        // per-call scratch [n_clusters x Tpad]
+    DevBuf<unsigned long long> d_masks;
+    int       cap_T = 0;            // frames d_dist and d_masks are sized for
     std::vector<uint32_t> h_cluster_of;
     std::vector<float>    h_cm;
 };
@@ -218,17 +219,8 @@ struct GmmPresel {
 }  // namespace amx
 
 extern "C" void amx_internal_gmm_presel_destroy(void* p) {
-    amx::GmmPresel* s = (amx::GmmPresel*)p;
-    if (!s)
-        return;
-    hipFree(s->d_cm);
-    hipFree(s->d_cluster_of);
-    hipFree(s->d_dist);
-    hipFree(s->d_masks);
-    delete s;
+    delete (amx::GmmPresel*)p;
 }
-
-#define AMX_PRESEL_DIMS(X) X(16) X(24) X(32) X(33) X(39) X(40) X(45) X(48) X(64)
 
 // smeans_host [n_mean x dim] pre-scaled means, k_mean_host [nk]; device copies of both are the scorer's own (d_smeans, d_k_mean)
 extern "C" int amx_internal_gmm_presel_create(amx_ctx* ctx, int dim, size_t nk, const uint32_t* k_mean_host, const float* smeans_host,
@@ -269,29 +261,29 @@ extern "C" int amx_internal_gmm_presel_create(amx_ctx* ctx, int dim, size_t nk, 
         amx_internal_gmm_presel_destroy(s);
         return AMX_ERR_DEVICE;
     };
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&s->d_cm, s->h_cm.size() * 4) != hipSuccess ||
-        hipMalloc((void**)&s->d_cluster_of, std::max<size_t>(nk, 1) * 4) != hipSuccess)
+    if (hipSetDevice(ctx->device) != hipSuccess || s->d_cm.reserve(s->h_cm.size()) != AMX_OK ||
+        s->d_cluster_of.reserve(std::max<size_t>(nk, 1)) != AMX_OK)
         return fail("device allocation");
     std::vector<double> sums((size_t)n_clusters * dim);
     std::vector<size_t> cnt(n_clusters);
     for (int it = 0; it < iterations; ++it) {
-        if (hipMemcpyAsync(s->d_cm, s->h_cm.data(), s->h_cm.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (hipMemcpyAsync(s->d_cm.get(), s->h_cm.data(), s->h_cm.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
             return fail("upload");
         const dim3 grid((unsigned)((nk + 255) / 256));
         switch (dim) {
 #define X(D)                                                                                                                        \
     case D:                                                                                                                         \
-        hipLaunchKernelGGL((s->fma ? presel_assign_kernel<D, true> : presel_assign_kernel<D, false>), grid, dim3(256), 0, ctx->stream, d_smeans, d_k_mean, (int)nk, s->d_cm, n_clusters, \
-                           s->d_cluster_of, dim);                                                                                   \
+        hipLaunchKernelGGL((s->fma ? presel_assign_kernel<D, true> : presel_assign_kernel<D, false>), grid, dim3(256), 0, ctx->stream, d_smeans, d_k_mean, (int)nk, s->d_cm.get(), n_clusters, \
+                           s->d_cluster_of.get(), dim);                                                                                   \
         break;
-            AMX_PRESEL_DIMS(X)
+            AMX_GMM_DIMS(X)
 #undef X
             default:  // any other dimension: rows re-read from memory, the same sums
-                hipLaunchKernelGGL((s->fma ? presel_assign_kernel<0, true> : presel_assign_kernel<0, false>), grid, dim3(256), 0, ctx->stream, d_smeans, d_k_mean, (int)nk, s->d_cm, n_clusters,
-                                   s->d_cluster_of, dim);
+                hipLaunchKernelGGL((s->fma ? presel_assign_kernel<0, true> : presel_assign_kernel<0, false>), grid, dim3(256), 0, ctx->stream, d_smeans, d_k_mean, (int)nk, s->d_cm.get(), n_clusters,
+                                   s->d_cluster_of.get(), dim);
                 break;
         }
-        if (hipMemcpyAsync(s->h_cluster_of.data(), s->d_cluster_of, nk * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        if (hipMemcpyAsync(s->h_cluster_of.data(), s->d_cluster_of.get(), nk * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess)
             return fail("density assignment");
         // updateClusterMeans: f64 sums in density order
@@ -310,8 +302,8 @@ extern "C" int amx_internal_gmm_presel_create(amx_ctx* ctx, int dim, size_t nk, 
                 for (int i = 0; i < dim; ++i)
                     s->h_cm[(size_t)c * dim + i] = (float)(sums[(size_t)c * dim + i] / (double)cnt[c]);
     }
-    if (hipMemcpy(s->d_cm, s->h_cm.data(), s->h_cm.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->d_cluster_of, s->h_cluster_of.data(), nk * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(s->d_cm.get(), s->h_cm.data(), s->h_cm.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(s->d_cluster_of.get(), s->h_cluster_of.data(), nk * 4, hipMemcpyHostToDevice) != hipSuccess)
         return fail("upload");
     *out = s;
     return AMX_OK;
@@ -353,13 +345,9 @@ static int presel_score_chunk(amx::GmmPresel* s, amx_ctx* ctx, const float* feat
     AMX_HIP(hipSetDevice(ctx->device));
     const int Tpad = (T + 63) / 64 * 64, n_groups = Tpad / 64;
     if (Tpad > s->cap_T) {
-        hipFree(s->d_dist);
-        hipFree(s->d_masks);
-        s->d_dist  = nullptr;
-        s->d_masks = nullptr;
-        s->cap_T   = 0;
-        AMX_HIP(hipMalloc((void**)&s->d_dist, (size_t)s->n_clusters * Tpad * 4));
-        AMX_HIP(hipMalloc((void**)&s->d_masks, (size_t)n_groups * s->n_clusters * 8));
+        s->cap_T = 0;
+        AMX_TRY(s->d_dist.reserve((size_t)s->n_clusters * Tpad));
+        AMX_TRY(s->d_masks.reserve((size_t)n_groups * s->n_clusters));
         s->cap_T = Tpad;
     }
     {
@@ -367,14 +355,14 @@ static int presel_score_chunk(amx::GmmPresel* s, amx_ctx* ctx, const float* feat
         switch (s->dim) {
 #define X(D)                                                                                                                             \
     case D:                                                                                                                              \
-        hipLaunchKernelGGL((s->fma ? cluster_select_kernel<D, true> : cluster_select_kernel<D, false>), dim3(n_groups), dim3(64), 0, ctx->stream, feats_dev, d_isr0, T, Tpad, s->d_cm,     \
-                           s->n_clusters, s->n_select, s->d_dist, s->d_masks, s->dim);                                                   \
+        hipLaunchKernelGGL((s->fma ? cluster_select_kernel<D, true> : cluster_select_kernel<D, false>), dim3(n_groups), dim3(64), 0, ctx->stream, feats_dev, d_isr0, T, Tpad, s->d_cm.get(),     \
+                           s->n_clusters, s->n_select, s->d_dist.get(), s->d_masks.get(), s->dim);                                                   \
         break;
-            AMX_PRESEL_DIMS(X)
+            AMX_GMM_DIMS(X)
 #undef X
             default:
-                hipLaunchKernelGGL((s->fma ? cluster_select_kernel<0, true> : cluster_select_kernel<0, false>), dim3(n_groups), dim3(64), 0, ctx->stream, feats_dev, d_isr0, T, Tpad, s->d_cm,
-                                   s->n_clusters, s->n_select, s->d_dist, s->d_masks, s->dim);
+                hipLaunchKernelGGL((s->fma ? cluster_select_kernel<0, true> : cluster_select_kernel<0, false>), dim3(n_groups), dim3(64), 0, ctx->stream, feats_dev, d_isr0, T, Tpad, s->d_cm.get(),
+                                   s->n_clusters, s->n_select, s->d_dist.get(), s->d_masks.get(), s->dim);
                 break;
         }
         AMX_HIP(hipGetLastError());
@@ -388,13 +376,13 @@ static int presel_score_chunk(amx::GmmPresel* s, amx_ctx* ctx, const float* feat
 #define X(D)                                                                                                                             \
     case D:                                                                                                                              \
         hipLaunchKernelGGL((s->fma ? presel_score_kernel<D, true> : presel_score_kernel<D, false>), grid, dim3(256), 0, ctx->stream, feats_dev, scores_dev, d_mix_off, d_k_mean, d_k_const, \
-                           d_smeans, d_isr0, s->d_cluster_of, s->d_masks, s->n_clusters, s->backoff, T, n_mix, mt, s->dim);              \
+                           d_smeans, d_isr0, s->d_cluster_of.get(), s->d_masks.get(), s->n_clusters, s->backoff, T, n_mix, mt, s->dim);              \
         break;
-        AMX_PRESEL_DIMS(X)
+        AMX_GMM_DIMS(X)
 #undef X
         default:
             hipLaunchKernelGGL((s->fma ? presel_score_kernel<0, true> : presel_score_kernel<0, false>), grid, dim3(256), 0, ctx->stream, feats_dev, scores_dev, d_mix_off, d_k_mean, d_k_const,
-                               d_smeans, d_isr0, s->d_cluster_of, s->d_masks, s->n_clusters, s->backoff, T, n_mix, mt, s->dim);
+                               d_smeans, d_isr0, s->d_cluster_of.get(), s->d_masks.get(), s->n_clusters, s->backoff, T, n_mix, mt, s->dim);
             break;
     }
     AMX_HIP(hipGetLastError());

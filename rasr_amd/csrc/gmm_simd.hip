@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gmm_internal.hpp"
 
 namespace amx {
 
@@ -381,20 +382,19 @@ struct GmmSimd {
     int      dim = 0, n_mix = 0, n_dens = 0, n_cov = 0;
     size_t   nk = 0;
     float    scaling = 0.f, scaling2 = 0.f;
-    float*   d_isr = nullptr;             // [n_cov x dim], scaled
-    unsigned char* d_qmean = nullptr;     // [n_dens x dim]
-    int*     d_cst[2] = {nullptr, nullptr};  // [nk] per-density constants: SIMD-diagonal-maximum, batch-diagonal-maximum-int
-    uint32_t *d_mix_off = nullptr, *d_k_dens = nullptr, *d_d_cov = nullptr;
-    int*     d_dist = nullptr;
-    size_t   dist_cap = 0;
+    DevBuf<float>         d_isr;     // [n_cov x dim], scaled
+    DevBuf<unsigned char> d_qmean;   // [n_dens x dim]
+    DevBuf<int>           d_cst[2];  // [nk] per-density constants: SIMD-diagonal-maximum, batch-diagonal-maximum-int
+    DevBuf<uint32_t>      d_mix_off, d_k_dens, d_d_cov;
+    DevBuf<int>           d_dist;
     int      n_tiles_r = 0;
-    int8_t*  d_A = nullptr;
-    int*     d_key[2] = {nullptr, nullptr};
+    DevBuf<int8_t>        d_A;
+    DevBuf<int>           d_key[2];
     bool     has_int = false;  // batch-int tables exist (pooled covariance)
     bool     mfma_v[2] = {false, false};
     float    int_scale = 0.f;
-    int8_t*  d_X = nullptr;
-    int*     d_nx = nullptr;
+    DevBuf<int8_t>        d_X;       // [cap_T x 64]
+    DevBuf<int>           d_nx;
     int      cap_T = 0;
     // preselection-batch-int
     std::vector<unsigned char> h_qmean;
@@ -402,20 +402,12 @@ struct GmmSimd {
     int                        ps_clusters = 0, ps_select = 0, ps_iterations = -1;  // parameters of the clustering below
     std::vector<unsigned char> h_cm;
     std::vector<uint32_t>      h_cluster_of;
-    unsigned char*             d_cm = nullptr;
-    uint32_t*                  d_cluster_of = nullptr;
-    int*                       d_cdist = nullptr;
-    unsigned long long*        d_masks = nullptr;
-    int                        ps_cap_T = 0;
+    DevBuf<unsigned char>      d_cm;
+    DevBuf<uint32_t>           d_cluster_of;
+    DevBuf<int>                d_cdist;
+    DevBuf<unsigned long long> d_masks;
+    int                        ps_cap_T = 0;  // frames d_cdist and d_masks are sized for
 };
-
-template<class T>
-static int upload(T** dst, const T* src, size_t n) {
-    AMX_HIP(hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n)
-        AMX_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return AMX_OK;
-}
 
 static int host_quantize(float v) {
     const float r  = std::round(v);
@@ -429,27 +421,7 @@ static int host_quantize(float v) {
 extern "C" {
 
 void amx_internal_gmm_simd_destroy(void* p) {
-    amx::GmmSimd* s = (amx::GmmSimd*)p;
-    if (!s)
-        return;
-    hipFree(s->d_isr);
-    hipFree(s->d_qmean);
-    hipFree(s->d_cst[0]);
-    hipFree(s->d_cst[1]);
-    hipFree(s->d_mix_off);
-    hipFree(s->d_k_dens);
-    hipFree(s->d_d_cov);
-    hipFree(s->d_dist);
-    hipFree(s->d_A);
-    hipFree(s->d_key[0]);
-    hipFree(s->d_key[1]);
-    hipFree(s->d_X);
-    hipFree(s->d_nx);
-    hipFree(s->d_cm);
-    hipFree(s->d_cluster_of);
-    hipFree(s->d_cdist);
-    hipFree(s->d_masks);
-    delete s;
+    delete (amx::GmmSimd*)p;
 }
 
 // float / double -> s32 as the reference's x86-64 build converts (cvttss2si / cvttsd2si): truncation, and the "integer indefinite"
@@ -520,7 +492,7 @@ int amx_internal_gmm_simd_create(const amx_gmm_model* m, int contract_fma, void*
         for (size_t k = 0; k < nk; ++k)
             cst_int[k] = cvt_s32_x86((double)log_norm_factor - (double)int_scale * m->log_weight[k]);
     }
-    GmmSimd* s  = new GmmSimd;
+    std::unique_ptr<GmmSimd> s(new GmmSimd);
     s->dim      = dim;
     s->n_mix    = m->n_mix;
     s->n_dens   = m->n_dens;
@@ -535,12 +507,11 @@ int amx_internal_gmm_simd_create(const amx_gmm_model* m, int contract_fma, void*
         s->h_k_dens.assign(m->dens_index, m->dens_index + nk);
     }
     int r;
-    if ((r = upload(&s->d_isr, isr.data(), isr.size())) != AMX_OK || (r = upload(&s->d_qmean, qmean.data(), qmean.size())) != AMX_OK ||
-        (r = upload(&s->d_cst[0], cst.data(), cst.size())) != AMX_OK ||
-        (s->has_int && (r = upload(&s->d_cst[1], cst_int.data(), cst_int.size())) != AMX_OK) ||
-        (r = upload(&s->d_mix_off, m->mix_offsets, (size_t)m->n_mix + 1)) != AMX_OK ||
-        (r = upload(&s->d_k_dens, m->dens_index, nk)) != AMX_OK || (r = upload(&s->d_d_cov, m->dens_cov, (size_t)m->n_dens)) != AMX_OK) {
-        amx_internal_gmm_simd_destroy(s);
+    if ((r = s->d_isr.upload(isr.data(), isr.size())) != AMX_OK || (r = s->d_qmean.upload(qmean.data(), qmean.size())) != AMX_OK ||
+        (r = s->d_cst[0].upload(cst.data(), cst.size())) != AMX_OK ||
+        (s->has_int && (r = s->d_cst[1].upload(cst_int.data(), cst_int.size())) != AMX_OK) ||
+        (r = s->d_mix_off.upload(m->mix_offsets, (size_t)m->n_mix + 1)) != AMX_OK ||
+        (r = s->d_k_dens.upload(m->dens_index, nk)) != AMX_OK || (r = s->d_d_cov.upload(m->dens_cov, (size_t)m->n_dens)) != AMX_OK) {
         return r;
     }
     // MFMA path tables: pooled covariance, <= 16 densities per mixture, one 64-byte row per slot, keys that fit 28 bits
@@ -548,15 +519,9 @@ int amx_internal_gmm_simd_create(const amx_gmm_model* m, int contract_fma, void*
     for (int i = 0; i < m->n_mix; ++i)
         kmax = std::max(kmax, m->mix_offsets[i + 1] - m->mix_offsets[i]);
     amx::Tuning tune;
-    if (!tune.parse(m->tuning, amx::gmm_tuning_keys, "amx_gmm_create")) {
-        amx_internal_gmm_simd_destroy(s);
+    int         want_i = 1;
+    if (!tune.parse(m->tuning, amx::gmm_tuning_keys, "amx_gmm_create") || !tune.get_int("simd_mfma", 1, 0, 1, &want_i, "amx_gmm_create"))
         return AMX_ERR_INVALID;
-    }
-    int want_i = 1;
-    if (!tune.get_int("simd_mfma", 1, 0, 1, &want_i, "amx_gmm_create")) {
-        amx_internal_gmm_simd_destroy(s);
-        return AMX_ERR_INVALID;
-    }
     const bool want = want_i != 0;
     if (want && m->n_cov == 1 && dim <= 64 && kmax <= 16) {
         const int           n_tiles = (m->n_mix + 15) / 16;
@@ -585,17 +550,15 @@ int amx_internal_gmm_simd_create(const amx_gmm_model* m, int contract_fma, void*
                     key[(size_t)tile * 256 + ml * 16 + slot] = -(int)(base * 16 + slot);
                 }
             if (fits) {
-                if ((!s->d_A && (r = upload(&s->d_A, A.data(), A.size())) != AMX_OK) ||
-                    (r = upload(&s->d_key[v], key.data(), key.size())) != AMX_OK) {
-                    amx_internal_gmm_simd_destroy(s);
+                if ((!s->d_A.get() && (r = s->d_A.upload(A.data(), A.size())) != AMX_OK) ||
+                    (r = s->d_key[v].upload(key.data(), key.size())) != AMX_OK)
                     return r;
-                }
                 s->mfma_v[v] = true;
                 s->n_tiles_r = n_tiles;
             }
         }
     }
-    *out = s;
+    *out = s.release();
     return AMX_OK;
 }
 
@@ -620,19 +583,15 @@ int amx_internal_gmm_simd_score(void* p, amx_ctx* ctx, int variant, const float*
         for (int t0 = 0; t0 < T; t0 += chunk) {
             const int Tc = std::min(chunk, T - t0), Tpad = (Tc + 255) / 256 * 256;
             if (Tpad > s->cap_T) {
-                hipFree(s->d_X);
-                hipFree(s->d_nx);
-                s->d_X   = nullptr;
-                s->d_nx  = nullptr;
                 s->cap_T = 0;
-                AMX_HIP(hipMalloc((void**)&s->d_X, (size_t)Tpad * 64));
-                AMX_HIP(hipMalloc((void**)&s->d_nx, (size_t)Tpad * 4));
+                AMX_TRY(s->d_X.reserve((size_t)Tpad * 64));
+                AMX_TRY(s->d_nx.reserve((size_t)Tpad));
                 s->cap_T = Tpad;
             }
             const float* x = feats_dev + (size_t)t0 * s->dim;
             {
                 ScopedKernelTimer timer(ctx, "gmm_simd_quantize");
-                hipLaunchKernelGGL(simd_quantize_kernel, dim3(Tpad / 4), dim3(256), 0, st, x, s->d_isr, s->d_X, s->d_nx, Tc, Tpad, s->dim);
+                hipLaunchKernelGGL(simd_quantize_kernel, dim3(Tpad / 4), dim3(256), 0, st, x, s->d_isr.get(), s->d_X.get(), s->d_nx.get(), Tc, Tpad, s->dim);
             }
             const int tiles_t = Tpad / 256;
             int       r_split = 1;
@@ -644,7 +603,7 @@ int amx_internal_gmm_simd_score(void* p, amx_ctx* ctx, int variant, const float*
                 attr = true;
             }
             ScopedKernelTimer timer(ctx, "gmm_simd");
-            hipLaunchKernelGGL(simd_mfma_kernel, dim3(tiles_t * r_split), dim3(512), kSimdLds, st, s->d_A, s->d_X, s->d_key[variant], s->d_nx,
+            hipLaunchKernelGGL(simd_mfma_kernel, dim3(tiles_t * r_split), dim3(512), kSimdLds, st, s->d_A.get(), s->d_X.get(), s->d_key[variant].get(), s->d_nx.get(),
                                scores_dev + (size_t)t0 * s->n_mix, best_dev ? best_dev + (size_t)t0 * s->n_mix : nullptr, Tc, s->n_mix,
                                s->n_tiles_r, r_split, scale);
         }
@@ -655,13 +614,7 @@ int amx_internal_gmm_simd_score(void* p, amx_ctx* ctx, int variant, const float*
     int chunk = (int)std::min<size_t>((size_t)T, std::max<size_t>(256, ((size_t)64 << 20) / (size_t)s->n_dens / 256 * 256));
     chunk     = (chunk + 255) / 256 * 256;
     const size_t need = (size_t)s->n_dens * chunk;
-    if (need > s->dist_cap) {
-        hipFree(s->d_dist);
-        s->d_dist   = nullptr;
-        s->dist_cap = 0;
-        AMX_HIP(hipMalloc((void**)&s->d_dist, need * 4));
-        s->dist_cap = need;
-    }
+    AMX_TRY(s->d_dist.reserve(need));
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int    Tc = std::min(chunk, T - t0), fblocks = (Tc + 255) / 256;
         const float* x  = feats_dev + (size_t)t0 * s->dim;
@@ -670,15 +623,15 @@ int amx_internal_gmm_simd_score(void* p, amx_ctx* ctx, int variant, const float*
             dt /= 2;
         {
             ScopedKernelTimer timer(ctx, "gmm_simd_dist");
-            hipLaunchKernelGGL(simd_dist_kernel, dim3((s->n_dens + dt - 1) / dt, fblocks), dim3(256), 0, st, x, s->d_isr, s->d_qmean, s->d_d_cov,
-                               s->d_dist, Tc, chunk, s->dim, s->n_dens, dt);
+            hipLaunchKernelGGL(simd_dist_kernel, dim3((s->n_dens + dt - 1) / dt, fblocks), dim3(256), 0, st, x, s->d_isr.get(), s->d_qmean.get(), s->d_d_cov.get(),
+                               s->d_dist.get(), Tc, chunk, s->dim, s->n_dens, dt);
         }
         int mt = 16;
         while (mt > 1 && (long)((s->n_mix + mt - 1) / mt) * fblocks < 1024)
             mt /= 2;
         ScopedKernelTimer timer(ctx, "gmm_simd");
-        hipLaunchKernelGGL(simd_combine_kernel, dim3((s->n_mix + mt - 1) / mt, fblocks), dim3(256), 0, st, s->d_dist, s->d_cst[variant], s->d_mix_off,
-                           s->d_k_dens, scores_dev + (size_t)t0 * s->n_mix, best_dev ? best_dev + (size_t)t0 * s->n_mix : nullptr, Tc, chunk,
+        hipLaunchKernelGGL(simd_combine_kernel, dim3((s->n_mix + mt - 1) / mt, fblocks), dim3(256), 0, st, s->d_dist.get(), s->d_cst[variant].get(), s->d_mix_off.get(),
+                           s->d_k_dens.get(), scores_dev + (size_t)t0 * s->n_mix, best_dev ? best_dev + (size_t)t0 * s->n_mix : nullptr, Tc, chunk,
                            s->n_mix, mt, scale);
     }
     AMX_HIP(hipGetLastError());
@@ -725,7 +678,7 @@ int amx_internal_gmm_simd_presel_build(void* p, amx_ctx* ctx, int n_clusters, in
     AMX_REQUIRE(n_clusters >= 1 && n_clusters <= 256, AMX_ERR_INVALID, "preselection: clusters must be in 1..256 (got %d)", n_clusters);
     AMX_REQUIRE(n_select >= 1 && n_select <= n_clusters, AMX_ERR_INVALID, "preselection: select-clusters (%d) must be in 1..clusters (%d)", n_select,
                 n_clusters);
-    if (s->d_cm && s->ps_clusters == n_clusters && s->ps_iterations == iterations) {
+    if (s->d_cm.get() && s->ps_clusters == n_clusters && s->ps_iterations == iterations) {
         s->ps_select = n_select;
         return AMX_OK;
     }
@@ -746,19 +699,17 @@ int amx_internal_gmm_simd_presel_build(void* p, amx_ctx* ctx, int n_clusters, in
         }
     }
     AMX_HIP(hipSetDevice(ctx->device));
-    hipFree(s->d_cm);
-    hipFree(s->d_cluster_of);
-    s->d_cm         = nullptr;
-    s->d_cluster_of = nullptr;
-    AMX_HIP(hipMalloc((void**)&s->d_cm, s->h_cm.size()));
-    AMX_HIP(hipMalloc((void**)&s->d_cluster_of, std::max<size_t>(nk, 1) * 4));
+    s->d_cm.release();  // (a failed build leaves no tables: the test above rebuilds)
+    s->d_cluster_of.release();
+    AMX_TRY(s->d_cm.reserve(s->h_cm.size()));
+    AMX_TRY(s->d_cluster_of.reserve(std::max<size_t>(nk, 1)));
     std::vector<double> sums((size_t)n_clusters * dim);
     std::vector<size_t> cnt(n_clusters);
     for (int it = 0; it < iterations; ++it) {
-        AMX_HIP(hipMemcpyAsync(s->d_cm, s->h_cm.data(), s->h_cm.size(), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(simd_presel_assign_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, s->d_qmean, s->d_k_dens,
-                           (int)nk, dim, s->d_cm, n_clusters, s->d_cluster_of);
-        AMX_HIP(hipMemcpyAsync(s->h_cluster_of.data(), s->d_cluster_of, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+        AMX_HIP(hipMemcpyAsync(s->d_cm.get(), s->h_cm.data(), s->h_cm.size(), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(simd_presel_assign_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, s->d_qmean.get(), s->d_k_dens.get(),
+                           (int)nk, dim, s->d_cm.get(), n_clusters, s->d_cluster_of.get());
+        AMX_HIP(hipMemcpyAsync(s->h_cluster_of.data(), s->d_cluster_of.get(), nk * 4, hipMemcpyDeviceToHost, ctx->stream));
         AMX_HIP(hipStreamSynchronize(ctx->stream));
         std::fill(sums.begin(), sums.end(), 0.0);  // updateClusterMeans: f64 sums in density order / count -> u8 (truncation)
         std::fill(cnt.begin(), cnt.end(), (size_t)0);
@@ -775,8 +726,8 @@ int amx_internal_gmm_simd_presel_build(void* p, amx_ctx* ctx, int n_clusters, in
                 for (int i = 0; i < dim; ++i)
                     s->h_cm[(size_t)c * dim + i] = (unsigned char)(sums[(size_t)c * dim + i] / (double)cnt[c]);
     }
-    AMX_HIP(hipMemcpy(s->d_cm, s->h_cm.data(), s->h_cm.size(), hipMemcpyHostToDevice));
-    AMX_HIP(hipMemcpy(s->d_cluster_of, s->h_cluster_of.data(), nk * 4, hipMemcpyHostToDevice));
+    AMX_HIP(hipMemcpy(s->d_cm.get(), s->h_cm.data(), s->h_cm.size(), hipMemcpyHostToDevice));
+    AMX_HIP(hipMemcpy(s->d_cluster_of.get(), s->h_cluster_of.data(), nk * 4, hipMemcpyHostToDevice));
     s->ps_clusters   = n_clusters;
     s->ps_select     = n_select;
     s->ps_iterations = iterations;
@@ -806,21 +757,11 @@ int amx_internal_gmm_simd_presel_score(void* p, amx_ctx* ctx, const float* feats
     int chunk = (int)std::min<size_t>((size_t)T, std::max<size_t>(256, ((size_t)64 << 20) / (size_t)s->n_dens / 256 * 256));
     chunk     = (chunk + 255) / 256 * 256;
     const size_t need = (size_t)s->n_dens * chunk;
-    if (need > s->dist_cap) {
-        hipFree(s->d_dist);
-        s->d_dist   = nullptr;
-        s->dist_cap = 0;
-        AMX_HIP(hipMalloc((void**)&s->d_dist, need * 4));
-        s->dist_cap = need;
-    }
+    AMX_TRY(s->d_dist.reserve(need));
     if (chunk > s->ps_cap_T) {
-        hipFree(s->d_cdist);
-        hipFree(s->d_masks);
-        s->d_cdist  = nullptr;
-        s->d_masks  = nullptr;
         s->ps_cap_T = 0;
-        AMX_HIP(hipMalloc((void**)&s->d_cdist, (size_t)256 * chunk * 4));
-        AMX_HIP(hipMalloc((void**)&s->d_masks, (size_t)(chunk / 64) * 256 * 8));
+        AMX_TRY(s->d_cdist.reserve((size_t)256 * chunk));
+        AMX_TRY(s->d_masks.reserve((size_t)(chunk / 64) * 256));
         s->ps_cap_T = chunk;
     }
     for (int t0 = 0; t0 < T; t0 += chunk) {
@@ -831,17 +772,17 @@ int amx_internal_gmm_simd_presel_score(void* p, amx_ctx* ctx, const float* feats
             dt /= 2;
         {
             ScopedKernelTimer timer(ctx, "gmm_simd_dist");
-            hipLaunchKernelGGL(simd_dist_kernel, dim3((s->n_dens + dt - 1) / dt, fblocks), dim3(256), 0, st, x, s->d_isr, s->d_qmean, s->d_d_cov,
-                               s->d_dist, Tc, chunk, s->dim, s->n_dens, dt);
+            hipLaunchKernelGGL(simd_dist_kernel, dim3((s->n_dens + dt - 1) / dt, fblocks), dim3(256), 0, st, x, s->d_isr.get(), s->d_qmean.get(), s->d_d_cov.get(),
+                               s->d_dist.get(), Tc, chunk, s->dim, s->n_dens, dt);
         }
         ScopedKernelTimer timer(ctx, "gmm_simd");
-        hipLaunchKernelGGL(simd_presel_select_kernel, dim3((Tc + 63) / 64), dim3(64), (size_t)s->dim * 64, st, x, s->d_isr, Tc, chunk, s->dim,
-                           s->d_cm, s->ps_clusters, s->ps_select, s->d_cdist, s->d_masks);
+        hipLaunchKernelGGL(simd_presel_select_kernel, dim3((Tc + 63) / 64), dim3(64), (size_t)s->dim * 64, st, x, s->d_isr.get(), Tc, chunk, s->dim,
+                           s->d_cm.get(), s->ps_clusters, s->ps_select, s->d_cdist.get(), s->d_masks.get());
         int mt = 16;
         while (mt > 1 && (long)((s->n_mix + mt - 1) / mt) * fblocks < 1024)
             mt /= 2;
-        hipLaunchKernelGGL(simd_presel_combine_kernel, dim3((s->n_mix + mt - 1) / mt, fblocks), dim3(256), 0, st, s->d_dist, s->d_cst[1],
-                           s->d_mix_off, s->d_k_dens, s->d_cluster_of, s->d_masks, s->ps_clusters, scores_dev + (size_t)t0 * s->n_mix, Tc, chunk,
+        hipLaunchKernelGGL(simd_presel_combine_kernel, dim3((s->n_mix + mt - 1) / mt, fblocks), dim3(256), 0, st, s->d_dist.get(), s->d_cst[1].get(),
+                           s->d_mix_off.get(), s->d_k_dens.get(), s->d_cluster_of.get(), s->d_masks.get(), s->ps_clusters, scores_dev + (size_t)t0 * s->n_mix, Tc, chunk,
                            s->n_mix, mt, scale);
     }
     AMX_HIP(hipGetLastError());

@@ -42,6 +42,7 @@
 // kernel -- each table element is then used once instead of 16 times from registers.  The kernel counts the survivors; the host
 // reads the count of earlier calls and goes back to gmm_tied_tile_kernel while the surviving fraction is high (gmm.hip).
 #include "common.hpp"
+#include "gmm_internal.hpp"
 
 #include <cfloat>
 #include <cstring>
@@ -85,8 +86,8 @@ __global__ __launch_bounds__(256) void tied_transpose_kernel(const float* __rest
     }
 }
 
-// The frame's closest density of every residue class k mod 32, for tied_bound_kernel (any subset gives a valid bound; this one needs
-// no selection).  One workgroup per frame; nd / nk [T][32].
+// The frame's closest density of every residue class k mod kTiedNear, for tied_bound_kernel (any subset gives a valid bound; this one
+// needs no selection).  One workgroup per frame; g_near [T][kTiedNear] u64 keys: distance bits in the high half, list position in the low.
 constexpr int kTiedNearThreads = 1024;
 static_assert(kTiedNearThreads % kTiedNear == 0 && kTiedNear >= 8 && kTiedNear <= 128, "a thread of tied_near_kernel stays inside one residue class");
 
@@ -737,15 +738,14 @@ static unsigned short tied_bf16_up(float v) {
     return (unsigned short)((u >> 16) + ((u >> 31) ? 0u : 1u));
 }
 
-extern "C" int amx_internal_gmm_tied_create(int K, int n_mix, int mix_pad, const float* ahat_t_host, float** d_amin, unsigned short** d_aup) {
+extern "C" int amx_internal_gmm_tied_create(int K, int n_mix, int mix_pad, const float* ahat_t_host, amx::DevBuf<float>& d_amin,
+                                            amx::DevBuf<unsigned short>& d_aup) {
     const int          n_tiles = mix_pad / 64, Kpad = (K + 63) & ~63;
     {
         std::vector<unsigned short> up((size_t)K * mix_pad);
         for (size_t i = 0; i < up.size(); ++i)
             up[i] = tied_bf16_up(ahat_t_host[i]);
-        *d_aup = nullptr;
-        AMX_HIP(hipMalloc((void**)d_aup, up.size() * 2));
-        AMX_HIP(hipMemcpy(*d_aup, up.data(), up.size() * 2, hipMemcpyHostToDevice));
+        AMX_TRY(d_aup.upload(up.data(), up.size()));
     }
     std::vector<float> amin((size_t)(n_tiles + 1) * Kpad, __builtin_inff());
     for (int k = 0; k < K; ++k)
@@ -763,10 +763,7 @@ extern "C" int amx_internal_gmm_tied_create(int K, int n_mix, int mix_pad, const
     for (int j = 0; j < n_tiles; ++j)
         for (int k = 0; k < K; ++k)
             amin[t0 + (size_t)k * tiles_pad + j] = amin[(size_t)j * Kpad + k];
-    *d_amin = nullptr;
-    AMX_HIP(hipMalloc((void**)d_amin, amin.size() * sizeof(float)));
-    AMX_HIP(hipMemcpy(*d_amin, amin.data(), amin.size() * sizeof(float), hipMemcpyHostToDevice));
-    return AMX_OK;
+    return d_amin.upload(amin.data(), amin.size());
 }
 
 namespace {
