@@ -16,10 +16,11 @@ def utterance_lengths(n_utt, seed, lo_s=5.0, hi_s=15.0, fs=16000.0):
     return np.rint(rng.uniform(lo_s, hi_s, n_utt) * fs).astype(np.int64)
 
 
-def gmm_cart(n_mix, k_lo, k_hi, dim, seed, pooled=True):
-    """CART-style model: every mixture owns its densities (k_lo..k_hi each)."""
+def gmm_cart(n_mix, k_lo, k_hi, dim, seed, pooled=True, ks=None):
+    """CART-style model: every mixture owns its densities (k_lo..k_hi each, or exactly ks[m] when ks is given)."""
     rng = np.random.Generator(np.random.PCG64(seed))
-    ks = rng.integers(k_lo, k_hi + 1, n_mix)
+    ks = rng.integers(k_lo, k_hi + 1, n_mix) if ks is None else np.asarray(ks, np.int64)
+    assert len(ks) == n_mix
     off = np.zeros(n_mix + 1, np.uint32)
     off[1:] = np.cumsum(ks)
     nd = int(off[-1])
@@ -51,6 +52,34 @@ def gmm_tied(n_mix, n_dens, dim, seed, pooled=True, alpha=0.1, k_per_mix=None):
                 dens_mean=np.arange(n_dens, dtype=np.uint32),
                 dens_cov=(np.zeros(n_dens, np.uint32) if pooled else np.arange(n_dens, dtype=np.uint32)),
                 means=means, variances=variances)
+
+
+def gmm_retie(model, seed, cov=None, n_mean=None):
+    """A copy of `model` with its parameter tying changed -- what the index tables dens_mean / dens_cov allow and neither generator
+    above produces:
+      cov = "mixture"   one covariance per mixture (1 < n_cov < n_dens; CART models, whose densities belong to one mixture each)
+      cov = G (int)     G covariances, every one shared by several densities spread over the model (any model)
+      n_mean = N        N < n_dens mean rows: several densities, usually of different mixtures, point to the same row
+    Variances are drawn anew for the new rows; the first n_mean mean rows are kept."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    m = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in model.items()}
+    n_dens, dim = len(m["dens_mean"]), int(m["dim"])
+
+    def spread(n_rows):   # every row used, by n_dens / n_rows densities each, in no particular order
+        assert 0 < n_rows <= n_dens
+        return rng.permutation(np.arange(n_dens) % n_rows).astype(np.uint32)
+
+    if cov is not None:
+        if isinstance(cov, str):
+            assert cov == "mixture" and np.array_equal(m["dens_index"], np.arange(n_dens)), "one covariance per mixture needs a CART model"
+            m["dens_cov"] = np.repeat(np.arange(len(m["mix_offsets"]) - 1, dtype=np.uint32), np.diff(m["mix_offsets"].astype(np.int64)))
+        else:
+            m["dens_cov"] = spread(int(cov))
+        m["variances"] = rng.uniform(0.5, 2.0, (int(m["dens_cov"].max()) + 1, dim)).astype(np.float32)
+    if n_mean is not None:
+        m["dens_mean"] = spread(int(n_mean))
+        m["means"] = np.ascontiguousarray(m["means"][:int(n_mean)])
+    return m
 
 
 def ffnn(dims, seed, act=1):
