@@ -595,6 +595,43 @@ void amx_gmm_estimate_cfg_default(amx_gmm_estimate_cfg* cfg);
 int  amx_gmm_estimate(const amx_gmm_model* topology, const double* acc_host, const amx_gmm_estimate_cfg* cfg /* NULL: defaults */,
                       amx_mixture_set** out);
 
+/* ------------------------------------------------------------------ LDA estimation: scatter matrices */
+
+/* Signal::ScatterMatricesEstimator (src/Signal/ScatterEstimator.cc), the corpus pass behind the matrix that amx_matrix_multiply_dev
+ * applies: Speech::TextDependentScatterMatricesEstimator::processAlignedFeature hands it every aligned frame with the emission
+ * index of the alignment as its class.  The accumulator is ONE flat f64 buffer,
+ *   [dim (dim + 1) / 2 square sums, lower triangle, row-major] [n_classes x dim class vector sums] [n_classes class counts]
+ * -- amx_scatter_accumulator_size() doubles, 0 for a shape outside 1 <= dim <= 1024, n_classes >= 1 -- which is the order of the
+ * accumulator file behind its two u32 headers (ScatterEstimator.cc:95-106, 359-376), so that data-parallel ranks combine with the one
+ * amx_comm_all_reduce_f64_dev they already issue (the reference: `combine-scatter-matrix-accus`, ScatterEstimator.cc:407-417). */
+long amx_scatter_accumulator_size(int dim, int n_classes);
+/* ScatterMatricesEstimator::accumulate(classIndex, x, weight) (ScatterEstimator.cc:227-234 -> :44-55) for T frames
+ * feats_dev[t * in_ld + 0 .. dim) of class class_dev[t] and f32 weight weight_dev[t] (NULL: 1), ADDED into acc_dev:
+ *   square[i][j] += (f64)((x_i * x_j) * w) for j <= i   both products in f32, in that order, then widened
+ *   sums[c][i]   += (f64)(x_i * w)                      x * weight is a Math::Vector<f32>
+ *   counts[c]    += (f64)w
+ * Nothing here can be contracted, so both amx_set_contract settings give the same bits.  A frame whose class is >= n_classes
+ * (0xffffffff: no label) is skipped; a NaN reaches the sums it touches.  in_ld >= dim; sums across workgroups are f64 atomics
+ * (order undefined; exact where no addition rounds).  AMX_ERR_INVALID with a named amx_last_error for a bad argument. */
+int amx_scatter_accumulate_dev(amx_ctx* ctx, const float* feats_dev, int in_ld, long T, int dim, const uint32_t* class_dev, int n_classes,
+                               const float* weight_dev /* NULL: 1 */, double* acc_dev);
+/* The accumulator file of ScatterMatricesEstimator::write / read (ScatterEstimator.cc:79-106, 337-376; `new-accumulator-file`,
+ * `old-accumulator-file`, `accumulator-files-to-combine`): u32 dim, the triangle, u32 nClasses, sums, counts; little endian.
+ * acc_host is the flat buffer in host memory; read allocates it (release with amx_free). */
+int amx_scatter_accumulator_write(int dim, int n_classes, const double* acc_host, const char* path);
+int amx_scatter_accumulator_read(const char* path, int* dim, int* n_classes, double** acc_host /* amx_free */);
+/* ScatterMatricesEstimator::finalize (ScatterEstimator.cc:245-285, 72-77, 287-292; hh:141-143), host, f64, the reference's order of
+ * operations: total-mean part (s_i s_j) / N, class-mean part sum over classes with n_c > 0 of (s_ci s_cj) / n_c,
+ * between = class-mean - total-mean, within = square - class-mean, total = square - total-mean, each times 1 / N when normalize
+ * (`shall-normalize`); the square sum's upper triangle mirrors its lower.  N = 0: AMX_ERR_INVALID ("No observation has been seen.").
+ * The eigenvalue step (Signal::LinearDiscriminantAnalysis) stays with RASR: write the matrices with amx_matrix_write_f64. */
+int amx_scatter_finalize(int dim, int n_classes, const double* acc_host, int normalize, double* between, double* within,
+                         double* total /* each dim x dim row-major, nullable */);
+/* Binary Math::Matrix<f64> (Math/Matrix.hh:560-574; Math/Module.cc:35 registers "bin" for Matrix<f64>): the f64 twins of
+ * amx_nn_matrix_read / amx_nn_matrix_write, same layout, an optional "bin:" prefix.  *data is malloc'ed; release it with amx_free. */
+int amx_matrix_read_f64(const char* path, int* rows, int* cols, double** data);
+int amx_matrix_write_f64(const char* path, int rows, int cols, const double* data);
+
 /* ------------------------------------------------------------------ mixture-set text files (.pms) */
 
 /* Reader / writer of RASR's text mixture-set format, "#Version: 2.0" (Mm/MixtureSet.cc:141-216,

@@ -9,6 +9,7 @@ same reference interfaces for tests and benchmarks:
   VoicednessExtractor  voicedness.flow network (autocorrelation by FFT, maximal peak value)
   GmmFeatureScorer     Mm::FeatureScorer over a Mm::MixtureSet (diagonal-maximum / diagonal-sum)
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
+  ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
   FileArchive          Core::FileArchive + Flow cache entries (feature caches between jobs; host IO)
 """
 import ctypes as C
@@ -22,6 +23,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
+           "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -973,6 +975,78 @@ def read_nn_matrix(path):
 def write_nn_matrix(path, m):
     m = np.ascontiguousarray(m, dtype=np.float32)
     _lib.check(_lib.lib().amx_nn_matrix_write(path.encode(), m.shape[0], m.shape[1], m.ctypes.data))
+
+
+def read_matrix_f64(path):
+    """binary Math::Matrix<f64> (a scatter matrix as RASR's LDA tool reads it, optional "bin:" prefix) -> numpy [rows, cols]"""
+    L = _lib.lib()
+    r, c, p = C.c_int(), C.c_int(), C.c_void_p()
+    _lib.check(L.amx_matrix_read_f64(os.fsencode(path), C.byref(r), C.byref(c), C.byref(p)))
+    try:
+        n = r.value * c.value
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(max(n, 1),))[:n].copy()
+        return a.reshape(r.value, c.value)
+    finally:
+        L.amx_free(p)
+
+
+def write_matrix_f64(path, m):
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    _lib.check(_lib.lib().amx_matrix_write_f64(os.fsencode(path), m.shape[0], m.shape[1], m.ctypes.data))
+
+
+class ScatterMatricesEstimator:
+    """Signal::ScatterMatricesEstimator: the flat f64 accumulator [dim (dim + 1) / 2 square sums (lower triangle) | n_classes x dim class
+    sums | n_classes counts], its corpus pass on the device, its file and its finalize step.  ctx may be None for host-only use
+    (files, finalize)."""
+
+    def __init__(self, ctx, dim, n_classes):
+        self.L = _lib.lib()
+        self.ctx, self.dim, self.n_classes = ctx, int(dim), int(n_classes)
+        if self.accumulator_size() == 0:
+            raise ValueError("ScatterMatricesEstimator: dim %d must lie in [1, 1024] and n_classes %d be positive" % (self.dim, self.n_classes))
+
+    def accumulator_size(self):
+        return int(self.L.amx_scatter_accumulator_size(self.dim, self.n_classes))
+
+    def accumulate_dev(self, feats_dev, in_ld, T, class_dev, acc_dev, weight_dev=None):
+        """add T frames feats_dev[t * in_ld + 0 .. dim) (f32) of class class_dev[t] (u32; >= n_classes: skipped) and weight
+        weight_dev[t] (f32, None: 1) into the flat accumulator acc_dev (f64, accumulator_size() entries)"""
+        if self.ctx is None:
+            raise RuntimeError("ScatterMatricesEstimator.accumulate_dev: created without a context")
+        _lib.check(self.L.amx_scatter_accumulate_dev(self.ctx.h, _ptr(feats_dev), int(in_ld), int(T), self.dim, _ptr(class_dev), self.n_classes,
+                                                     _ptr(weight_dev), _ptr(acc_dev)))
+
+    def _host(self, acc_host):
+        a = np.ascontiguousarray(acc_host, dtype=np.float64)
+        if a.size != self.accumulator_size():
+            raise ValueError("accumulator has %d entries, expected %d" % (a.size, self.accumulator_size()))
+        return a
+
+    def finalize(self, acc_host, normalize=False):
+        """(between-class, within-class, total) scatter matrices, each f64 [dim, dim]; normalize = `shall-normalize`"""
+        a = self._host(acc_host)
+        out = [np.zeros((self.dim, self.dim), np.float64) for _ in range(3)]
+        _lib.check(self.L.amx_scatter_finalize(self.dim, self.n_classes, a.ctypes.data, 1 if normalize else 0, *[m.ctypes.data for m in out]))
+        return tuple(out)
+
+    def write(self, acc_host, path):
+        """flat accumulator (numpy, host) -> the accumulator file of ScatterMatricesEstimator::write (`new-accumulator-file`)"""
+        a = self._host(acc_host)
+        _lib.check(self.L.amx_scatter_accumulator_write(self.dim, self.n_classes, a.ctypes.data, os.fsencode(path)))
+
+    @staticmethod
+    def read(path):
+        """accumulator file -> (dim, n_classes, flat accumulator)"""
+        L = _lib.lib()
+        d, n, p = C.c_int(), C.c_int(), C.c_void_p()
+        _lib.check(L.amx_scatter_accumulator_read(os.fsencode(path), C.byref(d), C.byref(n), C.byref(p)))
+        try:
+            size = int(L.amx_scatter_accumulator_size(d.value, n.value))
+            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(size,)).copy()
+        finally:
+            L.amx_free(p)
+        return d.value, n.value, a
 
 
 def layer_from_parameters(params, has_bias=True):

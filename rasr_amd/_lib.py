@@ -183,6 +183,13 @@ SIGNATURES = {
     "amx_gmm_accumulate_u8_dev": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "amx_gmm_accumulate_dev": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "amx_gmm_accumulate_weighted_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "amx_scatter_accumulator_size": (C.c_long, [C.c_int, C.c_int]),
+    "amx_scatter_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_long, C.c_int, _P, C.c_int, _P, _P]),
+    "amx_scatter_accumulator_write": (C.c_int, [C.c_int, C.c_int, _P, C.c_char_p]),
+    "amx_scatter_accumulator_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
+    "amx_scatter_finalize": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "amx_matrix_read_f64": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
+    "amx_matrix_write_f64": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P]),
     "amx_gmm_estimate_cfg_default": (None, [C.POINTER(GmmEstimateCfg)]),
     "amx_gmm_estimate": (C.c_int, [C.POINTER(GmmModel), _P, C.POINTER(GmmEstimateCfg), C.POINTER(_P)]),
     "amx_gmm_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),

@@ -77,6 +77,47 @@ int amx_nn_matrix_write(const char* path, int rows, int cols, const float* data)
     return AMX_OK;
 }
 
+// ---- Math::Matrix<f64> in the same binary layout (Math/Module.cc:35 registers "bin" for Matrix<f64>): what RASR's LDA tool reads
+// as between- / within-class / total scatter matrix
+int amx_matrix_read_f64(const char* path, int* rows, int* cols, double** data) {
+    AMX_REQUIRE(path && rows && cols && data, AMX_ERR_INVALID, "amx_matrix_read_f64: NULL argument");
+    *data = nullptr;
+    const char* p = strncmp(path, "bin:", 4) == 0 ? path + 4 : path;
+    FILE*       f = fopen(p, "rb");
+    AMX_REQUIRE(f, AMX_ERR_INVALID, "amx_matrix_read_f64: cannot open '%s'", p);
+    uint32_t nr = 0, nc = 0, n2 = 0;
+    bool     ok = read_u32(f, &nr) && read_u32(f, &nc) && read_u32(f, &n2) && n2 == nr && (uint64_t)nr * nc < (1ull << 30);
+    double*  d  = ok ? (double*)malloc(std::max<size_t>((size_t)nr * nc, 1) * sizeof(double)) : nullptr;
+    ok          = ok && d != nullptr;
+    for (uint32_t r = 0; ok && r < nr; ++r) {
+        uint32_t len = 0;
+        ok           = read_u32(f, &len) && len == nc && fread(d + (size_t)r * nc, 8, nc, f) == nc;
+    }
+    fclose(f);
+    if (!ok) {
+        free(d);
+        amx::set_error("amx_matrix_read_f64: '%s' is not a binary Math::Matrix<f64>", p);
+        return AMX_ERR_INVALID;
+    }
+    *rows = (int)nr;
+    *cols = (int)nc;
+    *data = d;
+    return AMX_OK;
+}
+
+int amx_matrix_write_f64(const char* path, int rows, int cols, const double* data) {
+    AMX_REQUIRE(path && rows >= 0 && cols >= 0 && (data || rows * cols == 0), AMX_ERR_INVALID, "amx_matrix_write_f64: bad argument");
+    const char* p = strncmp(path, "bin:", 4) == 0 ? path + 4 : path;
+    FILE*       f = fopen(p, "wb");
+    AMX_REQUIRE(f, AMX_ERR_INVALID, "amx_matrix_write_f64: cannot open '%s'", p);
+    bool ok = write_u32(f, (uint32_t)rows) && write_u32(f, (uint32_t)cols) && write_u32(f, (uint32_t)rows);
+    for (int r = 0; ok && r < rows; ++r)
+        ok = write_u32(f, (uint32_t)cols) && fwrite(data + (size_t)r * cols, 8, (size_t)cols, f) == (size_t)cols;
+    ok = (fclose(f) == 0) && ok;
+    AMX_REQUIRE(ok, AMX_ERR_INVALID, "amx_matrix_write_f64: write to '%s' failed", p);
+    return AMX_OK;
+}
+
 int amx_nn_layer_from_parameters(const float* params, int rows, int cols, int has_bias, float* W, float* bias) {
     AMX_REQUIRE(params && W && rows > 0 && cols > (has_bias ? 1 : 0), AMX_ERR_INVALID, "amx_nn_layer_from_parameters: bad argument");
     const int in = cols - (has_bias ? 1 : 0);
