@@ -632,6 +632,79 @@ int amx_scatter_finalize(int dim, int n_classes, const double* acc_host, int nor
 int amx_matrix_read_f64(const char* path, int* rows, int* cols, double** data);
 int amx_matrix_write_f64(const char* path, int rows, int cols, const double* data);
 
+/* ------------------------------------------------------------------ histogram normalisation (per-speaker): estimation, files, apply */
+
+/* amx_histogram is one Signal::HistogramVector<f32> (Signal/Histogram.hh:85-103): `dim` histograms of one bucket size (the estimator's
+ * `bucket-size`, 0.0002 by default, Speech/HistogramEstimator.cc:19-20), each a LookupTable that grows (Signal/LookupTable.hh:50-66).
+ * State after any number of calls, per dimension: offset = -min k, size = max k - min k + 1 over everything accumulated, where
+ * k = (s32)round(x / bucket_size) (LookupTable.hh:69-72: f32 division, round half away from zero), grow = true, value[b] = number of
+ * frames in bucket b as f32.  The reference adds 1.0f in f32 (Histogram.hh:46-48), so a value stops at 16 777 216; the handle counts in
+ * u32 and exports (float)min(count, 2^24).  A handle takes at most 2^32 - 1 frames; a call that would pass that is refused.
+ * A frame holding a NaN, an infinity or a value with |x / bucket_size| >= 2^30 makes accumulate return AMX_ERR_INVALID and add NOTHING
+ * of that call: the reference's cast to s32 is undefined there.  Weights are not taken (the estimator passes 1, HistogramEstimator.cc).
+ * A call holds the frames of ONE corpus key.  ctx may be NULL: a host-only handle for files and tables (amx_histogram_attach gives it a
+ * context later).  Nothing here depends on amx_set_contract: no multiply of this arithmetic feeds an add. */
+typedef struct amx_histogram amx_histogram;
+typedef struct {
+    int   dim;
+    float bucket_size;
+    int   frozen;          /* read from a file whose values are not counts: serves tables, refuses accumulate */
+    int   lds_max_buckets; /* a dimension whose window has at most this many buckets counts in a workgroup-private LDS table ... */
+    int   lds_capacity;    /* ... while the windows of such dimensions, taken in order, fit this many buckets in all; the rest use memory atomics */
+    unsigned long long frames;         /* accumulated so far (after a file: the largest sum of one dimension) */
+    unsigned long long n_lds;          /* (dimension, device call) pairs that counted in LDS */
+    unsigned long long n_global;       /* ... that counted with atomics on memory */
+    unsigned long long n_device_calls; /* amx_histogram_accumulate_dev calls that added frames; each synchronises the stream once */
+} amx_histogram_info;
+int  amx_histogram_create(amx_ctx* ctx /* nullable */, int dim /* 1 .. 4096 */, float bucket_size /* > 0 */, amx_histogram** out);
+void amx_histogram_destroy(amx_histogram* h);
+int  amx_histogram_attach(amx_histogram* h, amx_ctx* ctx);
+int  amx_histogram_describe(const amx_histogram* h, amx_histogram_info* info);
+/* HistogramVector::accumulate (Histogram.hh:107-112) for T frames feats_dev[t * in_ld + 0 .. dim).  Synchronises the context's stream
+ * once (the range of the call's buckets comes back to the host, which grows the tables).  Calls in any split give the same tables. */
+int  amx_histogram_accumulate_dev(amx_histogram* h, const float* feats_dev, int in_ld, long T);
+/* The same on the host, in plain C++ (a handle without a context; small corrections to a histogram read from a file). */
+int  amx_histogram_accumulate(amx_histogram* h, const float* feats_host, int in_ld, long T);
+/* HistogramVector::write / read (Histogram.hh:122-135; LookupTable::write / read, LookupTable.hh:298-319; Core::BinaryOutputStream, little
+ * endian): u32 n | n x (f32 bucketSize, s32 offset, one byte grow (0xff = true, Core/BinaryStream.cc:95-103), u32 size, f32 values[size]).  This is the per-key file of the
+ * estimator's object cache (Core/ObjectCache.hh:488-517) and the training-histogram file of the normalisation node.  A file whose values
+ * are all whole numbers <= 2^24 in growing tables of one bucket size resumes counting; any other file loads frozen. */
+int  amx_histogram_write(const amx_histogram* h, const char* path);
+int  amx_histogram_read(const char* path, amx_histogram** out);
+/* One dimension: the table itself, Histogram::getCdf (Histogram.hh:73-80: sequential f32 partial sums divided by the sequential f32 sum;
+ * an empty histogram is AMX_ERR_INVALID), Histogram::percentile (Histogram.hh:56-64).  values nullable: ask for *size first. */
+int  amx_histogram_table(const amx_histogram* h, int d, float* bucket_size, int* offset, int* size, float* values);
+int  amx_histogram_cdf(const amx_histogram* h, int d, float* bucket_size, int* offset, int* size, float* values);
+int  amx_histogram_percentile(const amx_histogram* h, int d, float percent, float* value);
+
+/* amx_histnorm is Signal::HistogramNormalization (Signal/HistogramNormalization.hh:26-68): inverse CDFs of the training histograms, test
+ * CDFs per corpus key, out[i] = inverse_i[ cdf_i[ in[i] ] ] (HistogramNormalization.cc:68-75).
+ * One training histogram: setTrainingHistograms(histograms, bucketSize) (HistogramNormalization.cc:24-34).  Several: the interpolated form
+ * (:36-60) -- normalizeSurface, *= scale, += into tables of the minimal bucket size -- built by amx_histnorm_set_scales from the
+ * n_train - 1 scales of the node's scale ports; the first scale is 1 - their sum (normalizeScales, :91-93) and a scale outside [0, 1] is
+ * AMX_ERR_INVALID (areScalesWellDefined, :77-84).  Until then such a handle cannot apply (AMX_ERR_STATE).  probability_bucket_size = 0
+ * selects LookupTable::proposeBucketSizeForInverse (LookupTable.hh:264-271); the inverse follows LookupTable::getInverse (:239-262).
+ * The training histograms are copied: they may be destroyed afterwards.  ctx may be NULL (tables only). */
+typedef struct amx_histnorm amx_histnorm;
+int  amx_histnorm_create(amx_ctx* ctx /* nullable */, int n_train, const amx_histogram* const* train, float probability_bucket_size, amx_histnorm** out);
+void amx_histnorm_destroy(amx_histnorm* h);
+int  amx_histnorm_set_scales(amx_histnorm* h, const float* scales /* [n_train - 1] */);
+/* setTestHistograms (HistogramNormalization.cc:62-66) for one more corpus key; *key is its number in amx_histnorm_apply_dev.  A histogram
+ * of another dimension is AMX_ERR_INVALID (HistogramNormalizationNode::init, :176-181), an empty one too. */
+int  amx_histnorm_add_key(amx_histnorm* h, const amx_histogram* test, int* key);
+int  amx_histnorm_n_keys(const amx_histnorm* h);
+int  amx_histnorm_inverse_cdf(const amx_histnorm* h, int d, float* bucket_size, int* offset, int* size, float* values /* nullable */);
+int  amx_histnorm_test_cdf(const amx_histnorm* h, int key, int d, float* bucket_size, int* offset, int* size, float* values /* nullable */);
+/* apply() on frames [frame_offsets[0], frame_offsets[n_seg]) of in_dev, one launch; segment s = frames [frame_offsets[s],
+ * frame_offsets[s + 1]) uses key key_of_segment[s] (both lists on the host).  in_dev == out_dev is allowed; columns >= dim are not touched.
+ * Per element: b = (s32)round(x / bs_test) + off_test, p = cdf[b], b2 = (s32)round(p / bs_inv) + off_inv, out = inverse[b2]
+ * (LookupTable.hh:69-72, 108-112).  A bucket outside its table is undefined in the reference's release build (the `ensure_` of :110 is
+ * compiled out); here it is the nearest end bucket, which is what LookupTable::insert does on a table that may not grow (:178-202).
+ * clamped (nullable, host): [0] = elements clamped at the test CDF, [1] = at the inverse; asking for it synchronises the stream.
+ * A NaN input gives a NaN output and counts in clamped[0]. */
+int  amx_histnorm_apply_dev(amx_histnorm* h, int n_seg, const long* frame_offsets, const int* key_of_segment, const float* in_dev, int in_ld,
+                            float* out_dev, int out_ld, unsigned long long clamped[2]);
+
 /* ------------------------------------------------------------------ mixture-set text files (.pms) */
 
 /* Reader / writer of RASR's text mixture-set format, "#Version: 2.0" (Mm/MixtureSet.cc:141-216,

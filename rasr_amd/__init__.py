@@ -23,7 +23,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
-           "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64",
+           "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1047,6 +1047,130 @@ class ScatterMatricesEstimator:
         finally:
             L.amx_free(p)
         return d.value, n.value, a
+
+
+def _lookup_table(fn, *head):
+    """(bucket_size, offset, values f32) of one table through an amx_*_table style getter (size first, then the values)"""
+    bs, off, n = C.c_float(), C.c_int(), C.c_int()
+    _lib.check(fn(*head, C.byref(bs), C.byref(off), C.byref(n), None))
+    v = np.zeros(n.value, np.float32)
+    _lib.check(fn(*head, C.byref(bs), C.byref(off), C.byref(n), v.ctypes.data))
+    return np.float32(bs.value), off.value, v
+
+
+class HistogramEstimator:
+    """Speech::HistogramEstimator for ONE corpus key: a Signal::HistogramVector<f32> of `dim` histograms (amx_histogram).  ctx may be
+    None for host-only use (files, tables, accumulate on the host)."""
+
+    def __init__(self, ctx, dim, bucket_size=0.0002, _handle=None):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        if _handle is None:
+            _handle = C.c_void_p()
+            _lib.check(self.L.amx_histogram_create(ctx.h if ctx is not None else None, int(dim), float(bucket_size), C.byref(_handle)))
+        self.h = _handle
+        self.dim = self.describe()["dim"]
+
+    def close(self):
+        if self.h:
+            self.L.amx_histogram_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def describe(self):
+        info = _lib.HistogramInfo()
+        _lib.check(self.L.amx_histogram_describe(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def attach(self, ctx):
+        _lib.check(self.L.amx_histogram_attach(self.h, ctx.h))
+        self.ctx = ctx
+
+    def accumulate_dev(self, feats_dev, in_ld, T):
+        """add T frames feats_dev[t * in_ld + 0 .. dim) (f32, device) of this key"""
+        _lib.check(self.L.amx_histogram_accumulate_dev(self.h, _ptr(feats_dev), int(in_ld), int(T)))
+
+    def accumulate(self, feats):
+        """the same for a host array [T, dim], in plain C++"""
+        x = np.ascontiguousarray(feats, dtype=np.float32)
+        _lib.check(self.L.amx_histogram_accumulate(self.h, x.ctypes.data, x.shape[1] if x.ndim == 2 else self.dim, x.size // max(1, x.shape[-1])))
+
+    def table(self, d):
+        """(bucket_size, offset, values) of dimension d"""
+        return _lookup_table(self.L.amx_histogram_table, self.h, int(d))
+
+    def cdf(self, d):
+        return _lookup_table(self.L.amx_histogram_cdf, self.h, int(d))
+
+    def percentile(self, d, percent):
+        v = C.c_float()
+        _lib.check(self.L.amx_histogram_percentile(self.h, int(d), float(percent), C.byref(v)))
+        return np.float32(v.value)
+
+    def write(self, path):
+        """the per-key file of the histograms cache == a training-histogram file (HistogramVector::write)"""
+        _lib.check(self.L.amx_histogram_write(self.h, os.fsencode(path)))
+
+    @classmethod
+    def read(cls, path, ctx=None):
+        h = C.c_void_p()
+        _lib.check(_lib.lib().amx_histogram_read(os.fsencode(path), C.byref(h)))
+        e = cls(None, 0, _handle=h)
+        if ctx is not None:
+            e.attach(ctx)
+        return e
+
+
+class HistogramNormalization:
+    """Signal::HistogramNormalization (the `signal-histogram-normalization` node's arithmetic): inverse CDFs from one training histogram, or
+    from several interpolated with set_scales; test CDFs per corpus key (add_key); apply_dev normalises all segments in one launch."""
+
+    def __init__(self, ctx, training, probability_bucket_size=0.0):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        training = list(training)
+        arr = (C.c_void_p * len(training))(*[t.h for t in training])
+        h = C.c_void_p()
+        _lib.check(self.L.amx_histnorm_create(ctx.h if ctx is not None else None, len(training), arr, float(probability_bucket_size), C.byref(h)))
+        self.h = h
+        self.dim = training[0].dim
+
+    def close(self):
+        if self.h:
+            self.L.amx_histnorm_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_scales(self, scales):
+        """the scales of training histograms 1 .. n - 1 (the node's `histogram-scale-<i>` ports); histogram 0 gets 1 - their sum"""
+        s = np.ascontiguousarray(scales, dtype=np.float32)
+        _lib.check(self.L.amx_histnorm_set_scales(self.h, s.ctypes.data))
+
+    def add_key(self, test):
+        """the test histograms of one more corpus key -> its number for apply_dev"""
+        k = C.c_int()
+        _lib.check(self.L.amx_histnorm_add_key(self.h, test.h, C.byref(k)))
+        return k.value
+
+    def inverse_cdf(self, d):
+        return _lookup_table(self.L.amx_histnorm_inverse_cdf, self.h, int(d))
+
+    def test_cdf(self, key, d):
+        return _lookup_table(self.L.amx_histnorm_test_cdf, self.h, int(key), int(d))
+
+    def apply_dev(self, frame_offsets, key_of_segment, in_dev, in_ld, out_dev, out_ld, count_clamped=True):
+        """segment s = frames [frame_offsets[s], frame_offsets[s + 1]) with key key_of_segment[s]; in_dev may be out_dev.  Returns
+        (clamped at the test CDF, clamped at the inverse CDF), or None without the synchronisation when count_clamped is False."""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        keys = np.ascontiguousarray(key_of_segment, dtype=np.int32)
+        if len(off) != len(keys) + 1:
+            raise ValueError("HistogramNormalization.apply_dev: %d frame offsets for %d segments" % (len(off), len(keys)))
+        cl = np.zeros(2, np.uint64)
+        _lib.check(self.L.amx_histnorm_apply_dev(self.h, len(keys), off.ctypes.data, keys.ctypes.data, _ptr(in_dev), int(in_ld), _ptr(out_dev), int(out_ld),
+                                                 cl.ctypes.data if count_clamped else None))
+        return (int(cl[0]), int(cl[1])) if count_clamped else None
 
 
 def layer_from_parameters(params, has_bias=True):

@@ -67,6 +67,11 @@ class VoicednessInfo(C.Structure):
                 ("max_position", C.c_int)]
 
 
+class HistogramInfo(C.Structure):
+    _fields_ = [("dim", C.c_int), ("bucket_size", C.c_float), ("frozen", C.c_int), ("lds_max_buckets", C.c_int), ("lds_capacity", C.c_int),
+                ("frames", C.c_ulonglong), ("n_lds", C.c_ulonglong), ("n_global", C.c_ulonglong), ("n_device_calls", C.c_ulonglong)]
+
+
 AMX_XCORR_NONE, AMX_XCORR_UNBIASED_ESTIMATE, AMX_XCORR_UPPER_BOUND = 0, 1, 2
 
 
@@ -190,6 +195,25 @@ SIGNATURES = {
     "amx_scatter_finalize": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "amx_matrix_read_f64": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
     "amx_matrix_write_f64": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P]),
+    "amx_histogram_create": (C.c_int, [_P, C.c_int, C.c_float, C.POINTER(_P)]),
+    "amx_histogram_destroy": (None, [_P]),
+    "amx_histogram_attach": (C.c_int, [_P, _P]),
+    "amx_histogram_describe": (C.c_int, [_P, C.POINTER(HistogramInfo)]),
+    "amx_histogram_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_long]),
+    "amx_histogram_accumulate": (C.c_int, [_P, _P, C.c_int, C.c_long]),
+    "amx_histogram_write": (C.c_int, [_P, C.c_char_p]),
+    "amx_histogram_read": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
+    "amx_histogram_table": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "amx_histogram_cdf": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "amx_histogram_percentile": (C.c_int, [_P, C.c_int, C.c_float, C.POINTER(C.c_float)]),
+    "amx_histnorm_create": (C.c_int, [_P, C.c_int, _P, C.c_float, C.POINTER(_P)]),
+    "amx_histnorm_destroy": (None, [_P]),
+    "amx_histnorm_set_scales": (C.c_int, [_P, _P]),
+    "amx_histnorm_add_key": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
+    "amx_histnorm_n_keys": (C.c_int, [_P]),
+    "amx_histnorm_inverse_cdf": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "amx_histnorm_test_cdf": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "amx_histnorm_apply_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
     "amx_gmm_estimate_cfg_default": (None, [C.POINTER(GmmEstimateCfg)]),
     "amx_gmm_estimate": (C.c_int, [C.POINTER(GmmModel), _P, C.POINTER(GmmEstimateCfg), C.POINTER(_P)]),
     "amx_gmm_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),
