@@ -1506,31 +1506,47 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------ ABI
 
+// AMX_PREC_F16MX: the word the kernels set when a value leaves the f16 range.  Page-locked host memory that the device addresses
+// directly (hipHostMallocMapped), so that the host reads it without a copy.
+struct OverflowWord {
+    unsigned *host = nullptr, *dev = nullptr;
+    OverflowWord()                               = default;
+    OverflowWord(const OverflowWord&)            = delete;
+    OverflowWord& operator=(const OverflowWord&) = delete;
+    ~OverflowWord() {
+        if (host)
+            hipHostFree(host);
+    }
+    int create() {
+        if (hipHostMalloc((void**)&host, 4, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&dev, host, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            amx::set_error("amx_ffnn_create: cannot allocate the overflow flag");
+            return AMX_ERR_DEVICE;
+        }
+        *host = 0;
+        return AMX_OK;
+    }
+};
+
 struct amx_ffnn {
     amx_ctx*           ctx = nullptr;
     int                n_layers = 0, precision = AMX_PREC_BF16;
     std::vector<int>   in, out, act, Kpad, Npad;
-    std::vector<void*> d_W;      // per layer [Npad x Kpad] bf16 or f32
-    std::vector<float*> d_bias;  // per layer [Npad]; output layer has -alpha*logprior folded in
-    // workspace (grown on demand)
-    int    cap_T = 0;
-    void*  d_in  = nullptr;      // packed input [cap_T x Kpad0]
-    void*  d_act[2] = {nullptr, nullptr};
+    std::vector<amx::DevBuf<unsigned char>> d_W;  // per layer [Npad x Kpad] bf16 or f32, [Npad x 2 Kpad] split bf16, or f16mx blocks
+    std::vector<amx::DevBuf<float>> d_bias;       // per layer [Npad]; output layer has -alpha*logprior folded in
+    // workspace, grown to the padded frames of the largest pass so far (ensure_workspace): the packed input [Tpad x Kpad0] and
+    // the hidden activations, in the handle's operand format (operand_bytes)
+    amx::DevBuf<unsigned char> d_in, d_act[2];
     std::vector<float> h_Wout, h_bout;  // output layer [n_emissions x K] f32 and its folded bias (on-demand scorer; uploaded on first use)
     bool   class_mapped = false; // a class-label wrapper reordered the output layer (amx_ffnn_forward_dev wants the network's own order)
-    float* d_rowstat = nullptr;  // softmax top layer: per-frame maximum / sum [2][cap]
-    int    rowstat_cap = 0;
-    float *d_Wout = nullptr, *d_bout = nullptr;
+    amx::DevBuf<float> d_rowstat;  // softmax top layer: per-frame maximum / sum, the sums in the second half
+    amx::DevBuf<float> d_Wout, d_bout;
     int    max_hidden_pad = 0;
     int    largest_layer  = 0;
     int    group_t = -1, group_n = -1;  // super-tile of the XCD-aware tile order
     // fused best-state statistics (amx_ffnn_score_stats_dev): per n-tile arg-min partials [ntn x Tpad]
-    float*    d_part_min = nullptr;
-    unsigned* d_part_idx = nullptr;
-    size_t    part_cap   = 0;
-    float*    cur_part_min = nullptr;
-    unsigned* cur_part_idx = nullptr;
-    int       cur_ntn      = 0;
+    amx::DevBuf<float>    d_part_min;
+    amx::DevBuf<unsigned> d_part_idx;
     // HIP graphs of whole forward passes, for small batches where the 8-10 launches of a pass cost as much as a third of it
     struct GraphKey {
         const void *feats, *scores, *best, *counts, *sum;
@@ -1541,10 +1557,8 @@ struct amx_ffnn {
                    std::tie(o.feats, o.scores, o.best, o.counts, o.sum, o.stream, o.stride, o.T, o.stats);
         }
     };
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    float *d_host_f = nullptr, *d_host_s = nullptr;  // staging buffers of the host-buffer entry point amx_ffnn_score
-    size_t host_f_cap = 0, host_s_cap = 0;
-    int    use_graphs = 1;
+    amx::GraphCache<GraphKey> graphs;  // (tuning "graph")
+    amx::DevBuf<float> d_host_f, d_host_s;  // staging buffers of the host-buffer entry point amx_ffnn_score
     int    gemm_persistent = 1;
     int    gemm_cfg       = -1;  // -1 = automatic; index into the bf16 tile configurations (launch_bf16_cfg); tuning "tile"
     int    chunk          = 32768;  // frames per internal pass (tuning "chunk")
@@ -1552,27 +1566,24 @@ struct amx_ffnn {
     int    mx_dbg         = 0;   // lab builds: ablation variant of gemm_mx_kernel (tuning "mx_dbg")
     int    mx_ksplit      = 1;   // tuning "ksplit": 4 = small batches (the one-tile-per-CU configuration with fewer tiles than a quarter of the
                                  // CUs) split K over four workgroups per tile (gemm_mx_kernel's comment)
-    float*    d_ks_ws  = nullptr;   // split-K workspace: partial sums [tile][group][wave][register][lane]
-    size_t    ks_ws_cap = 0;
-    // AMX_PREC_F16MX: host-mapped word the kernels set when a value leaves the f16 range (sticky: every later call fails)
-    unsigned* h_overflow = nullptr;
-    unsigned* d_overflow = nullptr;
+    amx::DevBuf<float> d_ks_ws;  // split-K workspace: partial sums [tile][group][wave][register][lane]
+    OverflowWord overflow;       // AMX_PREC_F16MX only (sticky: every later call fails)
     // amx_ffnn_layers: preprocessing of the features (device vectors in pre), maxoutvar behind hidden layers
     amx::PreOps         pre{};
-    std::vector<float*> d_pre;      // the mean / reciprocal stddev vectors pre points to
+    std::vector<amx::DevBuf<float>> d_pre;  // per preprocessing layer: [mean | reciprocal stddev], what pre points to (empty: a logarithm)
     std::vector<int>    mo_groups;  // per layer: G outputs of its maxout, 0 = none
-    std::vector<int*>   d_mo_off, d_mo_size;  // per layer [G] first unit and size of every group (nullptr without maxout)
+    std::vector<amx::DevBuf<int>> d_mo_off, d_mo_size;  // per layer [G] first unit and size of every group (empty without maxout)
     int    mo_width = 0;            // widest layer in front of a maxout
-    float* d_mo     = nullptr;      // its f32 rows -(W x + b) [cap_T x mo_width]
+    amx::DevBuf<float> d_mo;        // its f32 rows -(W x + b) [Tpad x mo_width]
     size_t elt() const { return precision == AMX_PREC_FP32 ? 4 : 2; }
     bool   mfma_bf16() const { return precision != AMX_PREC_FP32; }  // everything but the exact-f32 kernels (fused statistics, HIP graphs)
     bool   is_mx() const { return precision == AMX_PREC_F16MX; }
     int    requested_precision = 0;   // amx_ffnn_model.precision; `precision` is what the handle computes in (mx_fallback)
     double mx_block_ratio      = 0.0; // AMX_PREC_F16MX requested: largest rms(block maxima) / rms(elements) over the layers
 #ifdef AMX_LAB  // an ablation variant computes on stale operands: its scores are never valid, the flag is not looked at
-    int    overflowed() const { return mx_dbg == 0 && h_overflow && *(volatile unsigned*)h_overflow; }
+    int    overflowed() const { return mx_dbg == 0 && overflow.host && *(volatile unsigned*)overflow.host; }
 #else
-    int    overflowed() const { return h_overflow && *(volatile unsigned*)h_overflow; }
+    int    overflowed() const { return overflow.host && *(volatile unsigned*)overflow.host; }
 #endif
 };
 
@@ -1582,39 +1593,35 @@ int pad_to(int v, int m) {
     return (v + m - 1) / m * m;
 }
 
-int ensure_workspace(amx_ffnn* h, int Tpad) {
-    if (Tpad <= h->cap_T)
+// row stride of an operand `width` columns wide, as the kernels take it: elements of a row (split bf16: [hi plane | lo plane]), or
+// f16mx K-tiles per 256-row block
+int operand_stride(const amx_ffnn* h, int width) {
+    return h->is_mx() ? width / 32 : (h->precision == AMX_PREC_BF16X3 ? 2 : 1) * width;
+}
+
+// bytes of that operand for Tpad frames (f16mx: 24 KB blocks per (256 rows, 32 k))
+size_t operand_bytes(const amx_ffnn* h, int Tpad, int width) {
+    const size_t stride = (size_t)operand_stride(h, width);
+    return h->is_mx() ? (size_t)(Tpad / 256) * stride * amx::mx::BLK : (size_t)Tpad * stride * h->elt();
+}
+
+// grows a buffer whose address recorded passes may hold: the graphs go first, then the old memory
+template<class T>
+int grow(amx_ffnn* h, amx::DevBuf<T>& buf, size_t n) {
+    if (n <= buf.capacity())
         return AMX_OK;
-    // captured passes hold the old workspace addresses: drop them before the buffers move
-    for (auto& kv : h->graphs)
-        if (kv.second)
-            hipGraphExecDestroy(kv.second);
     h->graphs.clear();
-    hipFree(h->d_in);
-    hipFree(h->d_act[0]);
-    hipFree(h->d_act[1]);
-    hipFree(h->d_mo);
-    h->d_in = h->d_act[0] = h->d_act[1] = nullptr;
-    h->d_mo                             = nullptr;
-    h->cap_T                            = 0;
+    return buf.reserve(n);
+}
+
+int ensure_workspace(amx_ffnn* h, int Tpad) {
     if (h->mo_width > 0)
-        AMX_HIP(hipMalloc((void**)&h->d_mo, (size_t)Tpad * h->mo_width * 4));
-    const size_t planes = h->precision == AMX_PREC_BF16X3 ? 2 : 1;  // split bf16: rows are [hi plane | lo plane]
-    if (h->is_mx()) {  // 25 KB blocks per (256 rows, 32 k); the split-K workspace is sized once, by size_split_k_workspace
-        AMX_HIP(hipMalloc(&h->d_in, (size_t)(Tpad / 256) * (h->Kpad[0] / 32) * amx::mx::BLK));
-        if (h->max_hidden_pad > 0) {
-            AMX_HIP(hipMalloc(&h->d_act[0], (size_t)(Tpad / 256) * (h->max_hidden_pad / 32) * amx::mx::BLK));
-            AMX_HIP(hipMalloc(&h->d_act[1], (size_t)(Tpad / 256) * (h->max_hidden_pad / 32) * amx::mx::BLK));
-        }
-        h->cap_T = Tpad;
-        return AMX_OK;
-    }
-    AMX_HIP(hipMalloc(&h->d_in, (size_t)Tpad * planes * h->Kpad[0] * h->elt()));
+        AMX_TRY(grow(h, h->d_mo, (size_t)Tpad * h->mo_width));
+    AMX_TRY(grow(h, h->d_in, operand_bytes(h, Tpad, h->Kpad[0])));
     if (h->max_hidden_pad > 0) {
-        AMX_HIP(hipMalloc(&h->d_act[0], (size_t)Tpad * planes * h->max_hidden_pad * h->elt()));
-        AMX_HIP(hipMalloc(&h->d_act[1], (size_t)Tpad * planes * h->max_hidden_pad * h->elt()));
+        AMX_TRY(grow(h, h->d_act[0], operand_bytes(h, Tpad, h->max_hidden_pad)));
+        AMX_TRY(grow(h, h->d_act[1], operand_bytes(h, Tpad, h->max_hidden_pad)));
     }
-    h->cap_T = Tpad;
     return AMX_OK;
 }
 
@@ -1643,16 +1650,17 @@ void size_split_k_workspace(amx_ffnn* h) {
         if (!fits)
             break;
     }
-    if (need == 0)
-        return;
-    if (hipMalloc((void**)&h->d_ks_ws, need * 4) != hipSuccess) {
+    if (need != 0 && h->d_ks_ws.reserve(need) != AMX_OK) {
         (void)hipGetLastError();
-        h->d_ks_ws   = nullptr;
         h->mx_ksplit = 1;
-        return;
     }
-    h->ks_ws_cap = need;
 }
+
+// where the output layer's launch leaves its per-tile arg-min partials (empty: no fused statistics, or not the output layer)
+struct ArgminPart {
+    float*    min = nullptr;
+    unsigned* idx = nullptr;
+};
 
 // tile configurations of the bf16 GEMM, selected at run time (amx_ffnn_model.tuning tile=N overrides for experiments)
 using CfgA = amx::GemmCfg<128, 128, 2, 2, 2>;  //  64 KB LDS, 2 workgroups per CU
@@ -1683,7 +1691,7 @@ amx::GemmLd gemm_ld(const amx_ffnn* h, int l, int ldx, int ldo) {
 }
 
 template<class C, int ACT, bool LAST, int VAR>
-void launch_bf16v(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
+int launch_bf16v(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad, ArgminPart part) {
     const int ntn = h->Npad[l] / C::BN, ntt = Tpad / C::BT;
     auto      k   = amx::gemm_bf16_kernel<C, ACT, LAST, VAR>;
     // super-tile order: the tiles one XCD holds at a time share operand panels in its L2 (tools/gemm_probe.hip: output
@@ -1699,22 +1707,21 @@ void launch_bf16v(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo
         grid &= ~7;  // keep blockIdx % 8 == tile index % 8 for every stride step
     if (h->gemm_persistent == 0)
         grid = ntn * ntt;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const amx::bf16_t*)h->d_W[l],
-                       (const amx::bf16_t*)x, h->d_bias[l], out, h->Kpad[l], gemm_ld(h, l, ldx, ldo), h->out[l], T, ntn, ntn * ntt, gt, gn,
-                       LAST ? h->cur_part_min : nullptr, LAST ? h->cur_part_idx : nullptr, Tpad);
-    if (LAST)
-        h->cur_ntn = ntn;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const amx::bf16_t*)h->d_W[l].get(),
+                       (const amx::bf16_t*)x, h->d_bias[l].get(), out, h->Kpad[l], gemm_ld(h, l, ldx, ldo), h->out[l], T, ntn, ntn * ntt, gt, gn,
+                       LAST ? part.min : nullptr, LAST ? part.idx : nullptr, Tpad);
+    return ntn;
 }
 
 template<class C, int ACT, bool LAST>
-void launch_bf16(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
+int launch_bf16(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad, ArgminPart part) {
     // VAR bits are experiment switches (tools/gemm_probe.hip); the library instantiates variant 0.
-    launch_bf16v<C, ACT, LAST, 0>(h, l, x, ldx, out, ldo, T, Tpad);
+    return launch_bf16v<C, ACT, LAST, 0>(h, l, x, ldx, out, ldo, T, Tpad, part);
 }
 
 // large batches: the cross-tile pipelined kernel
 template<class C, int ACT, bool LAST>
-void launch_bf16_pipe(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
+int launch_bf16_pipe(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad, ArgminPart part) {
     using P       = amx::PipeLds<C, LAST>;
     const int ntn = h->Npad[l] / C::BN, ntt = Tpad / C::BT;
     auto      k   = amx::gemm_bf16_pipe_kernel<C, ACT, LAST>;
@@ -1725,11 +1732,10 @@ void launch_bf16_pipe(amx_ffnn* h, int l, const void* x, int ldx, void* out, int
     if (grid >= 8)
         grid &= ~7;  // keep blockIdx % 8 == tile index % 8 for every stride step
     const int aligned = LAST ? (((uintptr_t)out & 15) == 0 && (ldo & 3) == 0) : 1;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), P::BYTES, h->ctx->stream, (const amx::bf16_t*)h->d_W[l], (const amx::bf16_t*)x,
-                       h->d_bias[l], out, h->Kpad[l], gemm_ld(h, l, ldx, ldo), h->out[l], T, ntn, ntn * ntt, gt, gn, aligned,
-                       LAST ? h->cur_part_min : nullptr, LAST ? h->cur_part_idx : nullptr, Tpad);
-    if (LAST)
-        h->cur_ntn = ntn;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), P::BYTES, h->ctx->stream, (const amx::bf16_t*)h->d_W[l].get(), (const amx::bf16_t*)x,
+                       h->d_bias[l].get(), out, h->Kpad[l], gemm_ld(h, l, ldx, ldo), h->out[l], T, ntn, ntn * ntt, gt, gn, aligned,
+                       LAST ? part.min : nullptr, LAST ? part.idx : nullptr, Tpad);
+    return ntn;
 }
 
 // workgroups of the pipelined kernel for `tiles` 256 x 256 tiles (launch_bf16_pipe: one per CU, a multiple of 8 from 8 on)
@@ -1741,7 +1747,7 @@ static inline long pipe_grid(long tiles, long ncu) {
 }
 
 template<int ACT, bool LAST>
-void launch_bf16_cfg(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
+int launch_bf16_cfg(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad, ArgminPart part) {
     // default: 256x256 tiles when they still give >= 2 tiles per CU, else 128x128 (small batches)
     int cfg = h->gemm_cfg;
     if (cfg < 0) {
@@ -1764,27 +1770,25 @@ void launch_bf16_cfg(amx_ffnn* h, int l, const void* x, int ldx, void* out, int 
     }
     if (h->precision == AMX_PREC_BF16X3) {
         switch (cfg) {
-            case 2: launch_bf16_pipe<XfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            case 4: launch_bf16<XfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            case 3: launch_bf16<XfgS, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            case 6: launch_bf16<XfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-            default: launch_bf16<XfgA, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
+            case 2: return launch_bf16_pipe<XfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+            case 4: return launch_bf16<XfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+            case 3: return launch_bf16<XfgS, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+            case 6: return launch_bf16<XfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+            default: return launch_bf16<XfgA, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
         }
-        return;
     }
     switch (cfg) {
-        case 2: launch_bf16_pipe<CfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-        case 4: launch_bf16<CfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;  // previous large-batch kernel (A/B runs)
-        case 3: launch_bf16<CfgS, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
-        case 6: launch_bf16<CfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
+        case 2: return launch_bf16_pipe<CfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+        case 4: return launch_bf16<CfgC, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);  // previous large-batch kernel (A/B runs)
+        case 3: return launch_bf16<CfgS, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+        case 6: return launch_bf16<CfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
         case 11:   // round 6, A/B runs: CfgS3 with four loader waves for the hidden layers -- bit-identical, and measured NO gain (17.4 against
                    // 17.0 us per 2048 x 2048 layer at batch 1024): the tile is bound by the LDS time of its fragment reads (48 KB per K-tile)
             if constexpr (LAST)
-                launch_bf16<CfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad);
+                return launch_bf16<CfgS3, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
             else
-                launch_bf16<CfgS3L, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad);
-            break;
-        default: launch_bf16<CfgA, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad); break;
+                return launch_bf16<CfgS3L, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
+        default: return launch_bf16<CfgA, ACT, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part);
     }
 }
 
@@ -1806,7 +1810,7 @@ using Mfg64 = amx::mx::MxCfg<64, 64, 2, 2, 8, 0, 0, 4, 4>;    // round 6 (tile=1
 using MfgSP = amx::mx::MxCfg<128, 64, 2, 2, 8, 0, 0, 2, 4, 3>;  // round 6, the default for hidden layers of small batches: MfgSL with the READ-AHEAD K loop (two register images, conversions issued first, a steady-state body without run-time wait selection); MfgSL stays as tile=11
 
 template<class C, int ACT, bool LAST>
-void launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, int T, int Tpad, int n_valid) {
+int launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, int T, int Tpad, int n_valid, ArgminPart part) {
     const int ntn = h->Npad[l] / C::BN, ntt = Tpad / C::BT;
     const int gt = h->group_t >= 0 ? h->group_t : (C::BN == 256 ? 16 : 8), gn = h->group_n >= 0 ? h->group_n : (C::BN == 256 ? 8 : 2);
     constexpr int lds_bytes = amx::gemm_scratch_bytes<C, LAST>() + C::BN * 4;   // stages / epilogue scratch + the tile's bias
@@ -1818,7 +1822,7 @@ void launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, 
     if (h->mx_ksplit > 1 && C::BN == 128 && C::BT == 64 && C::U == 2 && (long)ntn * ntt * h->mx_ksplit <= (long)std::max(h->ctx->n_cu, 8) &&
         h->Kpad[l] / 32 >= 8 * h->mx_ksplit)
         ksplit = h->mx_ksplit;
-    if (ksplit > 1 && (size_t)ntn * ntt * ksplit * C::NW * C::MI * C::MJ * 16 * 64 > h->ks_ws_cap)
+    if (ksplit > 1 && (size_t)ntn * ntt * ksplit * C::NW * C::MI * C::MJ * 16 * 64 > h->d_ks_ws.capacity())
         ksplit = 1;  // (size_split_k_workspace sizes the workspace for every pass that can run split; nothing is allocated here: this may be inside a stream capture)
     int       grid   = std::min(ntn * ntt * ksplit, per_cu * std::max(h->ctx->n_cu, 8));
     if (grid >= 8)
@@ -1830,15 +1834,15 @@ void launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, 
     do {                                                                                                                                    \
         auto k = amx::mx::gemm_mx_kernel<C, ACT, LAST, DBG>;                                                                                \
         hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);                                         \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const char*)h->d_W[l], (const char*)x, h->d_bias[l], \
+        hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const char*)h->d_W[l].get(), (const char*)x, h->d_bias[l].get(), \
                            out, h->Kpad[l] / 32, xkts, h->Npad[l] / 32, ldo, n_valid, T, ntn, ntn * ntt, gt, gn,                            \
-                           LAST ? h->cur_part_min : nullptr, LAST ? h->cur_part_idx : nullptr, Tpad, h->d_overflow, stagger, ksplit,       \
-                           h->d_ks_ws);                                                                                                     \
+                           LAST ? part.min : nullptr, LAST ? part.idx : nullptr, Tpad, h->overflow.dev, stagger, ksplit,       \
+                           h->d_ks_ws.get());                                                                                                     \
         if (ksplit > 1) /* launch 2: the partial sums of every tile, in group order, then the epilogue */                                  \
-            hipLaunchKernelGGL(k, dim3(std::min(ntn * ntt, grid)), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const char*)h->d_W[l],     \
-                               (const char*)x, h->d_bias[l], out, h->Kpad[l] / 32, xkts, h->Npad[l] / 32, ldo, n_valid, T, ntn, ntn * ntt,  \
-                               gt, gn, LAST ? h->cur_part_min : nullptr, LAST ? h->cur_part_idx : nullptr, Tpad, h->d_overflow, 0, -ksplit, \
-                               h->d_ks_ws);                                                                                                 \
+            hipLaunchKernelGGL(k, dim3(std::min(ntn * ntt, grid)), dim3(C::THREADS), lds_bytes, h->ctx->stream, (const char*)h->d_W[l].get(),     \
+                               (const char*)x, h->d_bias[l].get(), out, h->Kpad[l] / 32, xkts, h->Npad[l] / 32, ldo, n_valid, T, ntn, ntn * ntt,  \
+                               gt, gn, LAST ? part.min : nullptr, LAST ? part.idx : nullptr, Tpad, h->overflow.dev, 0, -ksplit, \
+                               h->d_ks_ws.get());                                                                                                 \
     } while (0)
     int dbg = 0;
 #ifdef AMX_LAB  // ablations of the large-batch kernel (tools/ab_mx.sh, profiles/r04/gemm_mx_ablation.log)
@@ -1900,12 +1904,11 @@ void launch_mx(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, 
     if (dbg == 0)
         AMX_MX_LAUNCH(0);
 #undef AMX_MX_LAUNCH
-    if (LAST)
-        h->cur_ntn = ntn;
+    return ntn;
 }
 
 template<int ACT, bool LAST>
-void launch_mx_cfg(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, int T, int Tpad, int n_valid) {
+int launch_mx_cfg(amx_ffnn* h, int l, const void* x, int xkts, void* out, int ldo, int T, int Tpad, int n_valid, ArgminPart part) {
     int cfg = h->gemm_cfg;
     if (cfg < 0) {
         const long ncu = std::max(h->ctx->n_cu, 1), t256 = (long)(h->Npad[l] / 256) * (Tpad / 256), t128 = (long)(h->Npad[l] / 128) * (Tpad / 128);
@@ -1934,33 +1937,30 @@ void launch_mx_cfg(amx_ffnn* h, int l, const void* x, int xkts, void* out, int l
             cfg = 3;
     }
     switch (cfg) {
-        case 2: launch_mx<MfgL, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 4: launch_mx<MfgLP, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 5: launch_mx<MfgLH, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 7: launch_mx<MfgLF, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 8: launch_mx<MfgLQ, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 9: launch_mx<MfgLW, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
+        case 2: return launch_mx<MfgL, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 4: return launch_mx<MfgLP, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 5: return launch_mx<MfgLH, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 7: return launch_mx<MfgLF, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 8: return launch_mx<MfgLQ, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 9: return launch_mx<MfgLW, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
         case 3:
             if constexpr (LAST)
-                launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);
+                return launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
             else
-                launch_mx<MfgSP, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);   // round 6: read-ahead K loop (bit-identical to MfgSL: tile=11)
-            break;
-        case 6: launch_mx<MfgS4, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
-        case 12: launch_mx<MfgS8, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
+                return launch_mx<MfgSP, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);   // round 6: read-ahead K loop (bit-identical to MfgSL: tile=11)
+        case 6: return launch_mx<MfgS4, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        case 12: return launch_mx<MfgS8, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
         case 14:
             if constexpr (LAST)
-                launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);
+                return launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
             else
-                launch_mx<Mfg64, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);
-            break;
+                return launch_mx<Mfg64, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
 case 11:   // round 5's hidden-layer loop (no read-ahead): A/B runs
             if constexpr (LAST)
-                launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);
+                return launch_mx<MfgS, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
             else
-                launch_mx<MfgSL, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid);
-            break;
-        default: launch_mx<MfgA, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid); break;
+                return launch_mx<MfgSL, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
+        default: return launch_mx<MfgA, ACT, LAST>(h, l, x, xkts, out, ldo, T, Tpad, n_valid, part);
     }
 }
 
@@ -1989,7 +1989,7 @@ void pack_operand(amx_ffnn* h, const S& src, int T, int K, void* out, int Kp, in
     const int   blocks = (int)std::min<long long>(4096, ((long long)Tpad * Kp + 255) / 256);
     if (h->is_mx()) {
         const int b2 = (int)std::min<long long>(8192, ((long long)Tpad * (Kp / 32) * 2 + 255) / 256);
-        hipLaunchKernelGGL(amx::mx::pack_input_mx<S>, dim3(b2), dim3(256), 0, st, src, T, K, (char*)out, Kp / 32, Tpad, h->d_overflow);
+        hipLaunchKernelGGL(amx::mx::pack_input_mx<S>, dim3(b2), dim3(256), 0, st, src, T, K, (char*)out, Kp / 32, Tpad, h->overflow.dev);
     }
     else if (h->precision == AMX_PREC_BF16X3)
         hipLaunchKernelGGL(amx::pack_input_bf16x3<S>, dim3(blocks), dim3(256), 0, st, src, T, K, (amx::bf16_t*)out, Kp, Tpad);
@@ -1999,8 +1999,9 @@ void pack_operand(amx_ffnn* h, const S& src, int T, int K, void* out, int Kp, in
         hipLaunchKernelGGL(amx::pack_input_f32<S>, dim3(blocks), dim3(256), 0, st, src, T, K, (float*)out, Kp, Tpad);
 }
 
+// part: where a fused-statistics output layer leaves its arg-min partials; *ntn: how many rows of them (n-tiles) it wrote
 template<bool LAST>
-int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad) {
+int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo, int T, int Tpad, ArgminPart part = {}, int* ntn = nullptr) {
     hipStream_t            st = h->ctx->stream;
     amx::ScopedKernelTimer t_all(h->ctx, "ffnn_gemm");
     hipEvent_t             e0 = nullptr, e1 = nullptr;
@@ -2013,19 +2014,20 @@ int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo,
     // LAST (the score epilogue: the output layer, or a hidden layer leaving as f32 rows -(W x + b)) never applies an activation: only
     // its AMX_ACT_NONE instantiation exists
     const int act = LAST ? AMX_ACT_NONE : h->act[l];
+    int       tiles = 0;
     if (h->is_mx()) {  // LAST with l < n_layers - 1: a hidden layer as f32 rows (amx_ffnn_forward_hidden_dev, maxout)
-        with_act<LAST>(act, [&](auto a) { launch_mx_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l]); });
+        with_act<LAST>(act, [&](auto a) { tiles = launch_mx_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad, h->out[l], part); });
     }
     else if (h->mfma_bf16()) {
-        with_act<LAST>(act, [&](auto a) { launch_bf16_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad); });
+        with_act<LAST>(act, [&](auto a) { tiles = launch_bf16_cfg<decltype(a)::value, LAST>(h, l, x, ldx, out, ldo, T, Tpad, part); });
     }
     else {
         const int ntn = h->Npad[l] / amx::BN, ntt = Tpad / amx::BT;
         dim3      grid(ntn * ntt), block(256);
         const int nv = h->out[l];
         with_act<LAST>(act, [&](auto a) {
-            hipLaunchKernelGGL((amx::gemm_f32_kernel<decltype(a)::value, LAST>), grid, block, 0, st, (const float*)h->d_W[l], (const float*)x,
-                               h->d_bias[l], (float*)out, h->Kpad[l], ldx, ldo, nv, T, ntn);
+            hipLaunchKernelGGL((amx::gemm_f32_kernel<decltype(a)::value, LAST>), grid, block, 0, st, (const float*)h->d_W[l].get(), (const float*)x,
+                               h->d_bias[l].get(), (float*)out, h->Kpad[l], ldx, ldo, nv, T, ntn);
         });
     }
     if (time_max) {
@@ -2033,25 +2035,19 @@ int launch_layer(amx_ffnn* h, int l, const void* x, int ldx, void* out, int ldo,
         h->ctx->prof["ffnn_gemm_max"].events.emplace_back(e0, e1);
     }
     AMX_HIP(hipGetLastError());
+    if (ntn)
+        *ntn = tiles;
     return AMX_OK;
 }
 
 // hidden layer l with a maxout behind it: W x + b leaves through the score epilogue as exact f32 rows -(W x + b) (d_mo), then the maxout
 // of act(-v) becomes the next operand (dst: Kp columns, Trows rows, zero padded; export: plain f32 rows [T x G], Kp = G, Trows = T)
 int launch_maxout_layer(amx_ffnn* h, int l, const void* x, int ldx, void* dst, int Kp, int T, int Trows, int Tpad, bool export_f32) {
-    float* const    pm = h->cur_part_min;  // the arg-min partials belong to the output layer
-    unsigned* const pi = h->cur_part_idx;
-    h->cur_part_min    = nullptr;
-    h->cur_part_idx    = nullptr;
-    const int r        = launch_layer<true>(h, l, x, ldx, h->d_mo, h->out[l], T, Tpad);
-    h->cur_part_min    = pm;
-    h->cur_part_idx    = pi;
-    if (r != AMX_OK)
-        return r;
+    AMX_TRY(launch_layer<true>(h, l, x, ldx, h->d_mo.get(), h->out[l], T, Tpad));  // (no arg-min partials: they belong to the output layer)
     const int G = h->mo_groups[l];
     amx::ScopedKernelTimer timer(h->ctx, "ffnn_maxout");
     with_act(h->act[l], [&](auto a) {
-        const amx::MaxoutSrc<decltype(a)::value> src{h->d_mo, h->out[l], h->d_mo_off[l], h->d_mo_size[l]};
+        const amx::MaxoutSrc<decltype(a)::value> src{h->d_mo.get(), h->out[l], h->d_mo_off[l].get(), h->d_mo_size[l].get()};
         if (export_f32) {
             const int blocks = (int)std::min<long long>(4096, ((long long)Trows * Kp + 255) / 256);
             hipLaunchKernelGGL(amx::pack_input_f32<decltype(src)>, dim3(blocks), dim3(256), 0, h->ctx->stream, src, T, G, (float*)dst, Kp, Trows);
@@ -2063,26 +2059,20 @@ int launch_maxout_layer(amx_ffnn* h, int l, const void* x, int ldx, void* dst, i
     return AMX_OK;
 }
 
-}  // namespace
+// ---- amx_ffnn_create_ex, step by step.  The handle is host memory until the overflow word and the first layer are uploaded; whatever
+// step fails after that, the std::unique_ptr that holds it frees what the steps before have taken.
 
-extern "C" {
+// amx_ffnn_layers, checked: the maxout behind every layer
+struct MaxoutSpec {
+    std::vector<int>              groups;  // per layer: outputs of its maxout, 0 = none
+    std::vector<std::vector<int>> size;    // per layer: the size of every group
+};
 
-int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
-    return amx_ffnn_create_ex(ctx, m, nullptr, out);
-}
-
-int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_layers* ext, amx_ffnn** out) {
-    AMX_REQUIRE(ctx && m && out, AMX_ERR_INVALID, "amx_ffnn_create: NULL argument");
-    *out = nullptr;
-    AMX_REQUIRE(m->n_layers >= 1 && m->in_dim && m->out_dim && m->W && m->bias && m->activation, AMX_ERR_INVALID,
-                "amx_ffnn_create: empty network");
-    AMX_REQUIRE(m->precision == AMX_PREC_FP32 || m->precision == AMX_PREC_BF16 || m->precision == AMX_PREC_BF16X3 ||
-                        m->precision == AMX_PREC_F16MX,
-                AMX_ERR_INVALID, "amx_ffnn_create: unknown precision");
-    // ---- amx_ffnn_layers: preprocessing layers (Nn/PreprocessingLayer.cc) and maxoutvar group sizes (Nn/ActivationLayer.cc:404-470)
-    const int        n_pre = ext ? ext->n_pre : 0;
-    std::vector<int> mo_groups((size_t)m->n_layers, 0);
-    std::vector<std::vector<int>> mo_size((size_t)m->n_layers);
+// preprocessing layers (Nn/PreprocessingLayer.cc) and maxoutvar group sizes (Nn/ActivationLayer.cc:404-470)
+int check_extension(const amx_ffnn_model* m, const amx_ffnn_layers* ext, MaxoutSpec* mo) {
+    const int n_pre = ext ? ext->n_pre : 0;
+    mo->groups.assign((size_t)m->n_layers, 0);
+    mo->size.assign((size_t)m->n_layers, {});
     AMX_REQUIRE(n_pre >= 0 && n_pre <= AMX_NN_MAX_PRE, AMX_ERR_INVALID, "amx_ffnn_create_ex: %d preprocessing layers (0 to %d)", n_pre,
                 AMX_NN_MAX_PRE);
     AMX_REQUIRE(n_pre == 0 || ext->pre_type, AMX_ERR_INVALID, "amx_ffnn_create_ex: %d preprocessing layers without pre_type", n_pre);
@@ -2106,7 +2096,7 @@ int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
             AMX_REQUIRE(l + 1 < m->n_layers, AMX_ERR_INVALID, "amx_ffnn_create_ex: layer %d is the output layer: no maxout behind it", l);
             AMX_REQUIRE(m->out_dim[l] > 0, AMX_ERR_INVALID, "amx_ffnn_create: layer %d is empty", l);
             const int* sz = ext->maxout_sizes ? ext->maxout_sizes[l] : nullptr;
-            auto&      v  = mo_size[l];
+            auto&      v  = mo->size[l];
             if (sz) {  // maxout-sizes: require_eq(getInputDimension(0), sum of the sizes)
                 long sum = 0;
                 for (int g = 0; g < G; ++g) {
@@ -2124,8 +2114,12 @@ int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
                             "(require_eq(getInputDimension(0), maxoutSize_ * getOutputDimension()))", l, m->out_dim[l], G);
                 v.assign((size_t)G, m->out_dim[l] / G);
             }
-            mo_groups[l] = G;
+            mo->groups[l] = G;
         }
+    return AMX_OK;
+}
+
+int check_model(const amx_ffnn_model* m, const std::vector<int>& mo_groups) {
     for (int l = 0; l < m->n_layers; ++l) {
         AMX_REQUIRE(m->in_dim[l] > 0 && m->out_dim[l] > 0 && m->W[l], AMX_ERR_INVALID, "amx_ffnn_create: layer %d is empty", l);
         if (l > 0 && mo_groups[l - 1] > 0)
@@ -2140,264 +2134,236 @@ int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
     }
     // Nn::BatchFeatureScorer: "output layer must be of type 'linear+softmax'" with the softmax switched off
     AMX_REQUIRE(m->activation[m->n_layers - 1] == AMX_ACT_NONE, AMX_ERR_INVALID, "amx_ffnn_create: output layer must be linear (softmax is not evaluated)");
+    return AMX_OK;
+}
 
-    // ---- Nn::ClassLabelWrapper (Nn/ClassLabelWrapper.cc:56-75, Nn/BatchFeatureScorer.cc:148-171): emission e reads network output
-    // class_to_output[e]; a disregarded class (-1) scores Core::Type<f32>::max.  The mapping is one-to-one (the reference refuses
-    // anything else), so it is applied ONCE, to the output layer: row e of the emission-ordered layer is row class_to_output[e]
-    // of the network's (with its bias and prior), a disregarded class gets a zero row and bias -FLT_MAX -- score = -(0 + bias) =
-    // FLT_MAX exactly, in every precision mode.  Scores, arg-min statistics and the on-demand scorer then index emissions.
-    const int          L0 = m->n_layers - 1;
-    std::vector<int>   out_dim(m->out_dim, m->out_dim + m->n_layers);
-    std::vector<const float*> Wl(m->W, m->W + m->n_layers), bl(m->bias, m->bias + m->n_layers);
-    const float*       prior = m->log_prior;
-    std::vector<float> Wmap, bmap, pmap;
-    const bool class_mapped = m->class_to_output != nullptr;
-    if (m->class_to_output) {
-        AMX_REQUIRE(m->n_classes > 0, AMX_ERR_INVALID, "amx_ffnn_create: class_to_output without n_classes");
-        const int N = m->out_dim[L0], K = m->in_dim[L0];
-        std::vector<char> used((size_t)N, 0);
-        int               n_targets = 0;
-        for (int e = 0; e < m->n_classes; ++e) {
-            const int o = m->class_to_output[e];
-            AMX_REQUIRE(o >= -1 && o < N, AMX_ERR_INVALID, "amx_ffnn_create: class %d maps to output %d (network has %d outputs)", e, o, N);
-            if (o >= 0) {
-                // ClassLabelWrapper::isOneToOneMapping: "no one-to-one correspondence between network outputs and classes!"
-                AMX_REQUIRE(!used[o], AMX_ERR_INVALID, "amx_ffnn_create: no one-to-one correspondence between network outputs and classes (output %d)", o);
-                used[o] = 1;
-                ++n_targets;
+// the layers as the handle packs them: the model's own arrays, or -- behind a class-label mapping -- an output layer in emission order
+struct LayerParams {
+    std::vector<int>          out_dim;
+    std::vector<const float*> W, bias;
+    const float*              prior = nullptr;
+    std::vector<float>        Wmap, bmap, pmap;  // the remapped output layer that W / bias / prior then point to
+};
+
+// ---- Nn::ClassLabelWrapper (Nn/ClassLabelWrapper.cc:56-75, Nn/BatchFeatureScorer.cc:148-171): emission e reads network output
+// class_to_output[e]; a disregarded class (-1) scores Core::Type<f32>::max.  The mapping is one-to-one (the reference refuses
+// anything else), so it is applied ONCE, to the output layer: row e of the emission-ordered layer is row class_to_output[e]
+// of the network's (with its bias and prior), a disregarded class gets a zero row and bias -FLT_MAX -- score = -(0 + bias) =
+// FLT_MAX exactly, in every precision mode.  Scores, arg-min statistics and the on-demand scorer then index emissions.
+int remap_classes(const amx_ffnn_model* m, LayerParams* p) {
+    const int L0 = m->n_layers - 1;
+    p->out_dim.assign(m->out_dim, m->out_dim + m->n_layers);
+    p->W.assign(m->W, m->W + m->n_layers);
+    p->bias.assign(m->bias, m->bias + m->n_layers);
+    p->prior = m->log_prior;
+    if (!m->class_to_output)
+        return AMX_OK;
+    AMX_REQUIRE(m->n_classes > 0, AMX_ERR_INVALID, "amx_ffnn_create: class_to_output without n_classes");
+    const int N = m->out_dim[L0], K = m->in_dim[L0];
+    std::vector<char> used((size_t)N, 0);
+    int               n_targets = 0;
+    for (int e = 0; e < m->n_classes; ++e) {
+        const int o = m->class_to_output[e];
+        AMX_REQUIRE(o >= -1 && o < N, AMX_ERR_INVALID, "amx_ffnn_create: class %d maps to output %d (network has %d outputs)", e, o, N);
+        if (o >= 0) {
+            // ClassLabelWrapper::isOneToOneMapping: "no one-to-one correspondence between network outputs and classes!"
+            AMX_REQUIRE(!used[o], AMX_ERR_INVALID, "amx_ffnn_create: no one-to-one correspondence between network outputs and classes (output %d)", o);
+            used[o] = 1;
+            ++n_targets;
+        }
+    }
+    // require_eq(network_.getTopLayer().getOutputDimension(), labelWrapper_->nClassesToAccumulate())
+    AMX_REQUIRE(n_targets == N, AMX_ERR_INVALID, "amx_ffnn_create: %d classes to accumulate, but the output layer has %d units", n_targets, N);
+    p->Wmap.assign((size_t)m->n_classes * K, 0.f);
+    p->bmap.assign((size_t)m->n_classes, -3.402823466e+38f);
+    p->pmap.assign((size_t)m->n_classes, 0.f);
+    for (int e = 0; e < m->n_classes; ++e) {
+        const int o = m->class_to_output[e];
+        if (o < 0)
+            continue;
+        memcpy(&p->Wmap[(size_t)e * K], m->W[L0] + (size_t)o * K, (size_t)K * 4);
+        p->bmap[e] = m->bias[L0] ? m->bias[L0][o] : 0.f;
+        p->pmap[e] = m->log_prior ? m->log_prior[o] : 0.f;
+    }
+    p->out_dim[L0] = m->n_classes;
+    p->W[L0]       = p->Wmap.data();
+    p->bias[L0]    = p->bmap.data();
+    if (m->log_prior)
+        p->prior = p->pmap.data();
+    return AMX_OK;
+}
+
+// amx_ffnn_model.tuning into the handle; values are checked like keys (a typo must not silently select the default kernel)
+int parse_tuning(const amx_ffnn_model* m, amx_ffnn* h, bool* mx_fallback_auto) {
+    static const char* const keys[]      = {"tile", "graph", "persistent", "group", "chunk", "stagger", "mx_dbg", "mx_fallback", "ksplit", nullptr};
+    static const char* const fallbacks[] = {"auto", "off", nullptr};
+    const char*              who         = "amx_ffnn_create";
+    amx::Tuning              tune;
+    std::string              fallback;
+    if (!tune.parse(m->tuning, keys, who) || !tune.get_word("mx_fallback", "auto", fallbacks, &fallback, who) ||
+        !tune.get_int("ksplit", 1, 1, 4, &h->mx_ksplit, who))
+        return AMX_ERR_INVALID;
+    *mx_fallback_auto = fallback == "auto";
+    AMX_REQUIRE(h->mx_ksplit == 1 || h->mx_ksplit == 4, AMX_ERR_INVALID, "amx_ffnn_create: tuning ksplit=%d: expected 1 | 4", h->mx_ksplit);
+    AMX_REQUIRE(h->mx_ksplit == 1 || m->precision == AMX_PREC_F16MX, AMX_ERR_UNSUPPORTED, "amx_ffnn_create: tuning ksplit exists for AMX_PREC_F16MX only");
+    if (!tune.get_int("tile", -1, -1, 14, &h->gemm_cfg, who) || !tune.get_int("graph", 0, 0, 1, &h->graphs.use_graphs, who) ||
+        !tune.get_int("persistent", 1, 0, 1, &h->gemm_persistent, who) || !tune.get_int("chunk", 32768, 256, 1 << 24, &h->chunk, who) ||
+        !tune.get_int("mx_dbg", 0, 0, 1 << 16, &h->mx_dbg, who) || !tune.get_int("stagger", 0, 0, 100000, &h->mx_stagger, who))
+        return AMX_ERR_INVALID;
+    if (tune.has("group")) {
+        const std::string g    = tune.kv["group"];
+        char              tail = 0;
+        AMX_REQUIRE(sscanf(g.c_str(), "%dx%d%c", &h->group_t, &h->group_n, &tail) == 2 && h->group_t >= 1 && h->group_n >= 1 && h->group_t <= 4096 &&
+                            h->group_n <= 4096,
+                    AMX_ERR_INVALID, "amx_ffnn_create: tuning group=%s: expected <frame tiles>x<output tiles>, e.g. 16x8", g.c_str());
+    }
+    return AMX_OK;
+}
+
+// rms of the maxima of a layer's blocks of 32 k / rms of its elements (0 for a layer of zeros)
+double block_max_ratio(const float* W, int N, int K) {
+    double sum_max2 = 0.0, sum_w2 = 0.0;
+    long   n_blocks = 0;
+    for (int n = 0; n < N; ++n)
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            float mx = 0.f;
+            for (int k = k0; k < std::min(K, k0 + 32); ++k) {
+                const float v = W[(size_t)n * K + k];
+                mx            = std::fmax(mx, std::fabs(v));
+                sum_w2 += (double)v * (double)v;
             }
+            sum_max2 += (double)mx * (double)mx;
+            ++n_blocks;
         }
-        // require_eq(network_.getTopLayer().getOutputDimension(), labelWrapper_->nClassesToAccumulate())
-        AMX_REQUIRE(n_targets == N, AMX_ERR_INVALID, "amx_ffnn_create: %d classes to accumulate, but the output layer has %d units", n_targets, N);
-        Wmap.assign((size_t)m->n_classes * K, 0.f);
-        bmap.assign((size_t)m->n_classes, -3.402823466e+38f);
-        pmap.assign((size_t)m->n_classes, 0.f);
-        for (int e = 0; e < m->n_classes; ++e) {
-            const int o = m->class_to_output[e];
-            if (o < 0)
-                continue;
-            memcpy(&Wmap[(size_t)e * K], m->W[L0] + (size_t)o * K, (size_t)K * 4);
-            bmap[e] = m->bias[L0] ? m->bias[L0][o] : 0.f;
-            pmap[e] = m->log_prior ? m->log_prior[o] : 0.f;
-        }
-        out_dim[L0] = m->n_classes;
-        Wl[L0]      = Wmap.data();
-        bl[L0]      = bmap.data();
-        if (m->log_prior)
-            prior = pmap.data();
-    }
+    return sum_w2 > 0.0 ? std::sqrt((sum_max2 / (double)n_blocks) / (sum_w2 / ((double)N * (double)K))) : 0.0;
+}
 
-    amx::Tuning tune;
-    {
-        static const char* const keys[] = {"tile", "graph", "persistent", "group", "chunk", "stagger", "mx_dbg", "mx_fallback", "ksplit", nullptr};
-        if (!tune.parse(m->tuning, keys, "amx_ffnn_create"))
-            return AMX_ERR_INVALID;
+// AMX_PREC_F16MX on heavy-tailed WEIGHTS.  One e8m0 exponent serves 32 k of a row pair; a block whose maximum dwarfs the rest leaves
+// the fp6 image q(w) of the small values at zero, and their cross terms r(x) q(w) are lost: measured (tests/test_ffnn_f16mx_gpu.py,
+// profiles/r05/f16mx_families.log) the error grows from ~27 x that of f32 accumulation (Gaussian weights) to 54-115 x (log-normal
+// rows, one outlier per block).  The statistic G = rms of the block maxima / rms of the elements says which case a layer is:
+// 2.4 Gaussian, 3.0 Laplace, 3.3 Student-t(4), 5.0 log-normal(1.5), 5.66 = sqrt(32) when one element carries every block.  Above
+// 4.0 the handle computes in split bf16 instead (tuning mx_fallback=auto, the default; mx_fallback=off keeps f16mx):
+// amx_ffnn_precision() reports what it runs.  Activations have no such check (they are not known here); an outlier per block in the
+// FEATURES costs 1.2 x (32 x against 27 x, unnormalised MFCC context windows included).
+int choose_precision(const amx_ffnn_model* m, const LayerParams& p, bool mx_fallback_auto, amx_ffnn* h) {
+    h->precision = h->requested_precision = m->precision;
+    if (m->precision != AMX_PREC_F16MX)
+        return AMX_OK;
+    for (int l = 0; l < m->n_layers; ++l)
+        h->mx_block_ratio = std::max(h->mx_block_ratio, block_max_ratio(p.W[l], p.out_dim[l], m->in_dim[l]));
+    if (mx_fallback_auto && h->mx_block_ratio > 4.0) {
+        // the handle computes in split bf16: twice the matrix work, other rounding than the caller asked for -- said ONCE, on
+        // stderr (the adapter logs amx_ffnn_precision as well), and a split-K request -- an f16mx schedule -- is refused rather
+        // than accepted and ignored (advisor, round 5)
+        AMX_REQUIRE(h->mx_ksplit <= 1, AMX_ERR_INVALID,
+                    "amx_ffnn_create: tuning ksplit=%d applies to AMX_PREC_F16MX, but this network's weights are heavy-tailed (block-maximum "
+                    "statistic %.2f > 4.0) and the handle would compute in AMX_PREC_BF16X3: drop ksplit, or keep f16mx with mx_fallback=off",
+                    h->mx_ksplit, h->mx_block_ratio);
+        std::fprintf(stderr, "rasr_amd: amx_ffnn_create: AMX_PREC_F16MX requested, computing in AMX_PREC_BF16X3 (block-maximum statistic of the "
+                             "weights %.2f > 4.0; tuning mx_fallback=off keeps f16mx)\n", h->mx_block_ratio);
+        h->precision = AMX_PREC_BF16X3;
     }
-    // values are checked like keys (a typo must not silently select the default kernel)
-    int t_tile, t_graph, t_persistent, t_chunk, t_mx_dbg, t_stagger, t_group_t = -1, t_group_n = -1, t_ksplit = 1;
-    std::string t_mx_fallback;
-    {
-        const char* who = "amx_ffnn_create";
-        static const char* const fallbacks[] = {"auto", "off", nullptr};
-        if (!tune.get_word("mx_fallback", "auto", fallbacks, &t_mx_fallback, who) || !tune.get_int("ksplit", 1, 1, 4, &t_ksplit, who))
-            return AMX_ERR_INVALID;
-        AMX_REQUIRE(t_ksplit == 1 || t_ksplit == 4, AMX_ERR_INVALID, "amx_ffnn_create: tuning ksplit=%d: expected 1 | 4", t_ksplit);
-        AMX_REQUIRE(t_ksplit == 1 || m->precision == AMX_PREC_F16MX, AMX_ERR_UNSUPPORTED, "amx_ffnn_create: tuning ksplit exists for AMX_PREC_F16MX only");
-        if (!tune.get_int("tile", -1, -1, 14, &t_tile, who) || !tune.get_int("graph", 0, 0, 1, &t_graph, who) ||
-            !tune.get_int("persistent", 1, 0, 1, &t_persistent, who) || !tune.get_int("chunk", 32768, 256, 1 << 24, &t_chunk, who) ||
-            !tune.get_int("mx_dbg", 0, 0, 1 << 16, &t_mx_dbg, who) || !tune.get_int("stagger", 0, 0, 100000, &t_stagger, who))
-            return AMX_ERR_INVALID;
-        if (tune.has("group")) {
-            const std::string g = tune.kv["group"];
-            char              tail = 0;
-            AMX_REQUIRE(sscanf(g.c_str(), "%dx%d%c", &t_group_t, &t_group_n, &tail) == 2 && t_group_t >= 1 && t_group_n >= 1 && t_group_t <= 4096 &&
-                                t_group_n <= 4096,
-                        AMX_ERR_INVALID, "amx_ffnn_create: tuning group=%s: expected <frame tiles>x<output tiles>, e.g. 16x8", g.c_str());
-        }
-    }
-    // AMX_PREC_F16MX on heavy-tailed WEIGHTS.  One e8m0 exponent serves 32 k of a row pair; a block whose maximum dwarfs the rest leaves
-    // the fp6 image q(w) of the small values at zero, and their cross terms r(x) q(w) are lost: measured (tests/test_ffnn_f16mx_gpu.py,
-    // profiles/r05/f16mx_families.log) the error grows from ~27 x that of f32 accumulation (Gaussian weights) to 54-115 x (log-normal
-    // rows, one outlier per block).  The statistic G = rms of the block maxima / rms of the elements says which case a layer is:
-    // 2.4 Gaussian, 3.0 Laplace, 3.3 Student-t(4), 5.0 log-normal(1.5), 5.66 = sqrt(32) when one element carries every block.  Above
-    // 4.0 the handle computes in split bf16 instead (tuning mx_fallback=auto, the default; mx_fallback=off keeps f16mx):
-    // amx_ffnn_precision() reports what it runs.  Activations have no such check (they are not known here); an outlier per block in the
-    // FEATURES costs 1.2 x (32 x against 27 x, unnormalised MFCC context windows included).
-    int    prec = m->precision;
-    double mx_ratio = 0.0;
-    if (prec == AMX_PREC_F16MX) {
-        for (int l = 0; l < m->n_layers; ++l) {
-            const int    K = m->in_dim[l], N = out_dim[l];
-            const float* W = Wl[l];
-            double       sum_max2 = 0.0, sum_w2 = 0.0;
-            long         n_blocks = 0;
-            for (int n = 0; n < N; ++n)
-                for (int k0 = 0; k0 < K; k0 += 32) {
-                    float mx = 0.f;
-                    for (int k = k0; k < std::min(K, k0 + 32); ++k) {
-                        const float v = W[(size_t)n * K + k];
-                        mx            = std::fmax(mx, std::fabs(v));
-                        sum_w2 += (double)v * (double)v;
-                    }
-                    sum_max2 += (double)mx * (double)mx;
-                    ++n_blocks;
-                }
-            if (sum_w2 > 0.0)
-                mx_ratio = std::max(mx_ratio, std::sqrt((sum_max2 / (double)n_blocks) / (sum_w2 / ((double)N * (double)K))));
-        }
-        if (t_mx_fallback == "auto" && mx_ratio > 4.0) {
-            // the handle computes in split bf16: twice the matrix work, other rounding than the caller asked for -- said ONCE, on
-            // stderr (the adapter logs amx_ffnn_precision as well), and a split-K request -- an f16mx schedule -- is refused rather
-            // than accepted and ignored (advisor, round 5)
-            AMX_REQUIRE(t_ksplit <= 1, AMX_ERR_INVALID,
-                        "amx_ffnn_create: tuning ksplit=%d applies to AMX_PREC_F16MX, but this network's weights are heavy-tailed (block-maximum "
-                        "statistic %.2f > 4.0) and the handle would compute in AMX_PREC_BF16X3: drop ksplit, or keep f16mx with mx_fallback=off",
-                        t_ksplit, mx_ratio);
-            std::fprintf(stderr, "rasr_amd: amx_ffnn_create: AMX_PREC_F16MX requested, computing in AMX_PREC_BF16X3 (block-maximum statistic of the "
-                                 "weights %.2f > 4.0; tuning mx_fallback=off keeps f16mx)\n", mx_ratio);
-            prec = AMX_PREC_BF16X3;
-        }
-    }
-    amx_ffnn* h  = new amx_ffnn;
-    h->ctx       = ctx;
-    h->n_layers  = m->n_layers;
-    h->precision = prec;
-    h->requested_precision = m->precision;
-    h->mx_block_ratio      = mx_ratio;
-    h->class_mapped = class_mapped;
-    h->gemm_cfg        = t_tile;
-    h->use_graphs      = t_graph;
-    h->gemm_persistent = t_persistent;
-    h->chunk           = t_chunk;
-    h->mx_dbg          = t_mx_dbg;
-    h->mx_stagger      = t_stagger;
-    h->mx_ksplit       = t_ksplit;
-    h->group_t         = t_group_t;
-    h->group_n         = t_group_n;
-    hipSetDevice(ctx->device);
-    const int kmult = prec == AMX_PREC_F16MX ? amx::mx::TK : (prec != AMX_PREC_FP32) ? amx::BK : amx::FK;
-    if (prec == AMX_PREC_F16MX) {
-        if (hipHostMalloc((void**)&h->h_overflow, 4, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&h->d_overflow, h->h_overflow, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            amx::set_error("amx_ffnn_create: cannot allocate the overflow flag");
-            amx_ffnn_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
-        *h->h_overflow = 0;
-    }
+    return AMX_OK;
+}
+
+// dimensions and padded dimensions of every layer, in the handle's precision
+void set_shapes(amx_ffnn* h, const amx_ffnn_model* m, const LayerParams& p, const MaxoutSpec& mo) {
+    const int kmult = h->is_mx() ? amx::mx::TK : h->mfma_bf16() ? amx::BK : amx::FK;
     long      best_flops = -1;
-    h->mo_groups = mo_groups;
+    h->n_layers  = m->n_layers;
+    h->mo_groups = mo.groups;
     for (int l = 0; l < m->n_layers; ++l) {
         h->in.push_back(m->in_dim[l]);
-        h->out.push_back(out_dim[l]);
+        h->out.push_back(p.out_dim[l]);
         h->act.push_back(m->activation[l]);
-        if (mo_groups[l] > 0)
-            h->mo_width = std::max(h->mo_width, out_dim[l]);
+        if (mo.groups[l] > 0)
+            h->mo_width = std::max(h->mo_width, p.out_dim[l]);
         // hidden activations are stored with a row stride of Npad(l-1) >= Kpad(l)
         h->Kpad.push_back(pad_to(m->in_dim[l], kmult));
-        h->Npad.push_back(pad_to(out_dim[l], amx::PAD_NT));
+        h->Npad.push_back(pad_to(p.out_dim[l], amx::PAD_NT));
         if (l + 1 < m->n_layers)
             h->max_hidden_pad = std::max(h->max_hidden_pad, h->Npad[l]);
-        long fl = (long)m->in_dim[l] * out_dim[l];
+        long fl = (long)m->in_dim[l] * p.out_dim[l];
         if (fl > best_flops) {
             best_flops       = fl;
             h->largest_layer = l;
         }
     }
-    for (int l = 0; l < m->n_layers; ++l) {
-        const int    K = h->in[l], N = h->out[l], Kp = h->Kpad[l], Np = h->Npad[l];
-        const float* W = Wl[l];
-        void*        d = nullptr;
-        if (prec == AMX_PREC_F16MX) {
-            for (size_t i = 0; i < (size_t)N * K; ++i)
-                if (std::fabs(W[i]) >= 65520.f) {  // not a number a trained layer holds; f16 cannot
-                    amx::set_error("amx_ffnn_create: layer %d holds a weight outside the f16 range (%g): use AMX_PREC_BF16X3", l, (double)W[i]);
-                    h->d_W.push_back(nullptr);
-                    amx_ffnn_destroy(h);
-                    return AMX_ERR_INVALID;
-                }
-            std::vector<unsigned char> pk;
-            amx::mx::pack_weights_host(W, N, K, K, Np, Kp / 32, pk);
-            if (hipMalloc(&d, pk.size()) != hipSuccess || hipMemcpy(d, pk.data(), pk.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                amx::set_error("amx_ffnn_create: device allocation of layer %d failed", l);
-                h->d_W.push_back(d);
-                amx_ffnn_destroy(h);
-                return AMX_ERR_DEVICE;
-            }
-        }
-        else if (prec == AMX_PREC_BF16X3) {
-            // rows [W_hi | W_lo], each plane Kp columns wide (zero padded); the rows that feed the layer are [X_hi | X_lo] with the
-            // lo plane at column xlo = Kpad (layer 0) or Npad of the layer below
-            std::vector<amx::bf16_t> pk((size_t)Np * 2 * Kp, 0);
-            for (int n = 0; n < N; ++n)
-                for (int k = 0; k < K; ++k) {
-                    const float       w  = W[(size_t)n * K + k];
-                    const amx::bf16_t hi = amx::f2bf_host(w);
-                    unsigned          hu = (unsigned)hi << 16;
-                    float             hf;
-                    memcpy(&hf, &hu, 4);
-                    pk[(size_t)n * 2 * Kp + k]      = hi;
-                    pk[(size_t)n * 2 * Kp + Kp + k] = amx::f2bf_host(w - hf);
-                }
-            if (hipMalloc(&d, pk.size() * 2) != hipSuccess || hipMemcpy(d, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                amx::set_error("amx_ffnn_create: device allocation of layer %d failed", l);
-                h->d_W.push_back(d);
-                amx_ffnn_destroy(h);
-                return AMX_ERR_DEVICE;
-            }
-        }
-        else if (prec == AMX_PREC_BF16) {
-            std::vector<amx::bf16_t> pk((size_t)Np * Kp, 0);
-            for (int n = 0; n < N; ++n)
-                for (int k = 0; k < K; ++k)
-                    pk[(size_t)n * Kp + k] = amx::f2bf_host(W[(size_t)n * K + k]);
-            if (hipMalloc(&d, pk.size() * 2) != hipSuccess || hipMemcpy(d, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                amx::set_error("amx_ffnn_create: device allocation of layer %d failed", l);
-                h->d_W.push_back(d);
-                amx_ffnn_destroy(h);
-                return AMX_ERR_DEVICE;
-            }
-        }
-        else {
-            std::vector<float> pk((size_t)Np * Kp, 0.f);
-            for (int n = 0; n < N; ++n)
-                memcpy(&pk[(size_t)n * Kp], W + (size_t)n * K, (size_t)K * 4);
-            if (hipMalloc(&d, pk.size() * 4) != hipSuccess || hipMemcpy(d, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-                amx::set_error("amx_ffnn_create: device allocation of layer %d failed", l);
-                h->d_W.push_back(d);
-                amx_ffnn_destroy(h);
-                return AMX_ERR_DEVICE;
-            }
-        }
-        h->d_W.push_back(d);
-        std::vector<float> b((size_t)Np, 0.f);
-        for (int n = 0; n < N; ++n) {
-            float v = bl[l] ? bl[l][n] : 0.f;
-            // removeLogPriorFromBias (Nn/LinearAndActivationLayer.hh:137-160): bias -= scale * prior
-            if (l == m->n_layers - 1 && prior && m->prior_scale != 0.f) {
-                float prod = m->prior_scale * prior[n];
-                v          = v - prod;
-            }
-            b[n] = v;
-        }
-        if (l == m->n_layers - 1) {
-            h->h_Wout.assign(W, W + (size_t)N * K);
-            h->h_bout.assign(b.begin(), b.begin() + N);
-        }
-        float* db = nullptr;
-        if (hipMalloc((void**)&db, b.size() * 4) != hipSuccess || hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            amx::set_error("amx_ffnn_create: device allocation of bias %d failed", l);
-            h->d_bias.push_back(db);
-            amx_ffnn_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
-        h->d_bias.push_back(db);
+}
+
+// W [N x K] as the kernels of `precision` read it, zero padded to [Np x Kp]: f32 or bf16 rows, split bf16 rows [W_hi | W_lo] with each
+// plane Kp columns wide (the rows that feed the layer are [X_hi | X_lo] with the lo plane at column Kpad (layer 0) or Npad of the
+// layer below), or f16mx blocks
+std::vector<unsigned char> pack_weights(int precision, const float* W, int N, int K, int Np, int Kp) {
+    std::vector<unsigned char> pk;
+    if (precision == AMX_PREC_F16MX) {
+        amx::mx::pack_weights_host(W, N, K, K, Np, Kp / 32, pk);
+        return pk;
     }
-    // preprocessing vectors: the mean as given, the standard deviation as its f32 reciprocal (divideRowsByScalars' (T)1.0 / s)
-    const int K0 = m->in_dim[0];
-    h->pre.n     = n_pre;
-    for (int i = 0; i < n_pre; ++i) {
+    if (precision == AMX_PREC_FP32) {
+        pk.assign((size_t)Np * Kp * 4, 0);
+        for (int n = 0; n < N; ++n)
+            memcpy(&pk[(size_t)n * Kp * 4], W + (size_t)n * K, (size_t)K * 4);
+        return pk;
+    }
+    const bool   x3 = precision == AMX_PREC_BF16X3;
+    const size_t ld = x3 ? 2 * (size_t)Kp : (size_t)Kp;
+    pk.assign((size_t)Np * ld * 2, 0);
+    auto put = [&](size_t i, amx::bf16_t v) { memcpy(&pk[2 * i], &v, 2); };
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < K; ++k) {
+            const float       w  = W[(size_t)n * K + k];
+            const amx::bf16_t hi = amx::f2bf_host(w);
+            put(n * ld + k, hi);
+            if (x3) {
+                unsigned hu = (unsigned)hi << 16;
+                float    hf;
+                memcpy(&hf, &hu, 4);
+                put(n * ld + Kp + k, amx::f2bf_host(w - hf));
+            }
+        }
+    return pk;
+}
+
+// the bias [Np] (zero padded; NULL: zeros), prior != NULL: removeLogPriorFromBias (Nn/LinearAndActivationLayer.hh:137-160), bias -= scale * prior
+std::vector<float> fold_bias(const float* bias, const float* prior, float prior_scale, int N, int Np) {
+    std::vector<float> b((size_t)Np, 0.f);
+    for (int n = 0; n < N; ++n) {
+        float v = bias ? bias[n] : 0.f;
+        if (prior) {
+            float prod = prior_scale * prior[n];
+            v          = v - prod;
+        }
+        b[n] = v;
+    }
+    return b;
+}
+
+int upload_layer(amx_ffnn* h, const amx_ffnn_model* m, const LayerParams& p, int l) {
+    const int    K = h->in[l], N = h->out[l];
+    const float* W = p.W[l];
+    if (h->is_mx())  // (before anything of this layer is uploaded)
+        for (size_t i = 0; i < (size_t)N * K; ++i)
+            AMX_REQUIRE(!(std::fabs(W[i]) >= 65520.f), AMX_ERR_INVALID,  // not a number a trained layer holds; f16 cannot
+                        "amx_ffnn_create: layer %d holds a weight outside the f16 range (%g): use AMX_PREC_BF16X3", l, (double)W[i]);
+    const std::vector<unsigned char> pk = pack_weights(h->precision, W, N, K, h->Npad[l], h->Kpad[l]);
+    AMX_TRY(h->d_W[l].upload(pk.data(), pk.size()));
+    const bool               last = l == h->n_layers - 1;
+    const std::vector<float> b    = fold_bias(p.bias[l], last && m->prior_scale != 0.f ? p.prior : nullptr, m->prior_scale, N, h->Npad[l]);
+    if (last) {
+        h->h_Wout.assign(W, W + (size_t)N * K);
+        h->h_bout.assign(b.begin(), b.begin() + N);
+    }
+    return h->d_bias[l].upload(b.data(), b.size());
+}
+
+// preprocessing vectors: the mean as given, the standard deviation as its f32 reciprocal (divideRowsByScalars' (T)1.0 / s)
+int upload_preprocessing(amx_ffnn* h, const amx_ffnn_layers* ext) {
+    const int K0 = h->in[0];
+    h->pre.n     = ext ? ext->n_pre : 0;
+    h->d_pre     = std::vector<amx::DevBuf<float>>((size_t)h->pre.n);
+    for (int i = 0; i < h->pre.n; ++i) {
         h->pre.type[i] = ext->pre_type[i];
         if (ext->pre_type[i] != AMX_NN_PRE_MEAN_AND_VARIANCE)
             continue;
@@ -2406,39 +2372,69 @@ int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
             mr[k]      = ext->pre_mean[i][k];
             mr[K0 + k] = 1.0f / ext->pre_stddev[i][k];
         }
-        float* d = nullptr;
-        if (hipMalloc((void**)&d, mr.size() * 4) != hipSuccess || hipMemcpy(d, mr.data(), mr.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(d);
-            amx::set_error("amx_ffnn_create_ex: device allocation of preprocessing layer %d failed", i);
-            amx_ffnn_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
-        h->d_pre.push_back(d);
-        h->pre.mean[i] = d;
-        h->pre.rstd[i] = d + K0;
+        AMX_TRY(h->d_pre[i].upload(mr.data(), mr.size()));
+        h->pre.mean[i] = h->d_pre[i].get();
+        h->pre.rstd[i] = h->d_pre[i].get() + K0;
     }
-    // maxout groups: first unit and size of each
-    h->d_mo_off.assign((size_t)m->n_layers, nullptr);
-    h->d_mo_size.assign((size_t)m->n_layers, nullptr);
-    for (int l = 0; l < m->n_layers; ++l) {
-        const int G = mo_groups[l];
+    return AMX_OK;
+}
+
+// maxout groups: first unit and size of each
+int upload_maxout(amx_ffnn* h, const MaxoutSpec& mo) {
+    h->d_mo_off  = std::vector<amx::DevBuf<int>>((size_t)h->n_layers);
+    h->d_mo_size = std::vector<amx::DevBuf<int>>((size_t)h->n_layers);
+    for (int l = 0; l < h->n_layers; ++l) {
+        const int G = mo.groups[l];
         if (G == 0)
             continue;
         std::vector<int> off((size_t)G, 0);
         for (int g = 1; g < G; ++g)
-            off[g] = off[g - 1] + mo_size[l][g - 1];
-        if (hipMalloc((void**)&h->d_mo_off[l], (size_t)G * 4) != hipSuccess || hipMalloc((void**)&h->d_mo_size[l], (size_t)G * 4) != hipSuccess ||
-            hipMemcpy(h->d_mo_off[l], off.data(), (size_t)G * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->d_mo_size[l], mo_size[l].data(), (size_t)G * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            amx::set_error("amx_ffnn_create_ex: device allocation of the maxout behind layer %d failed", l);
-            amx_ffnn_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
+            off[g] = off[g - 1] + mo.size[l][g - 1];
+        AMX_TRY(h->d_mo_off[l].upload(off.data(), (size_t)G));
+        AMX_TRY(h->d_mo_size[l].upload(mo.size[l].data(), (size_t)G));
     }
-    size_split_k_workspace(h);
-    *out = h;
+    return AMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amx_ffnn_create(amx_ctx* ctx, const amx_ffnn_model* m, amx_ffnn** out) {
+    return amx_ffnn_create_ex(ctx, m, nullptr, out);
+}
+
+int amx_ffnn_create_ex(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_layers* ext, amx_ffnn** out) {
+    AMX_REQUIRE(ctx && m && out, AMX_ERR_INVALID, "amx_ffnn_create: NULL argument");
+    *out = nullptr;
+    AMX_REQUIRE(m->n_layers >= 1 && m->in_dim && m->out_dim && m->W && m->bias && m->activation, AMX_ERR_INVALID,
+                "amx_ffnn_create: empty network");
+    AMX_REQUIRE(m->precision == AMX_PREC_FP32 || m->precision == AMX_PREC_BF16 || m->precision == AMX_PREC_BF16X3 ||
+                        m->precision == AMX_PREC_F16MX,
+                AMX_ERR_INVALID, "amx_ffnn_create: unknown precision");
+    MaxoutSpec  mo;
+    LayerParams p;
+    AMX_TRY(check_extension(m, ext, &mo));
+    AMX_TRY(check_model(m, mo.groups));
+    AMX_TRY(remap_classes(m, &p));
+    std::unique_ptr<amx_ffnn> h(new amx_ffnn);
+    h->ctx          = ctx;
+    h->class_mapped = m->class_to_output != nullptr;
+    bool mx_fallback_auto = true;
+    AMX_TRY(parse_tuning(m, h.get(), &mx_fallback_auto));
+    AMX_TRY(choose_precision(m, p, mx_fallback_auto, h.get()));
+    set_shapes(h.get(), m, p, mo);
+    hipSetDevice(ctx->device);
+    if (h->is_mx())
+        AMX_TRY(h->overflow.create());
+    h->d_W    = std::vector<amx::DevBuf<unsigned char>>((size_t)m->n_layers);
+    h->d_bias = std::vector<amx::DevBuf<float>>((size_t)m->n_layers);
+    for (int l = 0; l < m->n_layers; ++l)
+        AMX_TRY(upload_layer(h.get(), m, p, l));
+    AMX_TRY(upload_preprocessing(h.get(), ext));
+    AMX_TRY(upload_maxout(h.get(), mo));
+    size_split_k_workspace(h.get());
+    *out = h.release();
     return AMX_OK;
 }
 
@@ -2446,33 +2442,6 @@ void amx_ffnn_destroy(amx_ffnn* h) {
     if (!h)
         return;
     hipSetDevice(h->ctx->device);
-    for (void* p : h->d_W)
-        hipFree(p);
-    for (float* p : h->d_bias)
-        hipFree(p);
-    hipFree(h->d_in);
-    hipFree(h->d_act[0]);
-    hipFree(h->d_act[1]);
-    hipFree(h->d_Wout);
-    hipFree(h->d_bout);
-    hipFree(h->d_rowstat);
-    hipFree(h->d_part_min);
-    hipFree(h->d_part_idx);
-    hipFree(h->d_host_f);
-    hipFree(h->d_host_s);
-    if (h->h_overflow)
-        hipHostFree(h->h_overflow);
-    hipFree(h->d_ks_ws);
-    hipFree(h->d_mo);
-    for (float* p : h->d_pre)
-        hipFree(p);
-    for (int* p : h->d_mo_off)
-        hipFree(p);
-    for (int* p : h->d_mo_size)
-        hipFree(p);
-    for (auto& kv : h->graphs)
-        if (kv.second)  // nullptr marks a signature seen once
-            hipGraphExecDestroy(kv.second);
     delete h;
 }
 
@@ -2492,81 +2461,11 @@ extern "C" int amx_internal_best_state_reduce(amx_ctx* ctx, const float* part_mi
     return AMX_OK;
 }
 
-static int ffnn_score_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
-                               uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev);
-
-static int ffnn_score_impl(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
-                           uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev) {
-    AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_ffnn_score_dev: NULL handle");
-    AMX_REQUIRE(T >= 0, AMX_ERR_INVALID, "amx_ffnn_score_dev: negative frame count");
-    if (T == 0)
-        return AMX_OK;
-    AMX_REQUIRE(feats_dev && scores_dev, AMX_ERR_INVALID, "amx_ffnn_score_dev: NULL buffer");
-    AMX_REQUIRE(feats_stride >= h->in[0], AMX_ERR_INVALID, "amx_ffnn_score_dev: feature stride %d < input dimension %d", feats_stride, h->in[0]);
-    AMX_REQUIRE(!h->overflowed(), AMX_ERR_STATE,
-                "amx_ffnn_score_dev: a feature or hidden activation left the f16 range (|v| >= 65520) in an earlier pass of this AMX_PREC_F16MX "
-                "handle; its scores were not valid -- create the scorer with AMX_PREC_BF16X3");
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    // Small batches (the decoder's ring buffer: 256 ... 1024 frames, the same device buffers every time): replay the pass as a
-    // HIP graph.  Not while profiling (the per-launch events are not part of the graph).
-    const bool graphable = h->use_graphs && !h->ctx->profiling && T <= 4096 && h->mfma_bf16();
-    if (!graphable)
-        return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-    const amx_ffnn::GraphKey key{feats_dev, scores_dev, best_state_dev, counts_dev, score_sum_dev, h->ctx->stream, feats_stride, T, stats ? 1 : 0};
-    auto                     it = h->graphs.find(key);
-    if (it == h->graphs.end()) {
-        // first call with this signature: run it plainly once (sizes the workspace, sets kernel attributes), capture the second time.
-        // The cap is checked HERE: a caller that slides its pointers through a large buffer never repeats a signature, and its
-        // "seen once" entries would otherwise grow the map for the life of the handle.
-        if (h->graphs.size() >= 64) {
-            for (auto& kv : h->graphs)
-                if (kv.second)
-                    hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            h->use_graphs = 0;
-            return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-        }
-        static const hipGraphExec_t kSeenOnce = nullptr;
-        h->graphs[key] = kSeenOnce;
-        return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-    }
-    if (it->second == nullptr) {
-        if (h->graphs.size() > 64) {  // a caller that keeps changing buffers: stop caching
-            h->use_graphs = 0;
-            return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-        }
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(h->ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            h->use_graphs = 0;
-            return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-        }
-        const int  r   = ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-        const bool ok  = hipStreamEndCapture(h->ctx->stream, &g) == hipSuccess && r == AMX_OK && g != nullptr;
-        hipGraphExec_t ex = nullptr;
-        if (!ok || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (g)
-                hipGraphDestroy(g);
-            h->use_graphs = 0;  // capture is not available on this stream: plain launches from now on
-            return ffnn_score_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev);
-        }
-        hipGraphDestroy(g);
-        it->second = ex;
-    }
-    AMX_HIP(hipGraphLaunch(it->second, h->ctx->stream));
-    return AMX_OK;
-}
+static const char* const kOverflowText =
+        "%s: a feature or hidden activation left the f16 range (|v| >= 65520, inf or NaN) in a pass of this AMX_PREC_F16MX handle; the scores of "
+        "that pass are not valid -- create the scorer with AMX_PREC_BF16X3";
 
 // hidden_out != nullptr: run the hidden layers only and export the last hidden activation as f32 [T x hidden_dim]
-static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
-                         uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev, float* hidden_out);
-
-static int ffnn_score_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
-                               uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev) {
-    return ffnn_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev, nullptr);
-}
-
 static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
                          uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev, float* hidden_out) {
     const int chunk = h->chunk;  // frames per pass (workspace: 2 x chunk x max_hidden x 2 B)
@@ -2574,44 +2473,29 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int Tc   = std::min(chunk, T - t0);
         const int Tpad = pad_to(Tc, amx::PAD_NT);
-        int       r    = ensure_workspace(h, Tpad);
-        if (r != AMX_OK)
-            return r;
-        const float* x = feats_dev + (size_t)t0 * feats_stride;
+        AMX_TRY(ensure_workspace(h, Tpad));
+        int          r    = AMX_OK;
+        void* const  d_in = h->d_in.get();
+        const float* x    = feats_dev + (size_t)t0 * feats_stride;
         const amx::FeatSrc feats{x, feats_stride, h->pre};  // the preprocessing layers run inside the pack kernel
         {
             amx::ScopedKernelTimer timer(h->ctx, "ffnn_pack");
             if (h->pre.n > 0)
-                pack_operand(h, feats, Tc, h->in[0], h->d_in, h->Kpad[0], Tpad);
+                pack_operand(h, feats, Tc, h->in[0], d_in, h->Kpad[0], Tpad);
             else  // a network without preprocessing layers packs its features with the kernels it always had
-                pack_operand(h, amx::RawSrc{x, feats_stride}, Tc, h->in[0], h->d_in, h->Kpad[0], Tpad);
+                pack_operand(h, amx::RawSrc{x, feats_stride}, Tc, h->in[0], d_in, h->Kpad[0], Tpad);
             AMX_HIP(hipGetLastError());
         }
-        const void* cur = h->d_in;
+        const void* cur = d_in;
         const bool  x3  = h->precision == AMX_PREC_BF16X3;
-        const int   planes = x3 ? 2 : 1;  // split bf16: rows are [hi plane | lo plane]
-        int         ldx    = h->is_mx() ? h->Kpad[0] / 32 : planes * h->Kpad[0];  // f16mx: K-tiles per 256-row block of the operand
+        int         ldx = operand_stride(h, h->Kpad[0]);
         const bool  fused = stats && h->mfma_bf16();
-        h->cur_part_min = nullptr;
-        h->cur_part_idx = nullptr;
+        ArgminPart  part;
         if (fused) {
             const size_t need = (size_t)(h->Npad[L - 1] / 128) * Tpad;  // >= n-tiles of any configuration
-            if (need > h->part_cap) {
-                for (auto& kv : h->graphs)  // captured passes hold the old addresses
-                    if (kv.second)
-                        hipGraphExecDestroy(kv.second);
-                h->graphs.clear();
-                hipFree(h->d_part_min);
-                hipFree(h->d_part_idx);
-                h->d_part_min = nullptr;
-                h->d_part_idx = nullptr;
-                h->part_cap   = 0;
-                AMX_HIP(hipMalloc((void**)&h->d_part_min, need * 4));
-                AMX_HIP(hipMalloc((void**)&h->d_part_idx, need * 4));
-                h->part_cap = need;
-            }
-            h->cur_part_min = h->d_part_min;
-            h->cur_part_idx = h->d_part_idx;
+            AMX_TRY(grow(h, h->d_part_min, need));
+            AMX_TRY(grow(h, h->d_part_idx, need));
+            part = {h->d_part_min.get(), h->d_part_idx.get()};
         }
         for (int l = 0; l < L; ++l) {
             if (h->is_mx() && hidden_out && l >= L - 2) {
@@ -2657,11 +2541,12 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
             }
             else if (l == L - 1) {
                 float* sc = scores_dev + (size_t)t0 * h->out[l];
-                r         = launch_layer<true>(h, l, cur, ldx, sc, h->out[l], Tc, Tpad);
+                int    ntn = 0;
+                r          = launch_layer<true>(h, l, cur, ldx, sc, h->out[l], Tc, Tpad, part, &ntn);
                 if (r == AMX_OK && fused) {
                     amx::ScopedKernelTimer timer(h->ctx, "stats");
                     hipLaunchKernelGGL(amx::best_state_reduce_kernel, dim3((Tc + 63) / 64), dim3(256), 0, h->ctx->stream,
-                                       h->d_part_min, h->d_part_idx, h->cur_ntn, Tpad, Tc, best_state_dev ? best_state_dev + t0 : nullptr,
+                                       part.min, part.idx, ntn, Tpad, Tc, best_state_dev ? best_state_dev + t0 : nullptr,
                                        counts_dev, score_sum_dev);
                     AMX_HIP(hipGetLastError());
                 }
@@ -2670,29 +2555,43 @@ static int ffnn_launches(amx_ffnn* h, const float* feats_dev, int feats_stride, 
                                                  score_sum_dev);
             }
             else if (h->mo_groups[l] > 0) {  // maxout: the next layer's operand [Tpad x Kpad(l + 1)] in the handle's format
-                void* dst = h->d_act[l & 1];
+                void* dst = h->d_act[l & 1].get();
                 r         = launch_maxout_layer(h, l, cur, ldx, dst, h->Kpad[l + 1], Tc, Tpad, Tpad, false);
                 cur       = dst;
-                ldx       = h->is_mx() ? h->Kpad[l + 1] / 32 : planes * h->Kpad[l + 1];
+                ldx       = operand_stride(h, h->Kpad[l + 1]);
             }
             else {
-                void* dst = h->d_act[l & 1];  // split bf16: the epilogue applies the activation and writes both planes
-                r         = launch_layer<false>(h, l, cur, ldx, dst, planes * h->Npad[l], Tc, Tpad);
+                void* dst = h->d_act[l & 1].get();  // split bf16: the epilogue applies the activation and writes both planes
+                r         = launch_layer<false>(h, l, cur, ldx, dst, (x3 ? 2 : 1) * h->Npad[l], Tc, Tpad);
                 cur       = dst;
-                ldx       = h->is_mx() ? h->Npad[l] / 32 : planes * h->Npad[l];
+                ldx       = operand_stride(h, h->Npad[l]);
             }
             if (r != AMX_OK)
                 return r;
         }
     }
-    h->cur_part_min = nullptr;
-    h->cur_part_idx = nullptr;
     return AMX_OK;
 }
 
-static const char* const kOverflowText =
-        "%s: a feature or hidden activation left the f16 range (|v| >= 65520, inf or NaN) in a pass of this AMX_PREC_F16MX handle; the scores of "
-        "that pass are not valid -- create the scorer with AMX_PREC_BF16X3";
+static int ffnn_score_impl(amx_ffnn* h, const float* feats_dev, int feats_stride, int T, float* scores_dev, bool stats,
+                           uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev) {
+    AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_ffnn_score_dev: NULL handle");
+    AMX_REQUIRE(T >= 0, AMX_ERR_INVALID, "amx_ffnn_score_dev: negative frame count");
+    if (T == 0)
+        return AMX_OK;
+    AMX_REQUIRE(feats_dev && scores_dev, AMX_ERR_INVALID, "amx_ffnn_score_dev: NULL buffer");
+    AMX_REQUIRE(feats_stride >= h->in[0], AMX_ERR_INVALID, "amx_ffnn_score_dev: feature stride %d < input dimension %d", feats_stride, h->in[0]);
+    AMX_REQUIRE(!h->overflowed(), AMX_ERR_STATE, kOverflowText, "amx_ffnn_score_dev");
+    AMX_HIP(hipSetDevice(h->ctx->device));
+    auto pass = [&](bool) { return ffnn_launches(h, feats_dev, feats_stride, T, scores_dev, stats, best_state_dev, counts_dev, score_sum_dev, nullptr); };
+    // Small batches (the decoder's ring buffer: 256 ... 1024 frames, the same device buffers every time): replay the pass as a
+    // HIP graph.  Not while profiling (the per-launch events are not part of the graph).
+    if (!(h->graphs.use_graphs && !h->ctx->profiling && T <= 4096 && h->mfma_bf16()))
+        return pass(false);
+    const amx_ffnn::GraphKey key{feats_dev, scores_dev, best_state_dev, counts_dev, score_sum_dev, h->ctx->stream, feats_stride, T, stats ? 1 : 0};
+    amx::GraphCache<amx_ffnn::GraphKey>::Ran ran;
+    return h->graphs.run(key, h->ctx->stream, pass, &ran);
+}
 
 int amx_ffnn_precision(const amx_ffnn* h, double* mx_block_ratio) {
     if (!h)
@@ -2737,14 +2636,12 @@ int amx_ffnn_score_on_demand_dev(amx_ffnn* h, const float* act_dev, int n_pairs,
     AMX_REQUIRE(act_dev && frame_dev && emission_dev && scores_dev, AMX_ERR_INVALID, "amx_ffnn_score_on_demand_dev: NULL buffer");
     AMX_REQUIRE(!h->overflowed(), AMX_ERR_STATE, kOverflowText, "amx_ffnn_score_on_demand_dev");   // its hidden activations come from this handle
     AMX_HIP(hipSetDevice(h->ctx->device));
-    if (!h->d_Wout) {  // OnDemandFeatureScorer::init pops the output layer and keeps its parameters apart: upload them on first use
-        AMX_HIP(hipMalloc((void**)&h->d_Wout, h->h_Wout.size() * 4));
-        AMX_HIP(hipMalloc((void**)&h->d_bout, h->h_bout.size() * 4));
-        AMX_HIP(hipMemcpy(h->d_Wout, h->h_Wout.data(), h->h_Wout.size() * 4, hipMemcpyHostToDevice));
-        AMX_HIP(hipMemcpy(h->d_bout, h->h_bout.data(), h->h_bout.size() * 4, hipMemcpyHostToDevice));
+    if (!h->d_bout.get()) {  // OnDemandFeatureScorer::init pops the output layer and keeps its parameters apart: upload them on first use
+        AMX_TRY(h->d_Wout.upload(h->h_Wout.data(), h->h_Wout.size()));
+        AMX_TRY(h->d_bout.upload(h->h_bout.data(), h->h_bout.size()));
     }
     amx::ScopedKernelTimer timer(h->ctx, "ffnn_on_demand");
-    hipLaunchKernelGGL(amx::on_demand_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, h->ctx->stream, act_dev, h->in.back(), h->d_Wout, h->d_bout,
+    hipLaunchKernelGGL(amx::on_demand_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, h->ctx->stream, act_dev, h->in.back(), h->d_Wout.get(), h->d_bout.get(),
                        frame_dev, emission_dev, n_pairs, scores_dev);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
@@ -2788,16 +2685,12 @@ int amx_ffnn_forward_dev(amx_ffnn* h, const float* feats_dev, int feats_stride, 
         AMX_HIP(hipGetLastError());
         return AMX_OK;
     }
-    if (T > h->rowstat_cap) {
-        hipFree(h->d_rowstat);
-        h->d_rowstat   = nullptr;
-        h->rowstat_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_rowstat, (size_t)2 * T * 4));
-        h->rowstat_cap = T;
-    }
-    hipLaunchKernelGGL(amx::top_negexp_kernel, dim3(T), dim3(256), 0, st, out_dev, n, h->d_rowstat);
-    hipLaunchKernelGGL(amx::top_rowsum_kernel, dim3((T + 63) / 64), dim3(64), 0, st, out_dev, T, n, h->d_rowstat + h->rowstat_cap);
-    hipLaunchKernelGGL(amx::top_finish_kernel, dim3(blocks), dim3(256), 0, st, out_dev, total, n, (const float*)(h->d_rowstat + h->rowstat_cap));
+    AMX_TRY(h->d_rowstat.reserve((size_t)2 * T));  // (these launches are in no recorded pass: no graph holds the address)
+    float* const row_max = h->d_rowstat.get();
+    float* const row_sum = row_max + h->d_rowstat.capacity() / 2;
+    hipLaunchKernelGGL(amx::top_negexp_kernel, dim3(T), dim3(256), 0, st, out_dev, n, row_max);
+    hipLaunchKernelGGL(amx::top_rowsum_kernel, dim3((T + 63) / 64), dim3(64), 0, st, out_dev, T, n, row_sum);
+    hipLaunchKernelGGL(amx::top_finish_kernel, dim3(blocks), dim3(256), 0, st, out_dev, total, n, (const float*)row_sum);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }
@@ -2819,40 +2712,23 @@ int amx_ffnn_score(amx_ffnn* h, const float* feats_host, int T, float* scores_ho
     // ffnn_score_impl replay its HIP graph)
     hipStream_t  st = h->ctx->stream;
     const size_t nf = (size_t)T * h->in[0], ns = (size_t)T * h->out.back();
-    auto grow = [h](float** p, size_t* cap, size_t need) {
-        if (need <= *cap)
-            return true;
-        for (auto& kv : h->graphs)  // captured passes may hold the old staging addresses: their keys would never be hit again
-            if (kv.second)
-                hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-        hipFree(*p);
-        *p   = nullptr;
-        *cap = 0;
-        if (hipMalloc((void**)p, need * 4) != hipSuccess)
-            return false;
-        *cap = need;
-        return true;
-    };
-    if (!grow(&h->d_host_f, &h->host_f_cap, nf) || !grow(&h->d_host_s, &h->host_s_cap, ns)) {
-        (void)hipGetLastError();
-        amx::set_error("amx_ffnn_score: out of device memory");
-        return AMX_ERR_DEVICE;
-    }
-    if (hipMemcpyAsync(h->d_host_f, feats_host, nf * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
+    // (captured passes may hold the old staging addresses: their keys would never be hit again)
+    AMX_TRY(grow(h, h->d_host_f, nf));
+    AMX_TRY(grow(h, h->d_host_s, ns));
+    float* const d_f = h->d_host_f.get();
+    float* const d_s = h->d_host_s.get();
+    if (hipMemcpyAsync(d_f, feats_host, nf * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
         amx::set_error("amx_ffnn_score: H2D copy failed");
         return AMX_ERR_DEVICE;
     }
-    int r = amx_ffnn_score_dev(h, h->d_host_f, h->in[0], T, h->d_host_s);
+    int r = amx_ffnn_score_dev(h, d_f, h->in[0], T, d_s);
     if (r != AMX_OK)
         return r;
-    if (hipMemcpyAsync(scores_host, h->d_host_s, ns * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    if (hipMemcpyAsync(scores_host, d_s, ns * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         amx::set_error("amx_ffnn_score: D2H copy / kernel execution failed: %s", hipGetErrorString(hipGetLastError()));
         return AMX_ERR_DEVICE;
     }
-    AMX_REQUIRE(!h->overflowed(), AMX_ERR_STATE,
-                "amx_ffnn_score: a feature or hidden activation left the f16 range (|v| >= 65520); the scores are not valid -- create the "
-                "scorer with AMX_PREC_BF16X3");
+    AMX_REQUIRE(!h->overflowed(), AMX_ERR_STATE, kOverflowText, "amx_ffnn_score");
     return AMX_OK;
 }
 

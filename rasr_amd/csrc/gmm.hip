@@ -1614,66 +1614,7 @@ struct GraphKey {
     }
 };
 
-// Small-batch passes on unchanged device buffers (the decoder's ring buffer), recorded once and replayed as HIP graphs: the
-// amx_gmm_model.tuning graph=1 option (default 0: every pass is launched plainly).  A recorded pass holds the addresses of the
-// handle's workspaces, so whoever moves one of those calls clear() first.
-struct GraphCache {
-    enum Ran { kPlain, kRecorded, kReplayed };
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    int                                use_graphs = 0;
-    GraphCache() = default;
-    GraphCache(const GraphCache&)            = delete;
-    GraphCache& operator=(const GraphCache&) = delete;
-    ~GraphCache() { clear(); }
-    void clear() {
-        for (auto& kv : graphs)
-            if (kv.second)
-                hipGraphExecDestroy(kv.second);
-        graphs.clear();
-    }
-    // pass(capturing) enqueues the launches.  First call with a key: plain (it sizes the workspaces) and remembered; second call:
-    // captured, instantiated and launched; later calls: launched.  A caller that never repeats a signature (64 of them) or a
-    // stream that cannot capture switches graphs off.  *ran tells the caller which statistics the pass itself has kept.
-    template<class Pass>
-    int run(const GraphKey& key, hipStream_t stream, Pass&& pass, Ran* ran) {
-        *ran    = kPlain;
-        auto it = graphs.find(key);
-        if (it == graphs.end()) {
-            if (graphs.size() >= 64) {
-                clear();
-                use_graphs = 0;
-            }
-            else
-                graphs[key] = nullptr;
-            return pass(false);
-        }
-        hipGraphExec_t ex = it->second;
-        if (ex)
-            *ran = kReplayed;
-        else {
-            hipGraph_t g = nullptr;
-            if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                (void)hipGetLastError();
-                use_graphs = 0;
-                return pass(false);
-            }
-            const int  r  = pass(true);
-            const bool ok = hipStreamEndCapture(stream, &g) == hipSuccess && r == AMX_OK && g != nullptr;
-            if (!ok || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                if (g)
-                    hipGraphDestroy(g);
-                use_graphs = 0;
-                return pass(false);
-            }
-            hipGraphDestroy(g);
-            graphs[key] = ex;  // by key: a pass that had to grow a workspace has emptied the map
-            *ran        = kRecorded;
-        }
-        AMX_HIP(hipGraphLaunch(ex, stream));
-        return AMX_OK;
-    }
-};
+using GraphCache = amx::GraphCache<GraphKey>;
 
 struct amx_gmm {
     amx_ctx* ctx = nullptr;

@@ -375,3 +375,27 @@ def test_bf16x3_full_size_shard_properties(ctx, capsys):
     with capsys.disabled():
         print("\nbf16x3 shard sample parity:", json.dumps(rep))
     assert rep["bar_violations"] == 0 and rep["worst_pure_relative"] <= 1e-4 and rep["argmin_mismatches_outside_gap_rule"] == 0, rep
+
+
+def test_failed_creation_leaves_the_context_usable(ctx):
+    """A creation that fails hands back everything it took: (a) f16mx refuses a weight outside the f16 range when it reaches the LAST
+    layer, after the overflow word and two layers are on the device (mx_fallback=off: that one weight is a heavy tail, and the
+    default would compute in split bf16, which has no such limit); (b) bf16 refuses a class mapping that names an output twice.
+    After each, the valid scorer created in the same context gives the bits of one created before any failure."""
+    import rasr_amd
+    Ws, bs, acts, logp = synth.ffnn([64, 256, 256, 100], seed=33)
+    x = feats(300, 64, 34)
+    perm = np.random.Generator(np.random.PCG64(35)).permutation(100).astype(np.int32)
+    valid = {"f16mx": dict(precision="f16mx", tuning="mx_fallback=off"), "bf16": dict(precision="bf16", class_to_output=perm)}
+    want = {k: rasr_amd.NnBatchFeatureScorer(ctx, Ws, bs, acts, log_prior=logp, **kw).score(x).view(np.uint32) for k, kw in valid.items()}
+    bad_W = [w.copy() for w in Ws]
+    bad_W[-1][57, 123] = 7e4
+    twice = perm.copy()
+    twice[9] = twice[8]
+    cases = (("f16mx", bad_W, valid["f16mx"], "f16 range"), ("bf16", Ws, dict(valid["bf16"], class_to_output=twice), "one-to-one"))
+    for k, W, args, text in cases:
+        with pytest.raises(rasr_amd.AmxError) as e:
+            rasr_amd.NnBatchFeatureScorer(ctx, W, bs, acts, log_prior=logp, **args)
+        assert e.value.status == -1 and text in str(e.value), k
+        got = rasr_amd.NnBatchFeatureScorer(ctx, Ws, bs, acts, log_prior=logp, **valid[k]).score(x).view(np.uint32)
+        assert np.array_equal(got, want[k]), k
