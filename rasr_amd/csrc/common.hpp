@@ -102,11 +102,7 @@ struct amx_ctx {
     std::map<std::string, amx::ProfileSlot>  prof;
     int                                      n_cu = 0;
     int                                      contract = AMX_CONTRACT_OFF;   // amx_set_contract: which build of the reference the f32 arithmetic follows
-    // scratch for amx_stats_accumulate_dev
-    void*  scratch       = nullptr;
-    size_t scratch_bytes = 0;
-
-    int ensure_scratch(size_t bytes);
+    amx::DevBuf<char> scratch;   // amx_gather_scores: index pairs up, scores down
 };
 
 namespace amx {

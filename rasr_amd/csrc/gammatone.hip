@@ -18,7 +18,7 @@
 // (43 MB per 10 s of audio at 68 channels) never exists unless a caller asks for it.  gammatone_post_kernel finishes the frame.
 // The host side restates the node's coefficient design operation by operation (f32 members, double-overload libm calls,
 // std::complex<f32> division and abs).
-#include "common.hpp"
+#include "frontend_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -30,14 +30,11 @@ struct amx_gammatone {
     bool               fma = false;   // contract=fma (cfg.tuning, else the context's): the reference's default build
     int                channels = 0, cascade = 0, ti_len = 0, ti_shift = 0, si_channels = 0, n_out = 0;
     std::vector<float> cf, coef, ti_win, si_win, dct;
-    float *            d_coef = nullptr, *d_ti_win = nullptr, *d_si_win = nullptr, *d_dct = nullptr;
+    amx::DevBuf<float> d_coef, d_ti_win, d_si_win, d_dct;
     // per-call scratch
-    float*     d_ti = nullptr;
-    size_t     ti_cap = 0;
-    long long* d_off = nullptr;  // [2][n_seg + 1] sample / frame offsets
-    size_t     off_cap = 0;
-    float *    d_pcm = nullptr, *d_out = nullptr;  // staging of the host entry point
-    size_t     pcm_cap = 0, out_cap = 0;
+    amx::DevBuf<float>     d_ti;
+    amx::DevBuf<long long> d_off;         // [2][n_seg + 1] sample / frame offsets
+    amx::DevBuf<float>     d_pcm, d_out;  // staging of the host entry point
 };
 
 namespace amx {
@@ -281,47 +278,7 @@ float host_window(int type, int len, int i) {
     return (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / M));
 }
 
-template<class T>
-int gt_upload(T** dst, const std::vector<T>& src) {
-    AMX_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
-    if (!src.empty())
-        AMX_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return AMX_OK;
-}
-
-}  // namespace
-}  // namespace amx
-
-extern "C" {
-
-void amx_gammatone_default_cfg(amx_gammatone_cfg* c) {
-    if (!c)
-        return;
-    c->sample_rate     = 16000.0;
-    c->cascade         = 4;  // GammaToneNode's parameter defaults (Signal/GammaTone.cc:222-231)
-    c->min_freq        = 100;
-    c->max_freq        = 6000;
-    c->q               = 9.264491981582191;
-    c->channels        = 50;
-    c->cf_mode         = AMX_GAMMATONE_HUMAN;
-    c->warp_freq_break = 6600;
-    c->warping_factor  = 1;
-    c->ti_window       = AMX_WINDOW_HANNING;
-    c->ti_length_s     = 0.025;
-    c->ti_shift_s      = 0.01;
-    c->si_window       = AMX_WINDOW_HANNING;
-    c->si_length       = 0;
-    c->si_shift        = 1;
-    c->power           = 0;
-    c->n_ceps          = 0;
-    c->dct_normalize   = 0;
-    c->tuning          = nullptr;
-}
-
-int amx_gammatone_create(amx_ctx* ctx, const amx_gammatone_cfg* c, amx_gammatone** out) {
-    using namespace amx;
-    AMX_REQUIRE(c && out, AMX_ERR_INVALID, "amx_gammatone_create: NULL argument");
-    *out = nullptr;
+int check_cfg(const amx_gammatone_cfg* c) {
     AMX_REQUIRE(c->sample_rate > 0, AMX_ERR_INVALID, "gammatone: sample rate (%f) is not positive", c->sample_rate);
     AMX_REQUIRE(c->channels >= 2 && c->channels <= 4096, AMX_ERR_INVALID, "gammatone: channels (%d) must be in 2..4096", c->channels);
     AMX_REQUIRE(c->cascade >= 0 && c->cascade <= kGtMaxCascade, AMX_ERR_UNSUPPORTED, "gammatone: cascade (%d) must be in 0..%d", c->cascade,
@@ -331,31 +288,16 @@ int amx_gammatone_create(amx_ctx* ctx, const amx_gammatone_cfg* c, amx_gammatone
                         (c->si_window == AMX_WINDOW_HANNING || c->si_window == AMX_WINDOW_RECTANGULAR),
                 AMX_ERR_UNSUPPORTED, "gammatone: window type must be hanning or rectangular");
     AMX_REQUIRE(c->ti_length_s > 0 && c->ti_shift_s > 0, AMX_ERR_INVALID, "gammatone: temporal integration length / shift must be positive");
-    amx::Tuning tune;
-    std::string t_contract;
-    {
-        static const char* const keys[] = {"contract", nullptr};
-        static const char* const cons[] = {"off", "fma", nullptr};
-        if (!tune.parse(c->tuning, keys, "amx_gammatone_create") ||
-            !tune.get_word("contract", ctx && ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", cons, &t_contract, "amx_gammatone_create"))
-            return AMX_ERR_INVALID;
-    }
-    amx_gammatone* h = new amx_gammatone;
-    h->ctx           = ctx;
-    h->cfg           = *c;
-    h->cfg.tuning    = nullptr;   // the caller's string is not kept
-    h->fma           = t_contract == "fma";
-    const bool fma   = h->fma;
-    h->channels      = c->channels;
-    h->cascade       = c->cascade;
-    // ---- GammaTone::init with the node's f32 members
+    return AMX_OK;
+}
+
+// GammaTone::init with the node's f32 members: centre frequencies and the four coefficients of every channel
+int design_filters(amx_gammatone* h, const amx_gammatone_cfg* c) {
+    const bool  fma     = h->fma;
     const float minFreq = (float)c->min_freq, maxFreq = (float)c->max_freq, l = 24.7f, q = (float)c->q;
     GtWarp      warp{(float)c->warping_factor, (float)c->warp_freq_break, (float)(c->sample_rate / 2)};
-    if (!warp.check()) {  // GammaToneNode::init: error("Maybe there is a problem with the warping function.")
-        delete h;
-        amx::set_error("gammatone: Maybe there is a problem with the warping function.");
-        return AMX_ERR_INVALID;
-    }
+    // GammaToneNode::init: error("Maybe there is a problem with the warping function.")
+    AMX_REQUIRE(warp.check(), AMX_ERR_INVALID, "gammatone: Maybe there is a problem with the warping function.");
     warp.init(fma);
     float g[3];
     if (c->cf_mode == AMX_GAMMATONE_HUMAN) {
@@ -402,16 +344,17 @@ int amx_gammatone_create(amx_ctx* ctx, const amx_gammatone_cfg* c, amx_gammatone
         h->coef[f * 4 + 2] = b1;
         h->coef[f * 4 + 3] = b2;
     }
-    // ---- TemporalIntegration::init
+    return AMX_OK;
+}
+
+// TemporalIntegration::init, SpectralIntegration and the cosine transform: sizes, windows and the transform's matrix
+int set_integration(amx_gammatone* h, const amx_gammatone_cfg* c) {
     h->ti_len   = (int)(unsigned)std::rint(c->ti_length_s * c->sample_rate);
     h->ti_shift = (int)(unsigned)std::rint(c->ti_shift_s * c->sample_rate);
     bool ok     = h->ti_len >= 1 && h->ti_shift >= 1;
-    if (ok && (h->ti_len > kGtMaxWindow || (h->ti_len + h->ti_shift - 1) / h->ti_shift > kGtMaxOverlap)) {
-        delete h;
-        amx::set_error("gammatone: temporal integration window of %d samples every %d is not supported (<= %d samples, <= %d overlapping)",
-                       h->ti_len, h->ti_shift, kGtMaxWindow, kGtMaxOverlap);
-        return AMX_ERR_UNSUPPORTED;
-    }
+    AMX_REQUIRE(!ok || (h->ti_len <= kGtMaxWindow && (h->ti_len + h->ti_shift - 1) / h->ti_shift <= kGtMaxOverlap), AMX_ERR_UNSUPPORTED,
+                "gammatone: temporal integration window of %d samples every %d is not supported (<= %d samples, <= %d overlapping)",
+                h->ti_len, h->ti_shift, kGtMaxWindow, kGtMaxOverlap);
     h->si_channels = h->channels;
     if (ok && c->si_length > 0) {
         ok = c->si_shift >= 1 && c->si_length <= h->channels;
@@ -436,41 +379,82 @@ int amx_gammatone_create(amx_ctx* ctx, const amx_gammatone_cfg* c, amx_gammatone
             h->n_out = c->n_ceps;
         }
     }
-    if (!ok) {
-        delete h;
-        amx::set_error("gammatone: inconsistent integration / cosine transform sizes");
-        return AMX_ERR_INVALID;
-    }
+    AMX_REQUIRE(ok, AMX_ERR_INVALID, "gammatone: inconsistent integration / cosine transform sizes");
     h->ti_win.resize(h->ti_len);
     for (int i = 0; i < h->ti_len; ++i)
         h->ti_win[i] = host_window(c->ti_window, h->ti_len, i);
-    if (ctx) {
-        AMX_HIP(hipSetDevice(ctx->device));
-        int r;
-        if ((r = gt_upload(&h->d_coef, h->coef)) != AMX_OK || (r = gt_upload(&h->d_ti_win, h->ti_win)) != AMX_OK ||
-            (r = gt_upload(&h->d_si_win, h->si_win)) != AMX_OK || (r = gt_upload(&h->d_dct, h->dct)) != AMX_OK) {
-            amx_gammatone_destroy(h);
-            return r;
-        }
+    return AMX_OK;
+}
+
+int upload_tables(amx_gammatone* h) {
+    AMX_HIP(hipSetDevice(h->ctx->device));
+    AMX_TRY(h->d_coef.upload(h->coef.data(), h->coef.size()));
+    AMX_TRY(h->d_ti_win.upload(h->ti_win.data(), h->ti_win.size()));
+    AMX_TRY(h->d_si_win.upload(h->si_win.data(), h->si_win.size()));
+    return h->d_dct.upload(h->dct.data(), h->dct.size());
+}
+
+}  // namespace
+}  // namespace amx
+
+extern "C" {
+
+void amx_gammatone_default_cfg(amx_gammatone_cfg* c) {
+    if (!c)
+        return;
+    c->sample_rate     = 16000.0;
+    c->cascade         = 4;  // GammaToneNode's parameter defaults (Signal/GammaTone.cc:222-231)
+    c->min_freq        = 100;
+    c->max_freq        = 6000;
+    c->q               = 9.264491981582191;
+    c->channels        = 50;
+    c->cf_mode         = AMX_GAMMATONE_HUMAN;
+    c->warp_freq_break = 6600;
+    c->warping_factor  = 1;
+    c->ti_window       = AMX_WINDOW_HANNING;
+    c->ti_length_s     = 0.025;
+    c->ti_shift_s      = 0.01;
+    c->si_window       = AMX_WINDOW_HANNING;
+    c->si_length       = 0;
+    c->si_shift        = 1;
+    c->power           = 0;
+    c->n_ceps          = 0;
+    c->dct_normalize   = 0;
+    c->tuning          = nullptr;
+}
+
+int amx_gammatone_create(amx_ctx* ctx, const amx_gammatone_cfg* c, amx_gammatone** out) {
+    using namespace amx;
+    AMX_REQUIRE(c && out, AMX_ERR_INVALID, "amx_gammatone_create: NULL argument");
+    *out = nullptr;
+    AMX_TRY(check_cfg(c));
+    amx::Tuning tune;
+    std::string t_contract;
+    {
+        static const char* const keys[] = {"contract", nullptr};
+        static const char* const cons[] = {"off", "fma", nullptr};
+        if (!tune.parse(c->tuning, keys, "amx_gammatone_create") ||
+            !tune.get_word("contract", ctx && ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", cons, &t_contract, "amx_gammatone_create"))
+            return AMX_ERR_INVALID;
     }
-    *out = h;
+    std::unique_ptr<amx_gammatone> h(new amx_gammatone);
+    h->ctx        = ctx;
+    h->cfg        = *c;
+    h->cfg.tuning = nullptr;   // the caller's string is not kept
+    h->fma        = t_contract == "fma";
+    h->channels   = c->channels;
+    h->cascade    = c->cascade;
+    AMX_TRY(design_filters(h.get(), c));
+    AMX_TRY(set_integration(h.get(), c));
+    if (ctx)
+        AMX_TRY(upload_tables(h.get()));
+    *out = h.release();
     return AMX_OK;
 }
 
 void amx_gammatone_destroy(amx_gammatone* h) {
-    if (!h)
-        return;
-    if (h->ctx) {
+    if (h && h->ctx)
         hipSetDevice(h->ctx->device);
-        hipFree(h->d_coef);
-        hipFree(h->d_ti_win);
-        hipFree(h->d_si_win);
-        hipFree(h->d_dct);
-        hipFree(h->d_ti);
-        hipFree(h->d_off);
-        hipFree(h->d_pcm);
-        hipFree(h->d_out);
-    }
     delete h;
 }
 
@@ -486,12 +470,7 @@ int amx_gammatone_describe(const amx_gammatone* h, amx_gammatone_info* info) {
 }
 
 long amx_gammatone_n_frames(const amx_gammatone* h, long n) {
-    if (!h || n <= 0)
-        return 0;
-    const long reach = std::max(h->ti_len, h->ti_shift);  // TimeWindowBuffer::get / flush: WindowBuffer's rule
-    if (n <= reach)
-        return 1;
-    return (n - reach + h->ti_shift - 1) / h->ti_shift + 1;
+    return h ? amx::window_frames(n, h->ti_len, h->ti_shift) : 0;
 }
 
 int amx_gammatone_tables(const amx_gammatone* h, float* center_freq, float* coefficients) {
@@ -511,46 +490,21 @@ int amx_gammatone_run_batch_dev(amx_gammatone* h, int n_seg, const long* sample_
     AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_gammatone_run_batch_dev: host-only handle (created without a context)");
     if (n_seg == 0)
         return AMX_OK;
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    std::vector<long long> off(2 * ((size_t)n_seg + 1));
-    long long*             so = off.data();
-    long long*             fo = off.data() + n_seg + 1;
-    so[0] = sample_offsets[0];
-    fo[0] = 0;
-    for (int u = 0; u < n_seg; ++u) {
-        const long len = sample_offsets[u + 1] - sample_offsets[u];
-        AMX_REQUIRE(len >= 0 && len <= 0x7fffffffL, AMX_ERR_INVALID, "amx_gammatone_run_batch_dev: segment %d has invalid length %ld", u, len);
-        so[u + 1] = sample_offsets[u + 1];
-        fo[u + 1] = fo[u] + amx_gammatone_n_frames(h, len);
-    }
-    const long long frames = fo[n_seg];
+    long long frames = 0;
+    AMX_TRY(upload_segment_table(h->ctx, h->d_off, n_seg, sample_offsets, [h](long len) { return amx_gammatone_n_frames(h, len); },
+                                 "amx_gammatone_run_batch_dev", &frames));
     if (frames == 0)
         return AMX_OK;
-    if (off.size() > h->off_cap) {
-        hipFree(h->d_off);
-        h->d_off   = nullptr;
-        h->off_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_off, off.size() * 8));
-        h->off_cap = off.size();
-    }
-    AMX_HIP(hipMemcpyAsync(h->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->ctx->stream));
-    AMX_HIP(hipStreamSynchronize(h->ctx->stream));  // `off` is a local
-    const bool   tail = h->cfg.si_length > 0 || h->cfg.power != 0 || h->cfg.n_ceps > 0;
-    const size_t need = (size_t)frames * h->channels;
-    if (tail && need > h->ti_cap) {
-        hipFree(h->d_ti);
-        h->d_ti   = nullptr;
-        h->ti_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_ti, need * 4));
-        h->ti_cap = need;
-    }
+    const bool tail = h->cfg.si_length > 0 || h->cfg.power != 0 || h->cfg.n_ceps > 0;
+    if (tail)
+        AMX_TRY(h->d_ti.reserve((size_t)frames * h->channels));
     GtParams p;
     p.pcm        = pcm_dev;
-    p.sample_off = h->d_off;
-    p.frame_off  = h->d_off + n_seg + 1;
-    p.coef       = h->d_coef;
-    p.ti_win     = h->d_ti_win;
-    p.ti         = tail ? h->d_ti : out_dev;
+    p.sample_off = h->d_off.get();
+    p.frame_off  = h->d_off.get() + n_seg + 1;
+    p.coef       = h->d_coef.get();
+    p.ti_win     = h->d_ti_win.get();
+    p.ti         = tail ? h->d_ti.get() : out_dev;
     p.filtered   = filtered_dev;
     p.channels   = h->channels;
     p.cascade    = h->cascade;
@@ -569,9 +523,9 @@ int amx_gammatone_run_batch_dev(amx_gammatone* h, int n_seg, const long* sample_
     }
     if (tail) {
         GtPostParams q;
-        q.ti            = h->d_ti;
-        q.si_win        = h->d_si_win;
-        q.dct           = h->d_dct;
+        q.ti            = h->d_ti.get();
+        q.si_win        = h->d_si_win.get();
+        q.dct           = h->d_dct.get();
         q.out           = out_dev;
         q.frames        = frames;
         q.channels      = h->channels;
@@ -595,30 +549,10 @@ int amx_gammatone_run(amx_gammatone* h, const float* pcm_host, long n_samples, f
     const long T = amx_gammatone_n_frames(h, n_samples);
     if (T == 0)
         return AMX_OK;
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    if ((size_t)n_samples > h->pcm_cap) {
-        hipFree(h->d_pcm);
-        h->d_pcm   = nullptr;
-        h->pcm_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_pcm, (size_t)n_samples * 4));
-        h->pcm_cap = (size_t)n_samples;
-    }
-    const size_t on = (size_t)T * h->n_out;
-    if (on > h->out_cap) {
-        hipFree(h->d_out);
-        h->d_out   = nullptr;
-        h->out_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_out, on * 4));
-        h->out_cap = on;
-    }
-    AMX_HIP(hipMemcpyAsync(h->d_pcm, pcm_host, (size_t)n_samples * 4, hipMemcpyHostToDevice, h->ctx->stream));
     const long off[2] = {0, n_samples};
-    const int  r      = amx_gammatone_run_batch_dev(h, 1, off, h->d_pcm, h->d_out, nullptr);
-    if (r != AMX_OK)
-        return r;
-    AMX_HIP(hipMemcpyAsync(out_host, h->d_out, on * 4, hipMemcpyDeviceToHost, h->ctx->stream));
-    AMX_HIP(hipStreamSynchronize(h->ctx->stream));
-    return AMX_OK;
+    return amx::run_staged(h->ctx, h->d_pcm, h->d_out, pcm_host, (size_t)n_samples, out_host, (size_t)T * h->n_out, [&](const float* pcm_dev, float* out_dev) {
+        return amx_gammatone_run_batch_dev(h, 1, off, pcm_dev, out_dev, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -1008,20 +1008,21 @@ struct amx_mfcc {
     int             tune_wgs = 0;
     amx::MfccTables tab;
     int             frames_per_tile = 16;
-    // device copies of the tables
-    float * d_window = nullptr, *d_fw = nullptr, *d_dct_t = nullptr;
-    int *   d_fs = nullptr, *d_fe = nullptr, *d_fo = nullptr;
-    float2 *d_tw = nullptr, *d_stw = nullptr;
-    double* d_eql = nullptr;
-    size_t  lds_bytes = 0;
-    float*  d_ac   = nullptr;  // MF-PLP: autocorrelation coefficients of the current call [frames x n_transform]
-    size_t  ac_cap = 0;
+    // device copies of the tables (d_eql: plp.flow only, else unallocated)
+    amx::DevBuf<float>  d_window, d_fw, d_dct_t;
+    amx::DevBuf<int>    d_fs, d_fe, d_fo;
+    amx::DevBuf<float2> d_tw, d_stw;
+    amx::DevBuf<double> d_eql;
+    size_t              lds_bytes = 0;
+    amx::DevBuf<float>  d_ac;  // MF-PLP: autocorrelation coefficients of the current call [frames x n_transform]
     // VTLN (amx_mfcc_create_vtln): one bank per warping factor, tab = banks[0]; empty for amx_mfcc_create
     std::vector<double>          vtln_factors;
     std::vector<amx::MfccTables> banks;
-    int                          bank_weights = 0;        // the largest bank's weights (LDS is sized for it)
-    unsigned*                    d_banks      = nullptr;  // [n_banks] records, see MfccParams::fweights
+    int                          bank_weights = 0;  // the largest bank's weights (LDS is sized for it)
+    amx::DevBuf<unsigned>        d_banks;           // [n_banks] records, see MfccParams::fweights
     size_t                       bank_rec = 0, bank_nw = 0;  // words per record, of which weights (padded)
+
+    int n_weights() const { return banks.empty() ? (int)tab.filter_weights.size() : bank_weights; }
 };
 
 struct amx_mfcc_plan {
@@ -1031,19 +1032,11 @@ struct amx_mfcc_plan {
     int                    uniform_bank = 0;  // the bank of every tile, or -1 when the plan mixes banks (bank-per-tile variant)
     std::vector<long>      sample_off, frame_off;
     std::vector<amx::MfccTile> tiles;
-    amx::MfccTile*         d_tiles     = nullptr;
-    long long*             d_frame_off = nullptr;
+    amx::DevBuf<amx::MfccTile> d_tiles;
+    amx::DevBuf<long long>     d_frame_off;
 };
 
 namespace {
-
-template<class T>
-int upload(T** dst, const T* src, size_t n) {
-    AMX_HIP(hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n)
-        AMX_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return AMX_OK;
-}
 
 size_t mfcc_lds_bytes(const amx::MfccTables& t, bool r16, int n_weights) {
     amx::MfccLds L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, n_weights, r16);
@@ -1260,20 +1253,338 @@ int launch_mfcc(amx_mfcc* h, const amx::MfccParams& p, int n_tiles, bool s16, bo
     // mfcc_fft_*): matrix pipe busy 36 % + vector ALUs busy 51 % = 87 % of the dispatch -- v_mfma_f32_16x16x4_f32 runs at the f32
     // vector rate and does not overlap with vector instructions on a SIMD, so 24 of them cost like 192 vector instructions, more
     // than the ~125 they replace.  The butterflies stay the default; the product form is kept for A/B runs.
-    const bool mfma = h->tune_fft_mfma;
     if constexpr (NC == 256) {
         if (h->fft_r16)
             return s16 ? launch_mfcc_bank<NC, 18>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 16>(h, p, n_tiles, bpt);
-    }
-    if constexpr (NC == 256) {
-        if (mfma)
+        if (h->tune_fft_mfma)
             return s16 ? launch_mfcc_bank<NC, 3>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 1>(h, p, n_tiles, bpt);
-    }
-    if constexpr (NC == 256) {
         if (h->tune_prefetch)
             return s16 ? launch_mfcc_bank<NC, 6>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 4>(h, p, n_tiles, bpt);
     }
     return s16 ? launch_mfcc_bank<NC, 2>(h, p, n_tiles, bpt) : launch_mfcc_bank<NC, 0>(h, p, n_tiles, bpt);
+}
+
+// amx_mfcc_cfg.tuning: the kernel choices go into the handle; *fma and *r16 are what creation itself needs
+int parse_tuning(amx_mfcc* h, const amx_mfcc_cfg* cfg, bool* fma, bool* r16) {
+    amx::Tuning tune;
+    {
+        static const char* const keys[] = {"fft", "wgs", "lpc", "prefetch", "contract", nullptr};
+        if (!tune.parse(cfg->tuning, keys, "amx_mfcc_create"))
+            return AMX_ERR_INVALID;
+    }
+    std::string t_fft, t_lpc, t_contract;
+    int         t_wgs, t_prefetch;
+    {
+        static const char* const ffts[] = {"stockham", "mfma", "r16", nullptr};
+        static const char* const lpcs[] = {"regs", "lds", nullptr};
+        static const char* const cons[] = {"off", "fma", nullptr};
+        const char*              who    = "amx_mfcc_create";
+        // contract: which build of the reference the TABLES follow bit for bit (filter-bank geometry, f64: amx_set_contract); the
+        // kernel's f32 chain is compared at 1e-4 against either build (its log10 / hypot are the device's)
+        if (!tune.get_word("fft", "stockham", ffts, &t_fft, who) || !tune.get_word("lpc", "regs", lpcs, &t_lpc, who) ||
+            !tune.get_int("wgs", 0, 0, 64, &t_wgs, who) || !tune.get_int("prefetch", 1, 0, 1, &t_prefetch, who) ||
+            !tune.get_word("contract", h->ctx && h->ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", cons, &t_contract, who))
+            return AMX_ERR_INVALID;
+    }
+    h->tune_fft_mfma = t_fft == "mfma";
+    h->tune_lpc_lds  = t_lpc == "lds";
+    h->tune_wgs      = t_wgs;
+    h->tune_prefetch = t_prefetch != 0;  // default since the end of round 4 (0.753 -> 0.73 ms on config 2)
+    *fma             = t_contract == "fma";
+    *r16             = t_fft == "r16";
+    return AMX_OK;
+}
+
+// the plain table set, or one per warping factor (all with the same number of filters); h->tab is the first
+int build_banks(amx_mfcc* h, const amx_mfcc_cfg& cfg, const amx_mfcc_vtln* vtln, bool fma) {
+    if (!vtln)
+        return h->tab.build(cfg, fma);
+    h->vtln_factors.assign(vtln->factors, vtln->factors + vtln->n_factors);
+    h->banks.resize((size_t)vtln->n_factors);
+    for (int i = 0; i < vtln->n_factors; ++i) {
+        const amx::MfccTables::Vtln v{vtln->factors[i], vtln->limit};
+        AMX_TRY(h->banks[(size_t)i].build(cfg, fma, &v));
+        AMX_REQUIRE(h->banks[(size_t)i].n_filters == h->banks[0].n_filters, AMX_ERR_INVALID,
+                    "amx_mfcc_create_vtln: warping factor %g gives %d filters, warping factor %g gives %d", vtln->factors[0],
+                    h->banks[0].n_filters, vtln->factors[i], h->banks[(size_t)i].n_filters);
+        h->bank_weights = std::max(h->bank_weights, (int)h->banks[(size_t)i].filter_weights.size());
+    }
+    h->tab = h->banks[0];
+    return AMX_OK;
+}
+
+// what the kernel can do: the FFT length for every handle; the LDS of a workgroup for one that will run
+int check_limits(amx_mfcc* h, const amx_mfcc_cfg& cfg, bool r16) {
+    const amx::MfccTables& t = h->tab;
+    AMX_REQUIRE(t.fft_len >= 8 && t.fft_len <= 2048, AMX_ERR_UNSUPPORTED,
+                "amx_mfcc_create: FFT length %d not supported by the gfx950 kernel (8..2048)", t.fft_len);
+    if (!h->ctx)
+        return AMX_OK;
+    h->frames_per_tile = amx::FT;
+    h->fft_r16         = r16 && t.fft_len == 512 && cfg.front_end == AMX_FRONT_END_MFCC;  // (other lengths and front ends: the Stockham stages)
+    h->lds_bytes       = mfcc_lds_bytes(t, h->fft_r16, h->n_weights());
+    AMX_REQUIRE(h->lds_bytes <= 160 * 1024, AMX_ERR_UNSUPPORTED,
+                "amx_mfcc_create: configuration needs %zu bytes of LDS per workgroup (> 160 KiB)", h->lds_bytes);
+    return AMX_OK;
+}
+
+// VTLN: bank records in the kernel's LDS layout: weights padded to r4(n_weights), then start / end / offset per input
+std::vector<unsigned> pack_bank_records(amx_mfcc* h) {
+    const amx::MfccTables& t = h->tab;
+    const amx::MfccLds     L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, h->n_weights(), h->fft_r16);
+    const size_t           nw = (size_t)(L.fidx - L.fw), rec = nw + 3 * (size_t)t.n_inputs;
+    h->bank_rec = rec, h->bank_nw = nw;
+    std::vector<unsigned> recs(rec * h->banks.size(), 0u);
+    for (size_t k = 0; k < h->banks.size(); ++k) {
+        const amx::MfccTables& b = h->banks[k];
+        unsigned*              o = recs.data() + k * rec;
+        std::vector<int>       bs, be, bo;
+        input_filters(b, bs, be, bo);
+        memcpy(o, b.filter_weights.data(), b.filter_weights.size() * 4);
+        memcpy(o + nw, bs.data(), bs.size() * 4);
+        memcpy(o + nw + bs.size(), be.data(), be.size() * 4);
+        memcpy(o + nw + 2 * bs.size(), bo.data(), bo.size() * 4);
+    }
+    return recs;
+}
+
+int upload_tables(amx_mfcc* h) {
+    const amx::MfccTables& t = h->tab;
+    AMX_HIP(hipSetDevice(h->ctx->device));
+    std::vector<float> dct_t((size_t)t.n_inputs * t.n_transform);
+    for (int k = 0; k < t.n_transform; ++k)
+        for (int n = 0; n < t.n_inputs; ++n)
+            dct_t[(size_t)n * t.n_transform + k] = t.dct[(size_t)k * t.n_inputs + n];
+    std::vector<int> in_start, in_end, in_off;
+    input_filters(t, in_start, in_end, in_off);
+    if (!h->banks.empty()) {
+        const std::vector<unsigned> recs = pack_bank_records(h);
+        AMX_TRY(h->d_banks.upload(recs.data(), recs.size()));
+    }
+    AMX_TRY(h->d_window.upload(t.window.data(), t.window.size()));
+    AMX_TRY(h->d_fw.upload(t.filter_weights.data(), t.filter_weights.size()));
+    AMX_TRY(h->d_dct_t.upload(dct_t.data(), dct_t.size()));
+    AMX_TRY(h->d_fs.upload(in_start.data(), in_start.size()));
+    AMX_TRY(h->d_fe.upload(in_end.data(), in_end.size()));
+    AMX_TRY(h->d_fo.upload(in_off.data(), in_off.size()));
+    if (!t.eql.empty())
+        AMX_TRY(h->d_eql.upload(t.eql.data(), t.eql.size()));
+    AMX_TRY(h->d_tw.upload((const float2*)t.twiddle.data(), t.twiddle.size() / 2));
+    return h->d_stw.upload((const float2*)t.split_twiddle.data(), t.split_twiddle.size() / 2);
+}
+
+// ctx == NULL creates a host-only handle: geometry and tables are available
+// (amx_mfcc_describe / _n_frames / _tables), running it returns AMX_ERR_STATE.
+int mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out) {
+    AMX_REQUIRE(cfg && out, AMX_ERR_INVALID, "amx_mfcc_create: NULL argument");
+    *out = nullptr;
+    std::unique_ptr<amx_mfcc> h(new amx_mfcc);
+    h->ctx   = ctx;
+    bool fma = false, r16 = false;
+    AMX_TRY(parse_tuning(h.get(), cfg, &fma, &r16));
+    AMX_TRY(build_banks(h.get(), *cfg, vtln, fma));
+    AMX_TRY(check_limits(h.get(), *cfg, r16));
+    if (ctx)
+        AMX_TRY(upload_tables(h.get()));
+    *out = h.release();
+    return AMX_OK;
+}
+
+int mfcc_tables(const amx::MfccTables& t, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
+    if (window)
+        memcpy(window, t.window.data(), t.window.size() * 4);
+    if (fs)
+        memcpy(fs, t.filter_start.data(), t.filter_start.size() * 4);
+    if (fe)
+        memcpy(fe, t.filter_end.data(), t.filter_end.size() * 4);
+    if (fo)
+        memcpy(fo, t.filter_offset.data(), t.filter_offset.size() * 4);
+    if (fw)
+        memcpy(fw, t.filter_weights.data(), t.filter_weights.size() * 4);
+    if (dct)
+        memcpy(dct, t.dct.data(), t.dct.size() * 4);
+    return AMX_OK;
+}
+
+// the bank index of a warping factor (exact match), -1 if the handle has none such; a plain handle has the one factor 1
+int mfcc_bank_of(const amx_mfcc* h, double factor) {
+    if (h->vtln_factors.empty())
+        return factor == 1.0 ? 0 : -1;
+    for (size_t k = 0; k < h->vtln_factors.size(); ++k)
+        if (h->vtln_factors[k] == factor)
+            return (int)k;
+    return -1;
+}
+
+int mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, const std::vector<int>* bank, amx_mfcc_plan** out) {
+    AMX_REQUIRE(h && out && n_seg >= 0 && (n_seg == 0 || sample_offsets), AMX_ERR_INVALID, "amx_mfcc_plan_create: bad argument");
+    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_mfcc_plan_create: host-only handle (created without a context)");
+    *out = nullptr;
+    std::unique_ptr<amx_mfcc_plan> p(new amx_mfcc_plan);
+    p->owner = h;
+    p->n_seg = n_seg;
+    p->vtln  = bank != nullptr;
+    p->sample_off.assign(sample_offsets, sample_offsets + n_seg + (n_seg ? 1 : 0));
+    if (n_seg == 0)
+        p->sample_off.assign(1, 0);
+    p->frame_off.assign((size_t)n_seg + 1, 0);
+    const int ft = h->frames_per_tile;
+    for (int u = 0; u < n_seg; ++u) {
+        long len = p->sample_off[u + 1] - p->sample_off[u];
+        AMX_REQUIRE(len >= 0 && len <= 0x7fffffffL, AMX_ERR_INVALID, "amx_mfcc_plan_create: segment %d has invalid length %ld", u, len);
+        long T              = h->tab.n_frames(len);
+        p->frame_off[u + 1] = p->frame_off[u] + T;
+        for (long f0 = 0; f0 < T; f0 += ft) {
+            amx::MfccTile t;
+            t.sample_base = p->sample_off[u];
+            t.out_frame   = p->frame_off[u] + f0;
+            t.n_samples   = (int)len;
+            t.frame0      = (int)f0;
+            t.n_frames    = (int)std::min<long>(ft, T - f0);
+            t.pad_        = bank ? (*bank)[(size_t)u] : 0;
+            if (!p->tiles.empty() && t.pad_ != p->tiles[0].pad_)
+                p->uniform_bank = -1;
+            else if (p->tiles.empty())
+                p->uniform_bank = t.pad_;
+            p->tiles.push_back(t);
+        }
+    }
+    hipSetDevice(h->ctx->device);
+    AMX_TRY(p->d_tiles.upload(p->tiles.data(), p->tiles.size()));
+    const std::vector<long long> fo(p->frame_off.begin(), p->frame_off.end());
+    AMX_TRY(p->d_frame_off.upload(fo.data(), fo.size()));
+    *out = p.release();
+    return AMX_OK;
+}
+
+// the kernel's arguments for one run of a plan; bpt: the plan's tiles mix banks
+amx::MfccParams mfcc_params(const amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_dev, float* ceps_dev, bool bpt) {
+    const amx::MfccTables& t = h->tab;
+    amx::MfccParams        k;
+    k.pcm             = pcm_dev;
+    k.ceps            = ceps_dev;
+    k.tiles           = p->d_tiles.get();
+    k.window          = h->d_window.get();
+    k.fstart          = h->d_fs.get();
+    k.fend            = h->d_fe.get();
+    k.foff            = h->d_fo.get();
+    k.fweights        = bpt ? (const float*)h->d_banks.get() : h->d_fw.get();
+    if (!h->banks.empty() && !bpt) {
+        const unsigned* rec = h->d_banks.get() + (size_t)p->uniform_bank * h->bank_rec;
+        k.fweights          = (const float*)rec;
+        k.fstart            = (const int*)(rec + h->bank_nw);
+        k.fend              = k.fstart + t.n_inputs;
+        k.foff              = k.fend + t.n_inputs;
+    }
+    k.dct_t           = h->d_dct_t.get();
+    k.tw              = h->d_tw.get();
+    k.stw             = h->d_stw.get();
+    k.frame_len       = t.frame_len;
+    k.frame_shift     = t.frame_shift;
+    k.n_filters       = t.n_inputs;
+    k.eql             = h->d_eql.get();
+    k.n_ceps          = t.n_transform;
+    k.n_weights       = h->n_weights();
+    k.front_end       = t.cfg.front_end != AMX_FRONT_END_MFCC ? 1 : 0;
+    k.norm_div        = t.norm_div;
+    k.plp_power       = (float)t.cfg.plp_power;
+    k.frames_per_tile = h->frames_per_tile;
+    k.alpha           = (float)t.cfg.preemph_alpha;
+    k.fft_scale       = t.fft_scale;
+    k.n_tiles         = (int)p->tiles.size();
+    k.apply_scale     = (t.cfg.apply_scale && t.cfg.sample_rate != 1) ? 1 : 0;
+    k.dct_normalize   = t.cfg.dct_normalize;
+    return k;
+}
+
+int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_dev, bool s16, float* ceps_dev) {
+    AMX_REQUIRE(h && p, AMX_ERR_INVALID, "amx_mfcc_run_plan_dev: NULL handle");
+    AMX_REQUIRE(p->owner == h, AMX_ERR_STATE, "amx_mfcc_run_plan_dev: plan belongs to another front-end handle");
+    if (p->tiles.empty())
+        return AMX_OK;
+    AMX_REQUIRE(pcm_dev && ceps_dev, AMX_ERR_INVALID, "amx_mfcc_run_plan_dev: NULL buffer");
+    AMX_HIP(hipSetDevice(h->ctx->device));
+    const amx::MfccTables& t = h->tab;
+    // a VTLN plan whose tiles mix banks runs the bank-per-tile variant; one whose tiles share one bank (one factor, or a one-factor
+    // handle) runs the unwarped kernel on that bank's record (weights padded to the largest bank's, then start / end / offset)
+    const bool      bpt = !h->banks.empty() && p->uniform_bank < 0;
+    amx::MfccParams k   = mfcc_params(h, p, pcm_dev, ceps_dev, bpt);
+    const long long total_frames = p->frame_off.back();
+    if (k.front_end) {  // the fused kernel stops at the autocorrelation coefficients; lpc_cepstrum_kernel finishes the chain
+        AMX_TRY(h->d_ac.reserve((size_t)total_frames * t.n_transform));
+        k.ceps = h->d_ac.get();
+    }
+    int r;
+    switch (t.fft_len / 2) {
+        case 4: r = launch_mfcc<4>(h, k, k.n_tiles, s16, bpt); break;
+        case 8: r = launch_mfcc<8>(h, k, k.n_tiles, s16, bpt); break;
+        case 16: r = launch_mfcc<16>(h, k, k.n_tiles, s16, bpt); break;
+        case 32: r = launch_mfcc<32>(h, k, k.n_tiles, s16, bpt); break;
+        case 64: r = launch_mfcc<64>(h, k, k.n_tiles, s16, bpt); break;
+        case 128: r = launch_mfcc<128>(h, k, k.n_tiles, s16, bpt); break;
+        case 256: r = launch_mfcc<256>(h, k, k.n_tiles, s16, bpt); break;
+        case 512: r = launch_mfcc<512>(h, k, k.n_tiles, s16, bpt); break;
+        case 1024: r = launch_mfcc<1024>(h, k, k.n_tiles, s16, bpt); break;
+        default:
+            amx::set_error("amx_mfcc_run_plan_dev: no kernel for FFT length %d", t.fft_len);
+            return AMX_ERR_UNSUPPORTED;
+    }
+    if (r != AMX_OK || !k.front_end || total_frames == 0)
+        return r;
+    amx::ScopedKernelTimer timer(h->ctx, "lpc_cepstrum");
+    const dim3 lgrid((unsigned)((total_frames + 63) / 64));
+    const bool in_regs = !h->tune_lpc_lds;  // tuning lpc=lds: the LDS kernel (A/B runs, tests)
+    if (in_regs && t.n_transform <= 16)
+        hipLaunchKernelGGL(lpc_cepstrum_reg_kernel<16>, lgrid, dim3(64), 0, h->ctx->stream, h->d_ac.get(), t.n_transform, ceps_dev, t.n_ceps, total_frames);
+    else if (in_regs && t.n_transform <= 24)
+        hipLaunchKernelGGL(lpc_cepstrum_reg_kernel<24>, lgrid, dim3(64), 0, h->ctx->stream, h->d_ac.get(), t.n_transform, ceps_dev, t.n_ceps, total_frames);
+    else {
+        const size_t lpc_lds = lpc_lds_bytes(t.n_transform);
+        hipFuncSetAttribute((const void*)lpc_cepstrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lpc_lds);
+        hipLaunchKernelGGL(lpc_cepstrum_kernel, lgrid, dim3(64), lpc_lds, h->ctx->stream, h->d_ac.get(), t.n_transform, ceps_dev, t.n_ceps,
+                           total_frames);
+    }
+    AMX_HIP(hipGetLastError());
+    return AMX_OK;
+}
+
+int mfcc_run_batch(amx_mfcc* h, int n_seg, const void* const* pcm_host, bool s16, const long* n_samples, float* const* ceps_host) {
+    AMX_REQUIRE(h && n_seg >= 0, AMX_ERR_INVALID, "amx_mfcc_run_batch: bad argument");
+    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_mfcc_run_batch: host-only handle (created without a context)");
+    if (n_seg == 0)
+        return AMX_OK;
+    AMX_REQUIRE(pcm_host && n_samples && ceps_host, AMX_ERR_INVALID, "amx_mfcc_run_batch: NULL argument");
+    const size_t ss = s16 ? 2 : 4;  // bytes per sample on the host link and in HBM
+    std::vector<long> off((size_t)n_seg + 1, 0);
+    for (int u = 0; u < n_seg; ++u) {
+        AMX_REQUIRE(n_samples[u] >= 0, AMX_ERR_INVALID, "amx_mfcc_run_batch: negative segment length");
+        off[u + 1] = off[u] + n_samples[u];
+    }
+    amx_mfcc_plan* made = nullptr;
+    AMX_TRY(mfcc_plan_create(h, n_seg, off.data(), nullptr, &made));
+    const std::unique_ptr<amx_mfcc_plan, decltype(&amx_mfcc_plan_destroy)> plan(made, amx_mfcc_plan_destroy);
+    const long          total_frames = plan->frame_off.back();
+    amx::DevBuf<char>   d_pcm;   // allocated per call
+    amx::DevBuf<float>  d_ceps;
+    const hipStream_t   st = h->ctx->stream;
+    AMX_REQUIRE(d_pcm.reserve(std::max<long>(off[n_seg], 1) * ss) == AMX_OK &&
+                        d_ceps.reserve(std::max<long>(total_frames * h->tab.n_ceps, 1)) == AMX_OK,
+                AMX_ERR_DEVICE, "amx_mfcc_run_batch: out of device memory");
+    for (int u = 0; u < n_seg; ++u)
+        if (n_samples[u] > 0)
+            AMX_REQUIRE(hipMemcpyAsync(d_pcm.get() + off[u] * ss, pcm_host[u], (size_t)n_samples[u] * ss, hipMemcpyHostToDevice, st) == hipSuccess,
+                        AMX_ERR_DEVICE, "amx_mfcc_run_batch: H2D copy failed");
+    AMX_TRY(mfcc_run_plan(h, plan.get(), d_pcm.get(), s16, d_ceps.get()));
+    for (int u = 0; u < n_seg; ++u) {
+        const long T = plan->frame_off[u + 1] - plan->frame_off[u];
+        if (T > 0)
+            AMX_REQUIRE(hipMemcpyAsync(ceps_host[u], d_ceps.get() + plan->frame_off[u] * h->tab.n_ceps, (size_t)T * h->tab.n_ceps * 4,
+                                       hipMemcpyDeviceToHost, st) == hipSuccess,
+                        AMX_ERR_DEVICE, "amx_mfcc_run_batch: D2H copy failed");
+    }
+    AMX_REQUIRE(hipStreamSynchronize(st) == hipSuccess, AMX_ERR_DEVICE, "amx_mfcc_run_batch: kernel execution failed: %s",
+                hipGetErrorString(hipGetLastError()));
+    return AMX_OK;
 }
 
 }  // namespace
@@ -1331,8 +1642,6 @@ void amx_mfplp_default_cfg(amx_mfcc_cfg* c) {
     c->n_ceps            = 13;
 }
 
-static int mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out);
-
 int amx_mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, amx_mfcc** out) {
     return mfcc_create(ctx, cfg, nullptr, out);
 }
@@ -1354,141 +1663,9 @@ int amx_mfcc_create_vtln(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_v
     return mfcc_create(ctx, cfg, vtln, out);
 }
 
-static int mfcc_create(amx_ctx* ctx, const amx_mfcc_cfg* cfg, const amx_mfcc_vtln* vtln, amx_mfcc** out) {
-    // ctx == NULL creates a host-only handle: geometry and tables are available
-    // (amx_mfcc_describe / _n_frames / _tables), running it returns AMX_ERR_STATE.
-    AMX_REQUIRE(cfg && out, AMX_ERR_INVALID, "amx_mfcc_create: NULL argument");
-    *out        = nullptr;
-    amx::Tuning tune;
-    {
-        static const char* const keys[] = {"fft", "wgs", "lpc", "prefetch", "contract", nullptr};
-        if (!tune.parse(cfg->tuning, keys, "amx_mfcc_create"))
-            return AMX_ERR_INVALID;
-    }
-    std::string t_fft, t_lpc, t_contract;
-    int         t_wgs, t_prefetch;
-    {
-        static const char* const ffts[] = {"stockham", "mfma", "r16", nullptr};
-        static const char* const lpcs[] = {"regs", "lds", nullptr};
-        static const char* const cons[] = {"off", "fma", nullptr};
-        const char*              who    = "amx_mfcc_create";
-        // contract: which build of the reference the TABLES follow bit for bit (filter-bank geometry, f64: amx_set_contract); the
-        // kernel's f32 chain is compared at 1e-4 against either build (its log10 / hypot are the device's)
-        if (!tune.get_word("fft", "stockham", ffts, &t_fft, who) || !tune.get_word("lpc", "regs", lpcs, &t_lpc, who) ||
-            !tune.get_int("wgs", 0, 0, 64, &t_wgs, who) || !tune.get_int("prefetch", 1, 0, 1, &t_prefetch, who) ||
-            !tune.get_word("contract", ctx && ctx->contract == AMX_CONTRACT_FMA ? "fma" : "off", cons, &t_contract, who))
-            return AMX_ERR_INVALID;
-    }
-    amx_mfcc* h = new amx_mfcc;
-    h->ctx      = ctx;
-    h->tune_fft_mfma = t_fft == "mfma";
-    h->tune_lpc_lds  = t_lpc == "lds";
-    h->tune_wgs      = t_wgs;
-    h->tune_prefetch = t_prefetch != 0;  // default since the end of round 4 (0.753 -> 0.73 ms on config 2)
-    int r = AMX_OK;
-    if (!vtln)
-        r = h->tab.build(*cfg, t_contract == "fma");
-    else {
-        h->vtln_factors.assign(vtln->factors, vtln->factors + vtln->n_factors);
-        h->banks.resize((size_t)vtln->n_factors);
-        for (int i = 0; i < vtln->n_factors && r == AMX_OK; ++i) {
-            const amx::MfccTables::Vtln v{vtln->factors[i], vtln->limit};
-            r = h->banks[(size_t)i].build(*cfg, t_contract == "fma", &v);
-            if (r == AMX_OK && h->banks[(size_t)i].n_filters != h->banks[0].n_filters) {
-                amx::set_error("amx_mfcc_create_vtln: warping factor %g gives %d filters, warping factor %g gives %d", vtln->factors[0],
-                               h->banks[0].n_filters, vtln->factors[i], h->banks[(size_t)i].n_filters);
-                r = AMX_ERR_INVALID;
-            }
-            h->bank_weights = std::max(h->bank_weights, (int)h->banks[(size_t)i].filter_weights.size());
-        }
-        if (r == AMX_OK)
-            h->tab = h->banks[0];
-    }
-    if (r != AMX_OK) {
-        delete h;
-        return r;
-    }
-    const amx::MfccTables& t = h->tab;
-    const int n_weights = vtln ? h->bank_weights : (int)t.filter_weights.size();
-    if (t.fft_len < 8 || t.fft_len > 2048) {
-        amx::set_error("amx_mfcc_create: FFT length %d not supported by the gfx950 kernel (8..2048)", t.fft_len);
-        delete h;
-        return AMX_ERR_UNSUPPORTED;
-    }
-    if (!ctx) {
-        *out = h;
-        return AMX_OK;
-    }
-    AMX_HIP(hipSetDevice(ctx->device));
-    h->frames_per_tile = amx::FT;
-    h->fft_r16         = t_fft == "r16" && t.fft_len == 512 && cfg->front_end == AMX_FRONT_END_MFCC;  // (other lengths and front ends: the Stockham stages)
-    h->lds_bytes       = mfcc_lds_bytes(t, h->fft_r16, n_weights);
-    if (h->lds_bytes > 160 * 1024) {
-        amx::set_error("amx_mfcc_create: configuration needs %zu bytes of LDS per workgroup (> 160 KiB)", h->lds_bytes);
-        delete h;
-        return AMX_ERR_UNSUPPORTED;
-    }
-    std::vector<float> dct_t((size_t)t.n_inputs * t.n_transform);
-    for (int k = 0; k < t.n_transform; ++k)
-        for (int n = 0; n < t.n_inputs; ++n)
-            dct_t[(size_t)n * t.n_transform + k] = t.dct[(size_t)k * t.n_inputs + n];
-    std::vector<int> in_start, in_end, in_off;
-    input_filters(t, in_start, in_end, in_off);
-    if (vtln) {  // bank records in the kernel's LDS layout: weights padded to r4(n_weights), then start / end / offset per input
-        const amx::MfccLds L(t.frame_len, t.frame_shift, t.fft_len, t.n_inputs, t.n_transform, n_weights, h->fft_r16);
-        const size_t       nw = (size_t)(L.fidx - L.fw), rec = nw + 3 * (size_t)t.n_inputs;
-        h->bank_rec = rec, h->bank_nw = nw;
-        std::vector<unsigned> recs(rec * h->banks.size(), 0u);
-        for (size_t k = 0; k < h->banks.size(); ++k) {
-            const amx::MfccTables& b = h->banks[k];
-            unsigned*              o = recs.data() + k * rec;
-            std::vector<int>       bs, be, bo;
-            input_filters(b, bs, be, bo);
-            memcpy(o, b.filter_weights.data(), b.filter_weights.size() * 4);
-            memcpy(o + nw, bs.data(), bs.size() * 4);
-            memcpy(o + nw + bs.size(), be.data(), be.size() * 4);
-            memcpy(o + nw + 2 * bs.size(), bo.data(), bo.size() * 4);
-        }
-        if ((r = upload(&h->d_banks, recs.data(), recs.size())) != AMX_OK) {
-            amx_mfcc_destroy(h);
-            return r;
-        }
-    }
-    if ((r = upload(&h->d_window, t.window.data(), t.window.size())) != AMX_OK ||
-        (r = upload(&h->d_fw, t.filter_weights.data(), t.filter_weights.size())) != AMX_OK ||
-        (r = upload(&h->d_dct_t, dct_t.data(), dct_t.size())) != AMX_OK ||
-        (r = upload(&h->d_fs, in_start.data(), in_start.size())) != AMX_OK ||
-        (r = upload(&h->d_fe, in_end.data(), in_end.size())) != AMX_OK ||
-        (r = upload(&h->d_fo, in_off.data(), in_off.size())) != AMX_OK ||
-        (!t.eql.empty() && (r = upload(&h->d_eql, t.eql.data(), t.eql.size())) != AMX_OK) ||
-        (r = upload(&h->d_tw, (const float2*)t.twiddle.data(), t.twiddle.size() / 2)) != AMX_OK ||
-        (r = upload(&h->d_stw, (const float2*)t.split_twiddle.data(), t.split_twiddle.size() / 2)) != AMX_OK) {
-        amx_mfcc_destroy(h);
-        return r;
-    }
-    *out = h;
-    return AMX_OK;
-}
-
 void amx_mfcc_destroy(amx_mfcc* h) {
-    if (!h)
-        return;
-    if (!h->ctx) {
-        delete h;
-        return;
-    }
-    hipSetDevice(h->ctx->device);
-    hipFree(h->d_window);
-    hipFree(h->d_fw);
-    hipFree(h->d_dct_t);
-    hipFree(h->d_fs);
-    hipFree(h->d_fe);
-    hipFree(h->d_fo);
-    hipFree(h->d_tw);
-    hipFree(h->d_stw);
-    hipFree(h->d_eql);
-    hipFree(h->d_ac);
-    hipFree(h->d_banks);
+    if (h && h->ctx)
+        hipSetDevice(h->ctx->device);
     delete h;
 }
 
@@ -1515,21 +1692,9 @@ double amx_mfcc_frame_start_time(const amx_mfcc* h, long frame) {
     return h ? h->tab.frame_start_time(frame) : 0.0;
 }
 
-static int mfcc_tables(const amx::MfccTables& t, float* window, int* fs, int* fe, int* fo, float* fw, float* dct);
-
 int amx_mfcc_tables(const amx_mfcc* h, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
     AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_mfcc_tables: NULL handle");
     return mfcc_tables(h->tab, window, fs, fe, fo, fw, dct);
-}
-
-// the bank index of a warping factor (exact match), -1 if the handle has none such; a plain handle has the one factor 1
-static int mfcc_bank_of(const amx_mfcc* h, double factor) {
-    if (h->vtln_factors.empty())
-        return factor == 1.0 ? 0 : -1;
-    for (size_t k = 0; k < h->vtln_factors.size(); ++k)
-        if (h->vtln_factors[k] == factor)
-            return (int)k;
-    return -1;
 }
 
 int amx_mfcc_tables_vtln(const amx_mfcc* h, double warping_factor, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
@@ -1539,30 +1704,12 @@ int amx_mfcc_tables_vtln(const amx_mfcc* h, double warping_factor, float* window
     return mfcc_tables(h->banks.empty() ? h->tab : h->banks[(size_t)k], window, fs, fe, fo, fw, dct);
 }
 
-static int mfcc_tables(const amx::MfccTables& t, float* window, int* fs, int* fe, int* fo, float* fw, float* dct) {
-    if (window)
-        memcpy(window, t.window.data(), t.window.size() * 4);
-    if (fs)
-        memcpy(fs, t.filter_start.data(), t.filter_start.size() * 4);
-    if (fe)
-        memcpy(fe, t.filter_end.data(), t.filter_end.size() * 4);
-    if (fo)
-        memcpy(fo, t.filter_offset.data(), t.filter_offset.size() * 4);
-    if (fw)
-        memcpy(fw, t.filter_weights.data(), t.filter_weights.size() * 4);
-    if (dct)
-        memcpy(dct, t.dct.data(), t.dct.size() * 4);
-    return AMX_OK;
-}
-
 int amx_mfcc_equal_loudness(const amx_mfcc* h, double* factors) {
     AMX_REQUIRE(h && factors, AMX_ERR_INVALID, "amx_mfcc_equal_loudness: NULL argument");
     AMX_REQUIRE(!h->tab.eql.empty(), AMX_ERR_STATE, "amx_mfcc_equal_loudness: not a plp.flow front end");
     memcpy(factors, h->tab.eql.data(), h->tab.eql.size() * sizeof(double));
     return AMX_OK;
 }
-
-static int mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, const std::vector<int>* bank, amx_mfcc_plan** out);
 
 int amx_mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, amx_mfcc_plan** out) {
     return mfcc_plan_create(h, n_seg, sample_offsets, nullptr, out);
@@ -1581,62 +1728,7 @@ int amx_mfcc_plan_create_vtln(amx_mfcc* h, int n_seg, const long* sample_offsets
     return mfcc_plan_create(h, n_seg, sample_offsets, &bank, out);
 }
 
-static int mfcc_plan_create(amx_mfcc* h, int n_seg, const long* sample_offsets, const std::vector<int>* bank, amx_mfcc_plan** out) {
-    AMX_REQUIRE(h && out && n_seg >= 0 && (n_seg == 0 || sample_offsets), AMX_ERR_INVALID, "amx_mfcc_plan_create: bad argument");
-    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_mfcc_plan_create: host-only handle (created without a context)");
-    *out             = nullptr;
-    amx_mfcc_plan* p = new amx_mfcc_plan;
-    p->owner         = h;
-    p->n_seg         = n_seg;
-    p->vtln          = bank != nullptr;
-    p->sample_off.assign(sample_offsets, sample_offsets + n_seg + (n_seg ? 1 : 0));
-    if (n_seg == 0)
-        p->sample_off.assign(1, 0);
-    p->frame_off.assign((size_t)n_seg + 1, 0);
-    const int ft = h->frames_per_tile;
-    for (int u = 0; u < n_seg; ++u) {
-        long len = p->sample_off[u + 1] - p->sample_off[u];
-        if (len < 0 || len > 0x7fffffffL) {
-            amx::set_error("amx_mfcc_plan_create: segment %d has invalid length %ld", u, len);
-            delete p;
-            return AMX_ERR_INVALID;
-        }
-        long T              = h->tab.n_frames(len);
-        p->frame_off[u + 1] = p->frame_off[u] + T;
-        for (long f0 = 0; f0 < T; f0 += ft) {
-            amx::MfccTile t;
-            t.sample_base = p->sample_off[u];
-            t.out_frame   = p->frame_off[u] + f0;
-            t.n_samples   = (int)len;
-            t.frame0      = (int)f0;
-            t.n_frames    = (int)std::min<long>(ft, T - f0);
-            t.pad_        = bank ? (*bank)[(size_t)u] : 0;
-            if (!p->tiles.empty() && t.pad_ != p->tiles[0].pad_)
-                p->uniform_bank = -1;
-            else if (p->tiles.empty())
-                p->uniform_bank = t.pad_;
-            p->tiles.push_back(t);
-        }
-    }
-    hipSetDevice(h->ctx->device);
-    int r = upload(&p->d_tiles, p->tiles.data(), p->tiles.size());
-    if (r == AMX_OK) {
-        std::vector<long long> fo(p->frame_off.begin(), p->frame_off.end());
-        r = upload(&p->d_frame_off, fo.data(), fo.size());
-    }
-    if (r != AMX_OK) {
-        amx_mfcc_plan_destroy(p);
-        return r;
-    }
-    *out = p;
-    return AMX_OK;
-}
-
 void amx_mfcc_plan_destroy(amx_mfcc_plan* p) {
-    if (!p)
-        return;
-    hipFree(p->d_tiles);
-    hipFree(p->d_frame_off);
     delete p;
 }
 
@@ -1650,162 +1742,12 @@ int amx_mfcc_plan_frame_offsets(const amx_mfcc_plan* p, long* frame_offsets) {
     return AMX_OK;
 }
 
-static int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_dev, bool s16, float* ceps_dev);
-
 int amx_mfcc_run_plan_dev(amx_mfcc* h, const amx_mfcc_plan* p, const float* pcm_dev, float* ceps_dev) {
     return mfcc_run_plan(h, p, pcm_dev, false, ceps_dev);
 }
 
 int amx_mfcc_run_plan_dev_s16(amx_mfcc* h, const amx_mfcc_plan* p, const int16_t* pcm_dev, float* ceps_dev) {
     return mfcc_run_plan(h, p, pcm_dev, true, ceps_dev);
-}
-
-static int mfcc_run_plan(amx_mfcc* h, const amx_mfcc_plan* p, const void* pcm_dev, bool s16, float* ceps_dev) {
-    AMX_REQUIRE(h && p, AMX_ERR_INVALID, "amx_mfcc_run_plan_dev: NULL handle");
-    AMX_REQUIRE(p->owner == h, AMX_ERR_STATE, "amx_mfcc_run_plan_dev: plan belongs to another front-end handle");
-    if (p->tiles.empty())
-        return AMX_OK;
-    AMX_REQUIRE(pcm_dev && ceps_dev, AMX_ERR_INVALID, "amx_mfcc_run_plan_dev: NULL buffer");
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    const amx::MfccTables& t = h->tab;
-    amx::MfccParams        k;
-    k.pcm             = pcm_dev;
-    k.ceps            = ceps_dev;
-    k.tiles           = p->d_tiles;
-    k.window          = h->d_window;
-    // a VTLN plan whose tiles mix banks runs the bank-per-tile variant; one whose tiles share one bank (one factor, or a one-factor
-    // handle) runs the unwarped kernel on that bank's record (weights padded to the largest bank's, then start / end / offset)
-    const bool vtln   = !h->banks.empty();
-    const bool bpt    = vtln && p->uniform_bank < 0;
-    k.fstart          = h->d_fs;
-    k.fend            = h->d_fe;
-    k.foff            = h->d_fo;
-    k.fweights        = bpt ? (const float*)h->d_banks : h->d_fw;
-    if (vtln && !bpt) {
-        const unsigned* rec = h->d_banks + (size_t)p->uniform_bank * h->bank_rec;
-        k.fweights          = (const float*)rec;
-        k.fstart            = (const int*)(rec + h->bank_nw);
-        k.fend              = k.fstart + t.n_inputs;
-        k.foff              = k.fend + t.n_inputs;
-    }
-    k.dct_t           = h->d_dct_t;
-    k.tw              = h->d_tw;
-    k.stw             = h->d_stw;
-    k.frame_len       = t.frame_len;
-    k.frame_shift     = t.frame_shift;
-    k.n_filters       = t.n_inputs;
-    k.eql             = h->d_eql;
-    k.n_ceps          = t.n_transform;
-    k.n_weights       = vtln ? h->bank_weights : (int)t.filter_weights.size();
-    k.front_end       = t.cfg.front_end != AMX_FRONT_END_MFCC ? 1 : 0;
-    k.norm_div        = t.norm_div;
-    k.plp_power       = (float)t.cfg.plp_power;
-    const long long total_frames = p->frame_off.back();
-    if (k.front_end) {  // the fused kernel stops at the autocorrelation coefficients; lpc_cepstrum_kernel finishes the chain
-        const size_t need = (size_t)total_frames * t.n_transform;
-        if (need > h->ac_cap) {
-            hipFree(h->d_ac);
-            h->d_ac   = nullptr;
-            h->ac_cap = 0;
-            AMX_HIP(hipMalloc((void**)&h->d_ac, std::max<size_t>(need, 1) * 4));
-            h->ac_cap = need;
-        }
-        k.ceps = h->d_ac;
-    }
-    k.frames_per_tile = h->frames_per_tile;
-    k.alpha           = (float)t.cfg.preemph_alpha;
-    k.fft_scale       = t.fft_scale;
-    const int n_tiles_total = (int)p->tiles.size();
-    k.n_tiles               = n_tiles_total;
-    k.apply_scale     = (t.cfg.apply_scale && t.cfg.sample_rate != 1) ? 1 : 0;
-    k.dct_normalize   = t.cfg.dct_normalize;
-    int r;
-    switch (t.fft_len / 2) {
-        case 4: r = launch_mfcc<4>(h, k, n_tiles_total, s16, bpt); break;
-        case 8: r = launch_mfcc<8>(h, k, n_tiles_total, s16, bpt); break;
-        case 16: r = launch_mfcc<16>(h, k, n_tiles_total, s16, bpt); break;
-        case 32: r = launch_mfcc<32>(h, k, n_tiles_total, s16, bpt); break;
-        case 64: r = launch_mfcc<64>(h, k, n_tiles_total, s16, bpt); break;
-        case 128: r = launch_mfcc<128>(h, k, n_tiles_total, s16, bpt); break;
-        case 256: r = launch_mfcc<256>(h, k, n_tiles_total, s16, bpt); break;
-        case 512: r = launch_mfcc<512>(h, k, n_tiles_total, s16, bpt); break;
-        case 1024: r = launch_mfcc<1024>(h, k, n_tiles_total, s16, bpt); break;
-        default:
-            amx::set_error("amx_mfcc_run_plan_dev: no kernel for FFT length %d", t.fft_len);
-            return AMX_ERR_UNSUPPORTED;
-    }
-    if (r != AMX_OK || !k.front_end || total_frames == 0)
-        return r;
-    amx::ScopedKernelTimer timer(h->ctx, "lpc_cepstrum");
-    const dim3 lgrid((unsigned)((total_frames + 63) / 64));
-    const bool in_regs = !h->tune_lpc_lds;  // tuning lpc=lds: the LDS kernel (A/B runs, tests)
-    if (in_regs && t.n_transform <= 16)
-        hipLaunchKernelGGL(lpc_cepstrum_reg_kernel<16>, lgrid, dim3(64), 0, h->ctx->stream, h->d_ac, t.n_transform, ceps_dev, t.n_ceps, total_frames);
-    else if (in_regs && t.n_transform <= 24)
-        hipLaunchKernelGGL(lpc_cepstrum_reg_kernel<24>, lgrid, dim3(64), 0, h->ctx->stream, h->d_ac, t.n_transform, ceps_dev, t.n_ceps, total_frames);
-    else {
-        const size_t lpc_lds = lpc_lds_bytes(t.n_transform);
-        hipFuncSetAttribute((const void*)lpc_cepstrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lpc_lds);
-        hipLaunchKernelGGL(lpc_cepstrum_kernel, lgrid, dim3(64), lpc_lds, h->ctx->stream, h->d_ac, t.n_transform, ceps_dev, t.n_ceps,
-                           total_frames);
-    }
-    AMX_HIP(hipGetLastError());
-    return AMX_OK;
-}
-
-static int mfcc_run_batch(amx_mfcc* h, int n_seg, const void* const* pcm_host, bool s16, const long* n_samples, float* const* ceps_host) {
-    AMX_REQUIRE(h && n_seg >= 0, AMX_ERR_INVALID, "amx_mfcc_run_batch: bad argument");
-    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_mfcc_run_batch: host-only handle (created without a context)");
-    if (n_seg == 0)
-        return AMX_OK;
-    AMX_REQUIRE(pcm_host && n_samples && ceps_host, AMX_ERR_INVALID, "amx_mfcc_run_batch: NULL argument");
-    const size_t ss = s16 ? 2 : 4;  // bytes per sample on the host link and in HBM
-    std::vector<long> off((size_t)n_seg + 1, 0);
-    for (int u = 0; u < n_seg; ++u) {
-        AMX_REQUIRE(n_samples[u] >= 0, AMX_ERR_INVALID, "amx_mfcc_run_batch: negative segment length");
-        off[u + 1] = off[u] + n_samples[u];
-    }
-    amx_mfcc_plan* plan = nullptr;
-    int            r    = amx_mfcc_plan_create(h, n_seg, off.data(), &plan);
-    if (r != AMX_OK)
-        return r;
-    const long total_frames = amx_mfcc_plan_total_frames(plan);
-    char*      d_pcm  = nullptr;
-    float*     d_ceps = nullptr;
-    hipStream_t st = h->ctx->stream;
-    auto fail = [&](int code) {
-        hipFree(d_pcm);
-        hipFree(d_ceps);
-        amx_mfcc_plan_destroy(plan);
-        return code;
-    };
-    if (hipMalloc((void**)&d_pcm, std::max<long>(off[n_seg], 1) * ss) != hipSuccess ||
-        hipMalloc((void**)&d_ceps, std::max<long>(total_frames * h->tab.n_ceps, 1) * 4) != hipSuccess) {
-        amx::set_error("amx_mfcc_run_batch: out of device memory");
-        return fail(AMX_ERR_DEVICE);
-    }
-    for (int u = 0; u < n_seg; ++u)
-        if (n_samples[u] > 0 &&
-            hipMemcpyAsync(d_pcm + off[u] * ss, pcm_host[u], (size_t)n_samples[u] * ss, hipMemcpyHostToDevice, st) != hipSuccess) {
-            amx::set_error("amx_mfcc_run_batch: H2D copy failed");
-            return fail(AMX_ERR_DEVICE);
-        }
-    r = mfcc_run_plan(h, plan, d_pcm, s16, d_ceps);
-    if (r != AMX_OK)
-        return fail(r);
-    for (int u = 0; u < n_seg; ++u) {
-        long T = plan->frame_off[u + 1] - plan->frame_off[u];
-        if (T > 0 && hipMemcpyAsync(ceps_host[u], d_ceps + plan->frame_off[u] * h->tab.n_ceps, (size_t)T * h->tab.n_ceps * 4,
-                                    hipMemcpyDeviceToHost, st) != hipSuccess) {
-            amx::set_error("amx_mfcc_run_batch: D2H copy failed");
-            return fail(AMX_ERR_DEVICE);
-        }
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) {
-        amx::set_error("amx_mfcc_run_batch: kernel execution failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail(AMX_ERR_DEVICE);
-    }
-    return fail(AMX_OK);
 }
 
 int amx_mfcc_run_batch(amx_mfcc* h, int n_seg, const float* const* pcm_host, const long* n_samples, float* const* ceps_host) {
@@ -1833,7 +1775,7 @@ int amx_mfcc_run_s16(amx_mfcc* h, const int16_t* pcm_host, long n_samples, float
 // internal (not in amx.h): the segmentation of a plan for the back-end kernels in backend.hip
 int amx_internal_plan_view(const amx_mfcc_plan* p, const long long** d_frame_off, int* n_seg, long long* total) {
     AMX_REQUIRE(p && d_frame_off && n_seg && total, AMX_ERR_INVALID, "plan view: NULL argument");
-    *d_frame_off = p->d_frame_off;
+    *d_frame_off = p->d_frame_off.get();
     *n_seg       = p->n_seg;
     *total       = p->frame_off.back();
     return AMX_OK;
@@ -1850,7 +1792,7 @@ int amx_context_window_dev(amx_ctx* ctx, const amx_mfcc_plan* p, const float* fe
     AMX_HIP(hipSetDevice(ctx->device));
     amx::ScopedKernelTimer timer(ctx, "context_window");
     hipLaunchKernelGGL(amx::context_window_kernel, dim3((unsigned)total), dim3(256), 0, ctx->stream, feats_dev,
-                       p->d_frame_off, p->n_seg, dim, left, right, out_dev, out_stride, total);
+                       p->d_frame_off.get(), p->n_seg, dim, left, right, out_dev, out_stride, total);
     AMX_HIP(hipGetLastError());
     return AMX_OK;
 }

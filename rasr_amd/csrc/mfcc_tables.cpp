@@ -18,6 +18,7 @@
 #include <limits>
 
 #include "common.hpp"
+#include "frontend_host.hpp"
 
 namespace amx {
 namespace {
@@ -373,15 +374,8 @@ int MfccTables::build(const amx_mfcc_cfg& c, bool fma, const Vtln* vtln) {
     return AMX_OK;
 }
 
-// Signal/WindowBuffer.cc:84-125: get() while >= 2*max(len,shift) buffered, then flush() every
-// `shift` samples until the rest fits into one window; the last frame is short.
 long MfccTables::n_frames(long n) const {
-    if (n <= 0)
-        return 0;
-    const long reach = std::max(frame_len, frame_shift);
-    if (n <= reach)
-        return 1;
-    return (n - reach + frame_shift - 1) / frame_shift + 1;
+    return window_frames(n, frame_len, frame_shift);
 }
 
 double MfccTables::frame_start_time(long frame) const {

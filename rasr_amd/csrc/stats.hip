@@ -131,10 +131,8 @@ extern "C" int amx_gather_scores(amx_ctx* ctx, const float* scores_dev, int n_ro
         AMX_REQUIRE(rows_host[i] < (uint32_t)n_rows && cols_host[i] < (uint32_t)ld, AMX_ERR_INVALID,
                     "amx_gather_scores: pair %d = (row %u, column %u) outside the %d x %d block", i, rows_host[i], cols_host[i], n_rows, ld);
     AMX_HIP(hipSetDevice(ctx->device));
-    int r = ctx->ensure_scratch((size_t)n * 12);
-    if (r != AMX_OK)
-        return r;
-    uint32_t* d_rows = (uint32_t*)ctx->scratch;
+    AMX_TRY(ctx->scratch.reserve((size_t)n * 12));
+    uint32_t* d_rows = (uint32_t*)ctx->scratch.get();
     uint32_t* d_cols = d_rows + n;
     float*    d_out  = (float*)(d_cols + n);
     AMX_HIP(hipMemcpyAsync(d_rows, rows_host, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -23,9 +23,8 @@
 //
 // Numerics: the energy sum has the reference's bits (see energy_sum); the butterflies and the split are f32 with explicit fmaf and
 // table twiddles, where the reference runs f64 recurrences narrowed per butterfly: graded by tolerance like the MFCC chain.
-#include "common.hpp"
+#include "frontend_host.hpp"
 
-#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -36,12 +35,10 @@ struct amx_voicedness {
     amx_ctx*            ctx = nullptr;
     amx_voicedness_cfg  cfg;
     int                 frame_len = 0, frame_shift = 0, fft_len = 0, n_lags = 0, min_pos = 0, max_pos = 0;
-    float2 *            d_tw = nullptr, *d_stw = nullptr;
+    amx::DevBuf<float2> d_tw, d_stw;
     // per-call scratch
-    long long* d_off = nullptr;  // [2][n_seg + 1] sample / frame offsets
-    size_t     off_cap = 0;
-    float *    d_pcm = nullptr, *d_out = nullptr;  // staging of the host entry point
-    size_t     pcm_cap = 0, out_cap = 0;
+    amx::DevBuf<long long> d_off;         // [2][n_seg + 1] sample / frame offsets
+    amx::DevBuf<float>     d_pcm, d_out;  // staging of the host entry point
 };
 
 namespace amx {
@@ -424,7 +421,7 @@ int amx_voicedness_create(amx_ctx* ctx, const amx_voicedness_cfg* c, amx_voicedn
                 "voicedness: unknown normalization %d", c->normalization);
     AMX_REQUIRE(c->min_position_s >= 0 && c->min_position_s < c->max_position_s, AMX_ERR_INVALID,
                 "voicedness: min-position (%f) is larger or equal to max-position (%f).", c->min_position_s, c->max_position_s);
-    amx_voicedness* h = new amx_voicedness;
+    std::unique_ptr<amx_voicedness> h(new amx_voicedness);
     h->ctx            = ctx;
     h->cfg            = *c;
     h->cfg.tuning     = nullptr;
@@ -434,32 +431,19 @@ int amx_voicedness_create(amx_ctx* ctx, const amx_voicedness_cfg* c, amx_voicedn
     // PeakDetection::init: the continuous positions are f32 members (PeakDetection.hh:33-36), the product with the sample rate is f64
     h->min_pos        = (int)(unsigned)std::rint((float)c->min_position_s * c->sample_rate);
     h->max_pos        = (int)(unsigned)std::rint((float)c->max_position_s * c->sample_rate);
-    int         status = AMX_OK;
-    if (h->frame_len < 2 || h->frame_shift < 1 || h->n_lags < 1) {
-        amx::set_error("voicedness: window of %d samples / shift of %d samples / %d lags", h->frame_len, h->frame_shift, h->n_lags);
-        status = AMX_ERR_INVALID;
-    }
-    else if (h->n_lags <= h->max_pos) {  // PeakDetectionNode::work
-        amx::set_error("voicedness: Input size (%d) is smaller or equal to max-position (%d).", h->n_lags, h->max_pos);
-        status = AMX_ERR_INVALID;
-    }
-    else {
-        // RealFastFourierTransform fft(size + K), K = max(|begin|, |end - 1|); FastFourierTransform::setLength
-        const unsigned len = (unsigned)h->frame_len + (unsigned)std::max(std::labs(begin), std::labs(end - 1));
-        unsigned       n   = 1;
-        while (n < len)
-            n <<= 1;
-        h->fft_len = (int)n;
-        if (h->fft_len != 1024 && h->fft_len != 2048) {
-            amx::set_error("voicedness: a window of %d samples with %d lags needs a %d-point transform; 1024 and 2048 are built "
-                           "(40 ms windows at 8 and 16 kHz)", h->frame_len, h->n_lags, h->fft_len);
-            status = AMX_ERR_UNSUPPORTED;
-        }
-    }
-    if (status != AMX_OK) {
-        delete h;
-        return status;
-    }
+    AMX_REQUIRE(h->frame_len >= 2 && h->frame_shift >= 1 && h->n_lags >= 1, AMX_ERR_INVALID,
+                "voicedness: window of %d samples / shift of %d samples / %d lags", h->frame_len, h->frame_shift, h->n_lags);
+    AMX_REQUIRE(h->n_lags > h->max_pos, AMX_ERR_INVALID,  // PeakDetectionNode::work
+                "voicedness: Input size (%d) is smaller or equal to max-position (%d).", h->n_lags, h->max_pos);
+    // RealFastFourierTransform fft(size + K), K = max(|begin|, |end - 1|); FastFourierTransform::setLength
+    const unsigned len = (unsigned)h->frame_len + (unsigned)std::max(std::labs(begin), std::labs(end - 1));
+    unsigned       n   = 1;
+    while (n < len)
+        n <<= 1;
+    h->fft_len = (int)n;
+    AMX_REQUIRE(h->fft_len == 1024 || h->fft_len == 2048, AMX_ERR_UNSUPPORTED,
+                "voicedness: a window of %d samples with %d lags needs a %d-point transform; 1024 and 2048 are built "
+                "(40 ms windows at 8 and 16 kHz)", h->frame_len, h->n_lags, h->fft_len);
     if (ctx) {
         const int           nc = h->fft_len / 2;
         std::vector<float2> tw(nc), stw(nc / 2);
@@ -467,30 +451,17 @@ int amx_voicedness_create(amx_ctx* ctx, const amx_voicedness_cfg* c, amx_voicedn
             tw[k] = make_float2((float)std::cos(2.0 * M_PI * k / nc), (float)std::sin(2.0 * M_PI * k / nc));
         for (int k = 0; k < nc / 2; ++k)
             stw[k] = make_float2((float)std::cos(M_PI * k / nc), (float)std::sin(M_PI * k / nc));
-        if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&h->d_tw, tw.size() * 8) != hipSuccess ||
-            hipMalloc((void**)&h->d_stw, stw.size() * 8) != hipSuccess ||
-            hipMemcpy(h->d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->d_stw, stw.data(), stw.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            amx::set_error("amx_voicedness_create: uploading the twiddle tables failed");
-            amx_voicedness_destroy(h);
-            return AMX_ERR_DEVICE;
-        }
+        AMX_REQUIRE(hipSetDevice(ctx->device) == hipSuccess && h->d_tw.upload(tw.data(), tw.size()) == AMX_OK &&
+                            h->d_stw.upload(stw.data(), stw.size()) == AMX_OK,
+                    AMX_ERR_DEVICE, "amx_voicedness_create: uploading the twiddle tables failed");
     }
-    *out = h;
+    *out = h.release();
     return AMX_OK;
 }
 
 void amx_voicedness_destroy(amx_voicedness* h) {
-    if (!h)
-        return;
-    if (h->ctx) {
+    if (h && h->ctx)
         hipSetDevice(h->ctx->device);
-        hipFree(h->d_tw);
-        hipFree(h->d_stw);
-        hipFree(h->d_off);
-        hipFree(h->d_pcm);
-        hipFree(h->d_out);
-    }
     delete h;
 }
 
@@ -506,12 +477,7 @@ int amx_voicedness_describe(const amx_voicedness* h, amx_voicedness_info* info) 
 }
 
 long amx_voicedness_n_frames(const amx_voicedness* h, long n) {
-    if (!h || n <= 0)
-        return 0;
-    const long reach = std::max(h->frame_len, h->frame_shift);  // TimeWindowBuffer::get / flush: WindowBuffer's rule
-    if (n <= reach)
-        return 1;
-    return (n - reach + h->frame_shift - 1) / h->frame_shift + 1;
+    return h ? amx::window_frames(n, h->frame_len, h->frame_shift) : 0;
 }
 
 static int voicedness_run_batch_dev(amx_voicedness* h, int n_seg, const long* sample_offsets, const void* pcm_dev, bool s16, float* out_dev,
@@ -523,36 +489,16 @@ static int voicedness_run_batch_dev(amx_voicedness* h, int n_seg, const long* sa
     AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "%s: host-only handle (created without a context)", who);
     if (n_seg == 0)
         return AMX_OK;
-    std::vector<long long> off(2 * ((size_t)n_seg + 1));
-    long long*             so = off.data();
-    long long*             fo = off.data() + n_seg + 1;
-    so[0] = sample_offsets[0];
-    fo[0] = 0;
-    for (int u = 0; u < n_seg; ++u) {
-        const long len = sample_offsets[u + 1] - sample_offsets[u];
-        AMX_REQUIRE(len >= 0 && len <= 0x7fffffffL, AMX_ERR_INVALID, "%s: segment %d has invalid length %ld", who, u, len);
-        so[u + 1] = sample_offsets[u + 1];
-        fo[u + 1] = fo[u] + amx_voicedness_n_frames(h, len);
-    }
-    const long long frames = fo[n_seg];
+    long long frames = 0;
+    AMX_TRY(upload_segment_table(h->ctx, h->d_off, n_seg, sample_offsets, [h](long len) { return amx_voicedness_n_frames(h, len); }, who, &frames));
     if (frames == 0)
         return AMX_OK;
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    if (off.size() > h->off_cap) {
-        hipFree(h->d_off);
-        h->d_off   = nullptr;
-        h->off_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_off, off.size() * 8));
-        h->off_cap = off.size();
-    }
-    AMX_HIP(hipMemcpyAsync(h->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->ctx->stream));
-    AMX_HIP(hipStreamSynchronize(h->ctx->stream));  // `off` is a local
     VcParams p;
     p.pcm          = pcm_dev;
-    p.sample_off   = h->d_off;
-    p.frame_off    = h->d_off + n_seg + 1;
-    p.tw           = h->d_tw;
-    p.stw          = h->d_stw;
+    p.sample_off   = h->d_off.get();
+    p.frame_off    = h->d_off.get() + n_seg + 1;
+    p.tw           = h->d_tw.get();
+    p.stw          = h->d_stw.get();
     p.out          = out_dev;
     p.acf          = acf_dev;
     p.total_frames = frames;
@@ -617,29 +563,10 @@ int amx_voicedness_run(amx_voicedness* h, const float* pcm_host, long n_samples,
     const long T = amx_voicedness_n_frames(h, n_samples);
     if (T == 0)
         return AMX_OK;
-    AMX_HIP(hipSetDevice(h->ctx->device));
-    if ((size_t)n_samples > h->pcm_cap) {
-        hipFree(h->d_pcm);
-        h->d_pcm   = nullptr;
-        h->pcm_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_pcm, (size_t)n_samples * 4));
-        h->pcm_cap = (size_t)n_samples;
-    }
-    if ((size_t)T > h->out_cap) {
-        hipFree(h->d_out);
-        h->d_out   = nullptr;
-        h->out_cap = 0;
-        AMX_HIP(hipMalloc((void**)&h->d_out, (size_t)T * 4));
-        h->out_cap = (size_t)T;
-    }
-    AMX_HIP(hipMemcpyAsync(h->d_pcm, pcm_host, (size_t)n_samples * 4, hipMemcpyHostToDevice, h->ctx->stream));
     const long off[2] = {0, n_samples};
-    const int  r      = amx_voicedness_run_batch_dev(h, 1, off, h->d_pcm, h->d_out, 1, nullptr);
-    if (r != AMX_OK)
-        return r;
-    AMX_HIP(hipMemcpyAsync(out_host, h->d_out, (size_t)T * 4, hipMemcpyDeviceToHost, h->ctx->stream));
-    AMX_HIP(hipStreamSynchronize(h->ctx->stream));
-    return AMX_OK;
+    return amx::run_staged(h->ctx, h->d_pcm, h->d_out, pcm_host, (size_t)n_samples, out_host, (size_t)T, [&](const float* pcm_dev, float* out_dev) {
+        return amx_voicedness_run_batch_dev(h, 1, off, pcm_dev, out_dev, 1, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -576,7 +576,7 @@ def test_gmm_tied_dense_pruned_decision_flips(ctx, tuning):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# front ends: workspaces sized to the largest batch so far (mfcc.hip ac_cap, gammatone.hip off_cap / ti_cap)
+# front ends: workspaces sized to the largest batch so far (mfcc.hip d_ac, gammatone.hip d_off / d_ti: DevBuf capacities)
 
 FE_BATCHES = [(48000, 16000, 0, 7777, 32000), (401,), (0, 160), (64000, 400, 12345, 0, 2000), (1,), (5281, 48077)]
 

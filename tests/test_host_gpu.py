@@ -60,6 +60,35 @@ def test_gather_refuses_pairs_outside_the_resident_block(ctx):
         assert "outside the 6 x 50 block" in str(e.value)
 
 
+def test_gather_scratch_grows_and_is_reused():
+    """the context's scratch (index pairs up, scores down) on a context of its own, so that it starts empty: 3 pairs allocate it,
+    5000 pairs grow it, 3 pairs reuse the larger one; amx_stats_accumulate_dev on the same context in between disturbs nothing.
+    Every result is exactly numpy's indexing of the block"""
+    import torch
+
+    import rasr_amd
+    rng = np.random.default_rng(20261017)
+    host = rng.standard_normal((64, 50)).astype(np.float32)
+    block = torch.from_numpy(host).cuda()
+    best = torch.empty(64, dtype=torch.int32, device="cuda")
+    counts = torch.zeros(50, dtype=torch.int64, device="cuda")
+    ssum = torch.zeros(1, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    c = rasr_amd.Context(0)
+    try:
+        c.use_torch_stream()
+        for n in (3, 5000, None, 3):
+            if n is None:
+                c.stats_accumulate(block, 64, 50, best, counts, ssum)
+                continue
+            rows, cols = rng.integers(0, 64, n), rng.integers(0, 50, n)   # repeats allowed
+            assert np.array_equal(c.gather_scores(block, 50, rows, cols), host[rows, cols]), n
+        torch.cuda.synchronize()
+        assert np.array_equal(best.cpu().numpy(), host.argmin(axis=1))
+    finally:
+        c.close()
+
+
 def test_copy_to_device_from_pinned_memory_may_reuse_the_source_on_return(ctx):
     """amx_copy_to_device's contract ("the source may be reused on return") also for a pinned source, where hipMemcpyAsync alone
     would return before the DMA engine has read it"""

@@ -230,3 +230,25 @@ def test_abi_surface_geometry_and_refusals():
     L, h, st = host(normalization=_lib.AMX_XCORR_NONE)
     assert st == 0
     L.amx_voicedness_destroy(h)
+
+
+def test_three_front_ends_count_frames_alike():
+    """one WindowBuffer rule behind amx_mfcc_n_frames, amx_gammatone_n_frames and amx_voicedness_n_frames: on host-only handles with
+    400-sample windows every 160 samples they agree with each other and with the closed form (frames start every `shift` samples
+    until the rest fits into one window)"""
+    import rasr_amd
+    L, vh, st = host(win_len_s=0.025)
+    assert st == 0, L.amx_last_error()
+    mcfg = _lib.MfccCfg()
+    L.amx_mfcc_default_cfg(C.byref(mcfg))
+    mh = C.c_void_p()
+    assert L.amx_mfcc_create(None, C.byref(mcfg), C.byref(mh)) == 0
+    gt = rasr_amd.GammatoneExtractor(None)
+    vi, mi = _lib.VoicednessInfo(), _lib.MfccInfo()
+    assert L.amx_voicedness_describe(vh, C.byref(vi)) == 0 and L.amx_mfcc_describe(mh, C.byref(mi)) == 0
+    assert (vi.frame_len, vi.frame_shift) == (mi.frame_len, mi.frame_shift) == (gt.info.frame_len, gt.info.frame_shift) == (400, 160)
+    for n in (0, 1, 2, 159, 160, 399, 400, 401, 560, 561, 800, 801, 48077):
+        want = 0 if n == 0 else 1 if n <= 400 else -(-(n - 400) // 160) + 1
+        assert L.amx_mfcc_n_frames(mh, n) == gt.n_frames(n) == L.amx_voicedness_n_frames(vh, n) == want, n
+    L.amx_mfcc_destroy(mh)
+    L.amx_voicedness_destroy(vh)
