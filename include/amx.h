@@ -705,6 +705,72 @@ int  amx_histnorm_test_cdf(const amx_histnorm* h, int key, int d, float* bucket_
 int  amx_histnorm_apply_dev(amx_histnorm* h, int n_seg, const long* frame_offsets, const int* key_of_segment, const float* in_dev, int in_ld,
                             float* out_dev, int out_ld, unsigned long long clamped[2]);
 
+/* ------------------------------------------------------------------ Bayes classification: segment, continuous and windowed decisions */
+
+/* amx_bayes is one Signal::BayesClassification (Signal/BayesClassification.hh:36-151) with the uniform prior and the independent-sequence
+ * likelihood, the only types the reference has: the arithmetic of the nodes `signal-bayes-classification` and
+ * `signal-bayes-classification-score` (Signal/Module.cc:126-129) on a [frames x classes] score matrix that a scorer left on the device.
+ * All values are f32.  Per frame t and class c: s = w_t * score(t, c), rounded once (LikelihoodFunction.cc:77); scores_[c] += s in frame
+ * order (:80); sumOfWeights += w_t (LikelihoodFunction.hh:55); w_t = 1 without a weight stream.  Both builds of the reference compute
+ * this alike (the product is stored as well as added, so it is not contracted): nothing here depends on amx_set_contract.
+ * Prior: logN = std::log((f32)n_classes) (AprioriProbability.cc:20).  Decision (argMin, BayesClassification.cc:135-161): per class
+ * score = logN, then += scores_[c] without a window, or += every stored s of the window FROM THE NEWEST FRAME TO THE OLDEST with one; strict
+ * `<` from FLT_MAX picks the label, so the first minimum wins and a NaN or a value >= FLT_MAX never does.  Where no class wins the
+ * reference indexes out of range; here the label is -1 and a counter reports it.
+ * Modes (classify, work: :103-119, :384-411):
+ *   segment     number_of_features, delay, window_length unset: one label at the end of the stream over all frames; none for 0 frames.
+ *   first N     number_of_features = N: the label after frame N - 1 over frames 0 .. N - 1, later frames are not scored; N >= T: segment mode.
+ *   continuous  delay = d: a label after every frame t >= d over frames 0 .. t; when no frame reached t >= d, one label at the end of
+ *               the stream.
+ *   windowed    window_length = L: the window holds the last L frames; a label after every frame once it is full (delay unset), or when it
+ *               is full and at least d frames came since the last label; one more label at the end of the stream, over what the window
+ *               holds, if frames came after the last label or the window never filled.  window_right does not change what the window
+ *               holds (SlidingWindow.hh:445-452) but must be < L.
+ * Refused with AMX_ERR_INVALID, the message naming the parameter: n_classes < 1; window_right >= window_length (the reference's init fails);
+ * a window together with number_of_features, and delay together with number_of_features (the reference lets both through and emits a
+ * label at frame N - 1 that belongs to neither mode). */
+typedef struct {
+    int  n_classes;            /* >= 1 */
+    long number_of_features;   /* <= 0 or >= INT_MAX: all frames */
+    long delay;                /* < 0 or >= INT_MAX: no continuous output */
+    int  window_length;        /* <= 0: no window */
+    int  window_right;         /* must be < window_length when a window is used */
+    int  single_frame;         /* score node only: single-frame-classification */
+} amx_bayes_cfg;
+typedef struct amx_bayes amx_bayes;
+void amx_bayes_default_cfg(amx_bayes_cfg* cfg); /* the node's defaults (:294-303): segment mode; n_classes 0 has to be set */
+int  amx_bayes_create(amx_ctx* ctx /* nullable: configuration and prior only */, const amx_bayes_cfg* cfg, amx_bayes** out);
+void amx_bayes_destroy(amx_bayes* h);
+int  amx_bayes_prior(const amx_bayes* h, float* log_n_classes); /* UniformAprioriProbability::setClasses (AprioriProbability.cc:19-22) */
+/* BayesClassificationNode::work (:384-411) for n_seg segments in one launch sequence.  Segment s = frames [frame_offsets[s],
+ * frame_offsets[s + 1]) (host list, absolute row numbers) of scores_dev[t * scores_ld + c], weights_dev[t] (NULL: 1) and frame_label_dev[t].
+ *   segment_label_dev[s]  the label that leaves at the end of the stream, or the single label of segment / first-N mode; -1 where the
+ *                         reference emits none (no frames; continuous or windowed mode whose last frame emitted its own label)
+ *   segment_score_dev     nullable, [n_seg x n_classes]: logN + sum per class as argMin formed it for that label; rows of segments
+ *                         without such a label keep what the buffer held
+ *   frame_label_dev[t]    continuous and windowed mode (required there, ignored otherwise): the label emitted after frame t, -1 where none is
+ *   sum_of_weights_dev    nullable, [n_seg]: sumOfWeights() at the end of the stream (first-N mode: over the frames scored)
+ *   no_winner             nullable, host: [0] = segment labels, [1] = frame labels that are -1 because no class won; asking synchronises
+ * A weight of a scored frame that is negative or NaN (BayesClassificationNode::featureScoreWeight, :364-382, a critical error there) fails
+ * the call with AMX_ERR_INVALID naming the first such frame, and nothing is written; with weights the call synchronises the stream once.
+ * The call keeps frames x n_classes floats of scratch in the handle in continuous and windowed mode. */
+int  amx_bayes_classify_dev(amx_bayes* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* scores_dev, int scores_ld,
+                            const float* weights_dev, int32_t* segment_label_dev, float* segment_score_dev, int32_t* frame_label_dev,
+                            float* sum_of_weights_dev, unsigned long long no_winner[2]);
+/* BayesClassificationScoreNode::work (:429-444; getScores :121-133, :182-189): after every frame t >= delay the vector logN + scores_[c]
+ * of the cumulative sums (never the window) leaves; with single_frame the sums are reset after each vector, so a vector leaves every
+ * delay + 1 frames over those frames.  Row t of out_dev[t * out_ld + c] is written where a vector leaves after frame t (emitted_dev[t] = 1).
+ * The vector that leaves at the end of the stream, when frames came after the last one, is stored in the row of the segment's last frame
+ * (emitted_dev[t] = 2).  Other rows keep what the buffer held (emitted_dev[t] = 0).  number_of_features and the window do not act here. */
+int  amx_bayes_scores_dev(amx_bayes* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* scores_dev, int scores_ld,
+                          const float* weights_dev, float* out_dev, int out_ld, uint8_t* emitted_dev);
+/* The fast-VTLN composition (one mixture per warping factor): amx_gmm_score_dev(gmm, mode, feats_dev + frame_offsets[0] * dim, frames)
+ * into a score matrix the handle owns, then amx_bayes_classify_dev on it.  feats_dev is [frames x amx_gmm_dimension(gmm)], dense.
+ * amx_gmm_n_mixtures(gmm) != n_classes is AMX_ERR_INVALID (IndependentSequenceLikelihood::setClasses, LikelihoodFunction.cc:34-45). */
+int  amx_bayes_classify_gmm_dev(amx_bayes* h, amx_gmm* gmm, int mode, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* feats_dev,
+                                const float* weights_dev, int32_t* segment_label_dev, float* segment_score_dev, int32_t* frame_label_dev,
+                                float* sum_of_weights_dev, unsigned long long no_winner[2]);
+
 /* ------------------------------------------------------------------ mixture-set text files (.pms) */
 
 /* Reader / writer of RASR's text mixture-set format, "#Version: 2.0" (Mm/MixtureSet.cc:141-216,

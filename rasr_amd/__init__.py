@@ -10,6 +10,7 @@ same reference interfaces for tests and benchmarks:
   GmmFeatureScorer     Mm::FeatureScorer over a Mm::MixtureSet (diagonal-maximum / diagonal-sum)
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
   ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
+  BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
   FileArchive          Core::FileArchive + Flow cache entries (feature caches between jobs; host IO)
 """
 import ctypes as C
@@ -24,6 +25,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
+           "BayesClassifier",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1171,6 +1173,89 @@ class HistogramNormalization:
         _lib.check(self.L.amx_histnorm_apply_dev(self.h, len(keys), off.ctypes.data, keys.ctypes.data, _ptr(in_dev), int(in_ld), _ptr(out_dev), int(out_ld),
                                                  cl.ctypes.data if count_clamped else None))
         return (int(cl[0]), int(cl[1])) if count_clamped else None
+
+
+class BayesClassifier:
+    """Signal::BayesClassification with the uniform prior: the decisions of `signal-bayes-classification` (classify) and the vectors of
+    `signal-bayes-classification-score` (scores) for a batch of segments whose [frames x classes] score matrix is on the device.
+    Keyword names are the fields of amx_bayes_cfg (= the nodes' parameters); ctx None gives a handle for configuration and prior only."""
+
+    def __init__(self, ctx, n_classes, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.BayesCfg()
+        self.L.amx_bayes_default_cfg(C.byref(cfg))
+        cfg.n_classes = int(n_classes)
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("BayesClassifier: unknown parameter %r" % k)
+            setattr(cfg, k, int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_bayes_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.n_classes = cfg.n_classes
+        self.per_frame = cfg.window_length > 0 or 0 <= cfg.delay < 2 ** 31 - 1
+
+    def close(self):
+        if self.h:
+            self.L.amx_bayes_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def prior(self):
+        """log(n_classes) as the reference's f32 holds it"""
+        v = C.c_float()
+        _lib.check(self.L.amx_bayes_prior(self.h, C.byref(v)))
+        return np.float32(v.value)
+
+    @staticmethod
+    def _offsets(frame_offsets):
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError("BayesClassifier: frame_offsets must hold n_seg + 1 offsets")
+        return off
+
+    def classify(self, frame_offsets, scores_dev, scores_ld, segment_label_dev, weights_dev=None, segment_score_dev=None, frame_label_dev=None,
+                 sum_of_weights_dev=None, count_no_winner=True):
+        """segment s = rows [frame_offsets[s], frame_offsets[s + 1]) of scores_dev.  Fills segment_label_dev (int32 [n_seg]) and the optional
+        buffers (amx_bayes_classify_dev); returns (segment labels, frame labels) that are -1 because no class won, or None without the
+        synchronisation when count_no_winner is False."""
+        off = self._offsets(frame_offsets)
+        nw = np.zeros(2, np.uint64)
+        _lib.check(self.L.amx_bayes_classify_dev(self.h, len(off) - 1, off.ctypes.data, _ptr(scores_dev), int(scores_ld), _ptr(weights_dev),
+                                                 _ptr(segment_label_dev), _ptr(segment_score_dev), _ptr(frame_label_dev), _ptr(sum_of_weights_dev),
+                                                 nw.ctypes.data if count_no_winner else None))
+        return (int(nw[0]), int(nw[1])) if count_no_winner else None
+
+    def scores(self, frame_offsets, scores_dev, scores_ld, out_dev, out_ld, emitted_dev, weights_dev=None):
+        """the score node: row t of out_dev where a vector leaves after frame t (emitted_dev[t] = 1) or, in the segment's last row, at the
+        end of the stream (2); other rows keep what they held"""
+        off = self._offsets(frame_offsets)
+        _lib.check(self.L.amx_bayes_scores_dev(self.h, len(off) - 1, off.ctypes.data, _ptr(scores_dev), int(scores_ld), _ptr(weights_dev), _ptr(out_dev),
+                                               int(out_ld), _ptr(emitted_dev)))
+
+    def classify_gmm(self, gmm, frame_offsets, feats_dev, segment_label_dev, weights_dev=None, segment_score_dev=None, frame_label_dev=None,
+                     sum_of_weights_dev=None, count_no_winner=True):
+        """fast VTLN in one call: gmm (a GmmFeatureScorer of the same context, one mixture per class) scores feats_dev [frames, dim] into a
+        matrix the handle owns, then classify"""
+        off = self._offsets(frame_offsets)
+        nw = np.zeros(2, np.uint64)
+        _lib.check(self.L.amx_bayes_classify_gmm_dev(self.h, gmm.h, gmm.mode, len(off) - 1, off.ctypes.data, _ptr(feats_dev), _ptr(weights_dev),
+                                                     _ptr(segment_label_dev), _ptr(segment_score_dev), _ptr(frame_label_dev),
+                                                     _ptr(sum_of_weights_dev), nw.ctypes.data if count_no_winner else None))
+        return (int(nw[0]), int(nw[1])) if count_no_winner else None
+
+    @staticmethod
+    def warping_factors(labels, factors):
+        """segment labels -> the warping factor of each segment for MfccExtractor.plan (amx_mfcc_plan_create_vtln): class c is the c-th of
+        the VTLN handle's factors.  A label of -1 (no frames, no winner) has no factor and raises."""
+        labels = np.asarray(labels).astype(np.int64)
+        factors = np.asarray(factors, np.float64)
+        bad = np.nonzero((labels < 0) | (labels >= len(factors)))[0]
+        if len(bad):
+            raise ValueError("BayesClassifier.warping_factors: segment %d has label %d, outside the %d factors" % (bad[0], labels[bad[0]], len(factors)))
+        return factors[labels]
 
 
 def layer_from_parameters(params, has_bias=True):

@@ -72,6 +72,11 @@ class HistogramInfo(C.Structure):
                 ("frames", C.c_ulonglong), ("n_lds", C.c_ulonglong), ("n_global", C.c_ulonglong), ("n_device_calls", C.c_ulonglong)]
 
 
+class BayesCfg(C.Structure):
+    _fields_ = [("n_classes", C.c_int), ("number_of_features", C.c_long), ("delay", C.c_long), ("window_length", C.c_int),
+                ("window_right", C.c_int), ("single_frame", C.c_int)]
+
+
 AMX_XCORR_NONE, AMX_XCORR_UNBIASED_ESTIMATE, AMX_XCORR_UPPER_BOUND = 0, 1, 2
 
 
@@ -214,6 +219,13 @@ SIGNATURES = {
     "amx_histnorm_inverse_cdf": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "amx_histnorm_test_cdf": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "amx_histnorm_apply_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "amx_bayes_default_cfg": (None, [C.POINTER(BayesCfg)]),
+    "amx_bayes_create": (C.c_int, [_P, C.POINTER(BayesCfg), C.POINTER(_P)]),
+    "amx_bayes_destroy": (None, [_P]),
+    "amx_bayes_prior": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "amx_bayes_classify_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "amx_bayes_scores_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
+    "amx_bayes_classify_gmm_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "amx_gmm_estimate_cfg_default": (None, [C.POINTER(GmmEstimateCfg)]),
     "amx_gmm_estimate": (C.c_int, [C.POINTER(GmmModel), _P, C.POINTER(GmmEstimateCfg), C.POINTER(_P)]),
     "amx_gmm_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),
