@@ -771,6 +771,86 @@ int  amx_bayes_classify_gmm_dev(amx_bayes* h, amx_gmm* gmm, int mode, int n_seg,
                                 const float* weights_dev, int32_t* segment_label_dev, float* segment_score_dev, int32_t* frame_label_dev,
                                 float* sum_of_weights_dev, unsigned long long no_winner[2]);
 
+/* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
+
+/* amx_quanteq is one Signal::QuantileEqualization (Signal/QuantileEqualization.{hh,cc}) in SEGMENT MODE (length = right = INT_MAX): the
+ * arithmetic of the node `signal-quantile-equalization` (Signal/Module.cc:145) for a batch of segments whose [frames x dim] f32 feature
+ * matrix is on the device.  Per segment of T frames, once, over all T frames (QuantileEqualization.cc:149-307):
+ *   quantiles   per channel d the column is sorted; currentQuantile[i * dim + d] = sorted[(u32)(i * (T - 1) / nq)], i = 0 .. nq.
+ *   alpha/gamma maximalQuantile = max(of * tq[nq], of * cq[nq]) (f32); scaled_i = max(tq[i], cq[i]) / maximalQuantile (f32);
+ *               transformed_i = (f32)((f64)maximalQuantile * ((f64)a * pow((f64)scaled_i, (f64)g) + (1. - (f64)a) * (f64)scaled_i)), pow the
+ *               double function; distance = sum over i = 1 .. nq - 1 of (transformed_i - tq[i])^2 in f32.  The grid is what the
+ *               reference's loop `for (f32 a = lo; a <= hi; a += (f64)step)` visits ([0, 1] for alpha, [1, 3] for gamma; 201 x 201 with
+ *               the default steps, which are (f64)(f32)0.005 and (f64)(f32)0.01); the winner is the first point, alpha outer, whose
+ *               distance is < the best so far, starting from FLT_MAX: NaN and infinite distances never win, and where none wins
+ *               alpha = 0, gamma = 1.  The interior quantiles are then replaced by their transformed values.
+ *   lambda/rho  (combination) over [0, 0.5]^2, step delta_lambda_and_rho: (1. - l - r) * cq[i][d] + l * cq[i][max(d - 1, 0)] +
+ *               r * cq[i][min(d + 1, dim - 1)] on the TRANSFORMED quantiles (the first product f64, the other two f32, summed in f64), narrowed, distance as above plus (l * l + r * r) * beta.
+ *   apply       x -> the power function of x / maximalQuantile under the winning (alpha, gamma); then the neighbour combination, all
+ *               channels read from the frame before the combination; then - mean and, with variance, / deviation, where
+ *               mean = (f32)(sum / T), deviation = (f32)sqrt((sumSquare - sum * sum / T) / T) are f64 sums over the transformed frames from
+ *               the oldest to the newest.  variance without mean does nothing (:330-335), and its reported deviation is 0.
+ * Division by a zero maximalQuantile or deviation gives inf / NaN where the reference gives them.
+ * amx_set_contract selects which build of the reference is followed: its -march=native build contracts `distance += tmp * tmp`,
+ * `a * pow + (1. - a) * scaled` (the first product), the f64 product of the combination, `l * l + r * r`, the penalty's
+ * `distance += ... * beta` and `sumSquare += x * x`.
+ * Not copied from the reference: only the first object of a process reads its training file there (`firstcall` is a function-local
+ * static, :29); here every handle gets its training quantiles.
+ * Bounds: dim <= AMX_QUANTEQ_MAX_DIM; number_of_quantiles 1 .. AMX_QUANTEQ_MAX_QUANTILES; a grid side of at most AMX_QUANTEQ_MAX_GRID_SIDE
+ * points; a segment of at most AMX_QUANTEQ_MAX_SEGMENT_FRAMES frames (the column is sorted in LDS). */
+#define AMX_QUANTEQ_MAX_DIM 4096
+#define AMX_QUANTEQ_MAX_QUANTILES 16
+#define AMX_QUANTEQ_MAX_GRID_SIDE 4096
+#define AMX_QUANTEQ_MAX_SEGMENT_FRAMES 16384
+typedef struct {
+    int   quantiles;             /* `quantiles`, 1 */
+    int   combination;           /* `combination`, 0 */
+    int   estimate;              /* `estimate`, 0: 1 gives a handle for amx_quanteq_estimate_dev only */
+    int   mean;                  /* `mean`, 1 */
+    int   variance;              /* `variance`, 0 */
+    int   number_of_quantiles;   /* `numberOfQuantiles`, 4 */
+    float overestimation_factor; /* `overestimationFactor`, 1 */
+    float delta_alpha;           /* `deltaAlpha`, .005: f32 as the reference's setter takes it */
+    float delta_gamma;           /* `deltaGamma`, .01 */
+    float delta_lambda_and_rho;  /* `deltaLambdaAndRho`, .005 */
+    float beta;                  /* `beta`, .05 */
+    int   pool_quantiles;        /* `poolQuantiles`, 1: acts in amx_quanteq_quantiles_read, whose result create takes */
+    int   piecewise_linear;      /* `piecewiseLinear`, 0; 1 is refused */
+    long  length;                /* `length`: anything below INT_MAX is the sliding-window mode, refused */
+    long  right;                 /* `right`: likewise */
+} amx_quanteq_cfg;
+typedef struct amx_quanteq amx_quanteq;
+void amx_quanteq_default_cfg(amx_quanteq_cfg* cfg);
+/* training_quantiles: [(nq + 1) x dim], element [i * dim + d], as amx_quanteq_quantiles_read returns them; NULL with quantiles = 0 or
+ * estimate = 1.  AMX_ERR_UNSUPPORTED, naming the parameter: length / right below INT_MAX, piecewise_linear, a step <= 0 (the reference
+ * loops forever) or a grid of more than AMX_QUANTEQ_MAX_GRID_SIDE points a side, number_of_quantiles outside its bounds. */
+int  amx_quanteq_create(amx_ctx* ctx /* nullable: configuration and grids only */, int dim, const amx_quanteq_cfg* cfg, const float* training_quantiles,
+                        amx_quanteq** out);
+void amx_quanteq_destroy(amx_quanteq* h);
+/* the grid tables as the reference's loops visit them: which = 0 alpha, 1 gamma, 2 lambda and rho; values nullable */
+int  amx_quanteq_grid(const amx_quanteq* h, int which, int* n, float* values);
+/* The training quantile file (text): per channel one line `"%i " d`, then `"%f "` for i = 0 .. nq, then "\n"
+ * (writeEstimatedQuantilesToFile, :103-119: value = sums[i * dim + d] / (u32)count).  read (:70-101) fills out[(nq + 1) x dim]; with pool
+ * each quantile is replaced by its f32 average over the channels (f32 sum in channel order, divided by dim).  A file that cannot be
+ * opened or holds fewer numbers is AMX_ERR_INVALID. */
+int  amx_quanteq_quantiles_read(const char* path, int dim, int nq, int pool, float* out);
+int  amx_quanteq_quantiles_write(const char* path, int dim, int nq, const double* sums, unsigned long long count);
+/* The whole node for segments s = frames [frame_offsets[s], frame_offsets[s + 1]) (host list, absolute rows) of in_dev[t * in_ld + d] into
+ * out_dev[t * out_ld + d]; columns >= dim are neither read nor written; out_dev may be in_dev with out_ld == in_ld.  An empty segment does
+ * nothing.  params_host (nullable): [n_seg x dim * (6 + nq + 1)] floats, per segment alpha[dim], gamma[dim], lambda[dim], rho[dim],
+ * mean[dim], deviation[dim], then the (nq + 1) x dim current quantiles AS FIRST TAKEN (before the interior ones are replaced); all zero for
+ * an empty segment.  With quantiles = 1 the call synchronises the stream once after the quantile kernel, and again when params_host is asked
+ * for.  A value of columns < dim that is not finite fails the call with AMX_ERR_INVALID naming the first (segment, channel), and nothing
+ * is written (std::sort is undefined on NaN).  -0 sorts before +0 (the reference leaves their order to the sort).  A segment of more than
+ * AMX_QUANTEQ_MAX_SEGMENT_FRAMES frames is AMX_ERR_UNSUPPORTED, naming it. */
+int  amx_quanteq_apply_dev(amx_quanteq* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* in_dev, int in_ld, float* out_dev,
+                           int out_ld, float* params_host);
+/* estimate = 1 (:171-172, :314-317): the quantiles of every non-empty segment, taken on the device, are added to the handle's f64 sums on the
+ * host in segment order, one count per segment; any split of the segments over calls gives the same sums.  The node's output stream in
+ * this mode is not built.  amx_quanteq_estimate_result copies the sums [(nq + 1) x dim] and the count for amx_quanteq_quantiles_write. */
+int  amx_quanteq_estimate_dev(amx_quanteq* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* in_dev, int in_ld);
+int  amx_quanteq_estimate_result(const amx_quanteq* h, double* sums, unsigned long long* count);
+
 /* ------------------------------------------------------------------ mixture-set text files (.pms) */
 
 /* Reader / writer of RASR's text mixture-set format, "#Version: 2.0" (Mm/MixtureSet.cc:141-216,

@@ -11,6 +11,7 @@ same reference interfaces for tests and benchmarks:
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
   ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
   BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
+  QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
   FileArchive          Core::FileArchive + Flow cache entries (feature caches between jobs; host IO)
 """
 import ctypes as C
@@ -25,7 +26,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier",
+           "BayesClassifier", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1256,6 +1257,118 @@ class BayesClassifier:
         if len(bad):
             raise ValueError("BayesClassifier.warping_factors: segment %d has label %d, outside the %d factors" % (bad[0], labels[bad[0]], len(factors)))
         return factors[labels]
+
+
+def _quanteq_cfg(L, kw, who):
+    cfg = _lib.QuanteqCfg()
+    L.amx_quanteq_default_cfg(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError("%s: unknown parameter %r" % (who, k))
+        setattr(cfg, k, v if isinstance(getattr(cfg, k), float) else int(v))
+    return cfg
+
+
+def _offsets(frame_offsets, who):
+    off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("%s: frame_offsets must hold n_seg + 1 offsets" % who)
+    return off
+
+
+def read_quantiles(path, dim, number_of_quantiles=4, pool=True):
+    """the training quantile file of `signal-quantile-equalization` -> f32 [(nq + 1), dim]; pool: each quantile averaged over the channels"""
+    out = np.zeros((int(number_of_quantiles) + 1, int(dim)), np.float32)
+    _lib.check(_lib.lib().amx_quanteq_quantiles_read(os.fsencode(path), int(dim), int(number_of_quantiles), int(bool(pool)), out.ctypes.data))
+    return out
+
+
+def write_quantiles(path, sums, count):
+    """the file the node writes in estimation mode: sums f64 [(nq + 1), dim] divided by count"""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    _lib.check(_lib.lib().amx_quanteq_quantiles_write(os.fsencode(path), s.shape[1], s.shape[0] - 1, s.ctypes.data, int(count)))
+
+
+class QuantileEqualization:
+    """Signal::QuantileEqualization in segment mode: quantiles, the alpha / gamma (and lambda / rho) grid search, the power function and
+    joint mean / variance normalisation for a batch of segments in one call.  Keyword names are the fields of amx_quanteq_cfg (= the
+    node's parameters); training_quantiles is what read_quantiles returns; ctx None gives a handle for configuration and grids only."""
+
+    def __init__(self, ctx, dim, training_quantiles=None, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _quanteq_cfg(self.L, kw, type(self).__name__)
+        self._configure(cfg)
+        tq = None
+        if training_quantiles is not None:
+            tq = np.ascontiguousarray(training_quantiles, dtype=np.float32)
+            if tq.shape != (cfg.number_of_quantiles + 1, int(dim)):
+                raise ValueError("%s: training_quantiles has shape %s, not %s" % (type(self).__name__, tq.shape, (cfg.number_of_quantiles + 1, int(dim))))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_quanteq_create(ctx.h if ctx is not None else None, int(dim), C.byref(cfg), _ptr(tq), C.byref(h)))
+        self.h = h
+        self.dim, self.nq = int(dim), cfg.number_of_quantiles
+
+    def _configure(self, cfg):
+        if cfg.estimate:
+            raise TypeError("QuantileEqualization: estimate = 1 is QuantileEstimator")
+
+    def close(self):
+        if self.h:
+            self.L.amx_quanteq_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def grid(self, which):
+        """the grid the search walks: "alpha", "gamma" or "lambda" (also rho's)"""
+        k = {"alpha": 0, "gamma": 1, "lambda": 2, "rho": 2}[which]
+        n = C.c_int()
+        _lib.check(self.L.amx_quanteq_grid(self.h, k, C.byref(n), None))
+        v = np.zeros(n.value, np.float32)
+        _lib.check(self.L.amx_quanteq_grid(self.h, k, C.byref(n), v.ctypes.data))
+        return v
+
+    def apply_dev(self, frame_offsets, in_dev, in_ld, out_dev, out_ld, want_params=False):
+        """segment s = rows [frame_offsets[s], frame_offsets[s + 1]); out_dev may be in_dev.  With want_params returns a dict of
+        alpha, gamma, lambda, rho, mean, deviation [n_seg, dim] and quantiles [n_seg, nq + 1, dim] (as first taken)."""
+        off = _offsets(frame_offsets, "QuantileEqualization.apply_dev")
+        n_seg = len(off) - 1
+        par = np.zeros((n_seg, 6 + self.nq + 1, self.dim), np.float32) if want_params else None
+        _lib.check(self.L.amx_quanteq_apply_dev(self.h, n_seg, off.ctypes.data, _ptr(in_dev), int(in_ld), _ptr(out_dev), int(out_ld), _ptr(par)))
+        if not want_params:
+            return None
+        out = {name: par[:, k] for k, name in enumerate(("alpha", "gamma", "lambda", "rho", "mean", "deviation"))}
+        out["quantiles"] = par[:, 6:]
+        return out
+
+
+class QuantileEstimator(QuantileEqualization):
+    """the node with estimate = true: the quantiles of every segment, taken on the device, summed on the host in segment order"""
+
+    def __init__(self, ctx, dim, **kw):
+        super().__init__(ctx, dim, None, estimate=1, **kw)
+
+    def _configure(self, cfg):
+        pass
+
+    def apply_dev(self, *a, **kw):
+        raise TypeError("QuantileEstimator: the output stream of estimation mode is not built")
+
+    def accumulate_dev(self, frame_offsets, in_dev, in_ld):
+        off = _offsets(frame_offsets, "QuantileEstimator.accumulate_dev")
+        _lib.check(self.L.amx_quanteq_estimate_dev(self.h, len(off) - 1, off.ctypes.data, _ptr(in_dev), int(in_ld)))
+
+    def result(self):
+        """(sums f64 [nq + 1, dim], count)"""
+        sums = np.zeros((self.nq + 1, self.dim), np.float64)
+        n = C.c_ulonglong()
+        _lib.check(self.L.amx_quanteq_estimate_result(self.h, sums.ctypes.data, C.byref(n)))
+        return sums, n.value
+
+    def write(self, path):
+        sums, n = self.result()
+        write_quantiles(path, sums, n)
 
 
 def layer_from_parameters(params, has_bias=True):

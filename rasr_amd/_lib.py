@@ -77,6 +77,14 @@ class BayesCfg(C.Structure):
                 ("window_right", C.c_int), ("single_frame", C.c_int)]
 
 
+class QuanteqCfg(C.Structure):
+    _fields_ = [("quantiles", C.c_int), ("combination", C.c_int), ("estimate", C.c_int), ("mean", C.c_int), ("variance", C.c_int),
+                ("number_of_quantiles", C.c_int), ("overestimation_factor", C.c_float), ("delta_alpha", C.c_float), ("delta_gamma", C.c_float),
+                ("delta_lambda_and_rho", C.c_float), ("beta", C.c_float), ("pool_quantiles", C.c_int), ("piecewise_linear", C.c_int),
+                ("length", C.c_long), ("right", C.c_long)]
+
+
+AMX_QUANTEQ_MAX_DIM, AMX_QUANTEQ_MAX_QUANTILES, AMX_QUANTEQ_MAX_GRID_SIDE, AMX_QUANTEQ_MAX_SEGMENT_FRAMES = 4096, 16, 4096, 16384
 AMX_XCORR_NONE, AMX_XCORR_UNBIASED_ESTIMATE, AMX_XCORR_UPPER_BOUND = 0, 1, 2
 
 
@@ -226,6 +234,15 @@ SIGNATURES = {
     "amx_bayes_classify_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "amx_bayes_scores_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "amx_bayes_classify_gmm_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
+    "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
+    "amx_quanteq_destroy": (None, [_P]),
+    "amx_quanteq_grid": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P]),
+    "amx_quanteq_quantiles_read": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, _P]),
+    "amx_quanteq_quantiles_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P, C.c_ulonglong]),
+    "amx_quanteq_apply_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "amx_quanteq_estimate_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "amx_quanteq_estimate_result": (C.c_int, [_P, _P, C.POINTER(C.c_ulonglong)]),
     "amx_gmm_estimate_cfg_default": (None, [C.POINTER(GmmEstimateCfg)]),
     "amx_gmm_estimate": (C.c_int, [C.POINTER(GmmModel), _P, C.POINTER(GmmEstimateCfg), C.POINTER(_P)]),
     "amx_gmm_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),
