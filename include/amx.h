@@ -472,6 +472,8 @@ int  amx_gmm_create(amx_ctx* ctx, const amx_gmm_model* model, amx_gmm** out); /*
 void amx_gmm_destroy(amx_gmm* h);
 int  amx_gmm_n_mixtures(const amx_gmm* h);
 int  amx_gmm_dimension(const amx_gmm* h);
+/* the topology as amx_gmm_model holds it: *n_entries = mix_offsets[n_mix]; mix_offsets [n_mix + 1] and dens_index [n_entries] nullable */
+int  amx_gmm_topology(const amx_gmm* h, int* n_entries, uint32_t* mix_offsets, uint32_t* dens_index);
 /* host copies of the prepared scorer tables (Mm/MixtureFeatureScorerElement.cc:21-33,
  * Mm/CovarianceFeatureScorerElement.cc:21-51); any pointer may be NULL */
 int amx_gmm_tables(const amx_gmm* h, float* minus2_log_weights, float* inv_sqrt_var, float* log_norm);
@@ -770,6 +772,121 @@ int  amx_bayes_scores_dev(amx_bayes* h, int n_seg, const long* frame_offsets /*[
 int  amx_bayes_classify_gmm_dev(amx_bayes* h, amx_gmm* gmm, int mode, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* feats_dev,
                                 const float* weights_dev, int32_t* segment_label_dev, float* segment_score_dev, int32_t* frame_label_dev,
                                 float* sum_of_weights_dev, unsigned long long no_winner[2]);
+
+/* ------------------------------------------------------------------ State posteriors: p(mixture | x) from a score matrix on the device */
+
+/* amx_posterior is one Mm::StatePosteriorFeatureScorer (Mm/StatePosteriorFeatureScorer.{hh,cc}) with viterbi = true, working on
+ * scores_dev[t * scores_ld + m] (f32, as any scorer of this library leaves it) for T frames.  All arithmetic is f64 (Mm::Weight,
+ * Mm/Types.hh:30) with the device's double exp and log1p.  Per frame, over the mixtures m of the filter, in this order:
+ *   s(m)      = prior(m) + scale * score(t, m)                                                   (cc:43, cc:90, cc:265)
+ *   min, imin = the smallest s below DBL_MAX and its mixture; strict <, the FIRST index wins     (cc:49-52; the reference's choice
+ *               among equal values follows its hash order and changes no value)
+ *   stored(m) = s(m), in density-keyed mode + margin where m == margin_mixture[t]                (cc:45-48: the minimum is taken over
+ *               the un-margined values)
+ *   survivors = every m of the filter when pruning_threshold == DBL_MAX, else stored(m) < pruning_threshold + min   (cc:105-116)
+ *   p(m)      = min - stored(m)                                                                  (cc:134)
+ *   sum       = sum of exp(p(m)) over the survivors except imin's own entry                      (cc:135-137)
+ *   logZs     = log1p(sum); posterior(m) = exp(p(m) - logZs); logZ = logZs - min                 (cc:139-143)
+ * Mixture likelihoods (workMixtureLikelihoods, cc:162-165, 201-207): exp(-stored(m)) per survivor; log_z_dev is not written.
+ * s follows amx_set_contract: the reference's -march=native build contracts it into one fused multiply-add
+ * (tests/golden/ref_posterior.npz records where the two builds differ: wherever scale != 1 and the prior is not 0).
+ * The order of the f64 sum is fixed per row (the reference's is the iteration order of a std::unordered_map): a frame's results are
+ * the same bits whatever the batch, the frame's place in it or the other frames.  Against the reference logZ and the f64 posteriors
+ * agree to 1e-11 relative (a reordered sum of n <= 16384 non-negative terms moves by (n - 1) * 2^-53).
+ * Deviation, on purpose: in the reference the MIXTURE paths never assign minimumScore_ (workMixtureScores, cc:81-102, leaves it at the
+ * DBL_MAX of reset()), so posteriorsAndMixtures() there yields 0 everywhere with logZ = inf and pruneScores prunes nothing.  Here the
+ * mixture modes compute the lines above, which is what the reference's density path computes for one density per mixture.
+ * Filter (a prior per mixture): the default is every mixture with prior 0 (DefaultFilter, cc:361-368).  The disregard list is erased
+ * from the filter AS MIXTURE INDICES, whatever the parameter's name says (hh:148-154: filter_->erase(*it) on a map keyed by mixture);
+ * numbers that name no mixture of the filter do nothing.
+ * Refused: viterbi = 0 with AMX_ERR_UNSUPPORTED naming `viterbi` (it needs per-density scores no scorer here exports); n_mixtures < 1,
+ * a filter index out of range, a filter that is empty (also once the disregard list is erased) with AMX_ERR_INVALID.  Context
+ * priors, the statistics channel and Mc::ScaleUpdate have no counterpart.
+ * Added rules: a frame in which no mixture of the filter has s < DBL_MAX, or whose minimum is -inf, gets min index -1, min DBL_MAX,
+ * logZ 0, outputs 0 and no survivors, and is counted (no_minimum, host, nullable; asking synchronises the stream). */
+typedef struct {
+    int    n_mixtures;         /* >= 1 */
+    double scale;              /* 1 */
+    double pruning_threshold;  /* DBL_MAX: none */
+    double margin;             /* 0; acts in density-keyed mode */
+    int    viterbi;            /* 1; 0 is refused */
+} amx_posterior_cfg;
+enum { AMX_POSTERIOR_MIXTURE = 0 /* workMixturePosteriors */, AMX_POSTERIOR_LIKELIHOOD = 1 /* workMixtureLikelihoods */,
+       AMX_POSTERIOR_DENSITY = 2 /* workDensityPosteriors */ };
+/* Outputs of one call, each nullable (the three sparse arrays together).
+ *   posterior_f32_dev / posterior_f64_dev  [T x ld], ld >= n_mixtures: column m holds mixture m's value, 0 where m was filtered or pruned;
+ *                                          the f32 value is the narrowed f64 one (the Flow node's Sparse::Vector<f32>)
+ *   log_z_dev, min_dev [T] f64; min_index_dev [T]: imin (a MIXTURE index in every mode); n_survivors_dev [T]
+ *   sparse_index_dev / sparse_value_dev    [T x sparse_capacity]: the survivors' (index, f32 value) in increasing mixture order;
+ *   sparse_count_dev [T]                   the number of survivors.  A frame with more survivors than sparse_capacity keeps the first
+ *                                          sparse_capacity of them; nothing is written outside its row, entries past the count keep
+ *                                          what they held.  In density-keyed mode index = topology[m][best_density(t, m)]. */
+typedef struct {
+    float*   posterior_f32_dev;
+    int      posterior_f32_ld;
+    double*  posterior_f64_dev;
+    int      posterior_f64_ld;
+    double*  log_z_dev;
+    double*  min_dev;
+    int32_t* min_index_dev;
+    int32_t* n_survivors_dev;
+    int32_t* sparse_index_dev;
+    float*   sparse_value_dev;
+    int32_t* sparse_count_dev;
+    int      sparse_capacity;
+} amx_posterior_out;
+typedef struct amx_posterior amx_posterior;
+void amx_posterior_default_cfg(amx_posterior_cfg* cfg); /* the parameters' defaults (cc:289-313); n_mixtures 0 has to be set */
+int  amx_posterior_create(amx_ctx* ctx /* nullable: configuration only */, const amx_posterior_cfg* cfg, amx_posterior** out);
+void amx_posterior_destroy(amx_posterior* h);
+/* the filter: n (mixture, prior) pairs (prior NULL: 0); a repeated mixture keeps its last prior.  On failure the old filter stays. */
+int  amx_posterior_set_filter(amx_posterior* h, int n, const int* mixture, const double* prior);
+int  amx_posterior_set_default_filter(amx_posterior* h);             /* setDefaultFilter (hh:220-222) */
+int  amx_posterior_set_single_filter(amx_posterior* h, int mixture); /* setFilter(mixtureIndex) (cc:401-403) */
+int  amx_posterior_set_disregard(amx_posterior* h, int n, const int* numbers); /* paramDisregardDensities; applies to every filter set */
+/* the filter in effect (without the disregarded mixtures), in increasing mixture order; mixture and prior nullable, [n_mixtures] */
+int  amx_posterior_filter(const amx_posterior* h, int* n, int* mixture, double* prior);
+/* Density-keyed mode: topology[m] = dens_index[mix_offsets[m] .. mix_offsets[m + 1]) (the fields of amx_gmm_model), or taken from a
+ * GMM scorer.  monotone: every density number of mixture m is below those of mixture m + 1, so the sparse form's mixture order is
+ * also increasing key order (otherwise the adapter sorts each row, as StatePosteriorFeatureScorerNode.cc:49-57 does).
+ * shared_density: a density that two mixtures list (-1: none).  With one the reference's map keeps whichever mixture its hash order
+ * visits last; density-keyed calls are refused with AMX_ERR_UNSUPPORTED naming the density. */
+int  amx_posterior_set_topology(amx_posterior* h, const uint32_t* mix_offsets /*[n_mixtures+1]*/, const uint32_t* dens_index);
+int  amx_posterior_set_topology_gmm(amx_posterior* h, const amx_gmm* gmm);
+int  amx_posterior_topology_info(const amx_posterior* h, int* monotone, long long* shared_density);
+/* One launch on the context's stream.  mode AMX_POSTERIOR_DENSITY needs best_density_dev[t * best_ld + m] (u32, the matrix
+ * amx_gmm_score_dev writes; a value past the mixture's list is read as its last density) and takes margin_mixture_dev[t]
+ * (nullable; -1: none), which the other modes refuse.  The dense outputs stay keyed by mixture in every mode. */
+int  amx_posterior_dev(amx_posterior* h, int mode, const float* scores_dev, int scores_ld, int T, const uint32_t* best_density_dev, int best_ld,
+                       const int32_t* margin_mixture_dev, const amx_posterior_out* out, unsigned long long* no_minimum);
+/* posteriorsAndMixtures(IndicesAndWeights&) (cc:258-284): frame t has the candidates [list_offsets[t], list_offsets[t + 1]) (host list) of
+ * mixture_dev[i] / prior_dev[i]; s, the minimum (first in LIST order), sum, log1p and the posteriors as above over the list only, no
+ * filter, no pruning, no margin; one posterior per entry into posterior_f64_dev[i] and/or posterior_f32_dev[i].  A mixture outside
+ * [0, n_mixtures) is never read: its score is +inf.  A list without a minimum gets posteriors 0 and is counted.
+ * The call synchronises the stream once (the host list is copied and waited for). */
+int  amx_posterior_lists_dev(amx_posterior* h, const float* scores_dev, int scores_ld, int T, const long long* list_offsets /*[T+1]*/,
+                             const int32_t* mixture_dev, const double* prior_dev, double* posterior_f64_dev, float* posterior_f32_dev,
+                             unsigned long long* no_minimum);
+/* amx_gmm_score_dev(gmm, gmm_mode, feats_dev, T) into a score matrix (and, in density-keyed mode, a best-density matrix) the handle
+ * owns, then amx_posterior_dev on it.  feats_dev is [T x amx_gmm_dimension(gmm)], dense. */
+int  amx_posterior_gmm_dev(amx_posterior* h, amx_gmm* gmm, int gmm_mode, int mode, const float* feats_dev, int T, const int32_t* margin_mixture_dev,
+                           const amx_posterior_out* out, unsigned long long* no_minimum);
+
+/* ------------------------------------------------------------------ Model combination: log-linear sum of several score matrices */
+
+/* amx_combine is one Mm::CombinedFeatureScorer: out[t][e] = ((0 + r_0) + r_1) + ... in model order (CombinedFeatureScorer.cc:42-59),
+ * r_i = scale_i * scores_i[t][table[e][i]] (ScaledContextScorer::score, ScaledFeatureScorer.hh:65-67), all f32, every product rounded
+ * before it is added (it is a virtual call's return value; both builds of the reference agree, so nothing follows amx_set_contract).
+ * table is [n_emissions x n_models]; an entry outside [0, n_mixtures[i]) is AMX_ERR_INVALID (verifyMixtureIndexTable, :85-100), as
+ * are n_models outside 1 .. AMX_COMBINE_MAX_MODELS and n_emissions < 1.  A column that is 0, 1, 2, ... is read straight, any other
+ * through the table.  out_dev may overlap none of the inputs (AMX_ERR_INVALID). */
+#define AMX_COMBINE_MAX_MODELS 8
+typedef struct amx_combine amx_combine;
+int  amx_combine_create(amx_ctx* ctx /* nullable: validation only */, int n_models, int n_emissions, const int* n_mixtures /*[n_models]*/,
+                        const int* table, const float* scale /*[n_models]*/, amx_combine** out);
+void amx_combine_destroy(amx_combine* h);
+int  amx_combine_identity_columns(const amx_combine* h, unsigned* mask); /* bit i: column i is read straight */
+int  amx_combine_dev(amx_combine* h, int T, const float* const* scores_dev /*[n_models]*/, const int* ld /*[n_models]*/, float* out_dev, int out_ld);
 
 /* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
 

@@ -11,6 +11,8 @@ same reference interfaces for tests and benchmarks:
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
   ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
   BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
+  StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
+  CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
   FileArchive          Core::FileArchive + Flow cache entries (feature caches between jobs; host IO)
 """
@@ -26,7 +28,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1257,6 +1259,175 @@ class BayesClassifier:
         if len(bad):
             raise ValueError("BayesClassifier.warping_factors: segment %d has label %d, outside the %d factors" % (bad[0], labels[bad[0]], len(factors)))
         return factors[labels]
+
+
+class StatePosteriorScorer:
+    """Mm::StatePosteriorFeatureScorer with viterbi = true on a [frames x mixtures] score matrix that is on the device.  Keyword names are
+    the fields of amx_posterior_cfg (= the reference's parameters: scale, pruning_threshold, margin, viterbi); ctx None gives a handle
+    for configuration only.  Buffers are device tensors (or anything with data_ptr()); every output is optional."""
+
+    MODES = {"mixture": _lib.AMX_POSTERIOR_MIXTURE, "likelihood": _lib.AMX_POSTERIOR_LIKELIHOOD, "density": _lib.AMX_POSTERIOR_DENSITY}
+    OUTPUTS = ("posterior_f32_dev", "posterior_f64_dev", "log_z_dev", "min_dev", "min_index_dev", "n_survivors_dev", "sparse_index_dev",
+               "sparse_value_dev", "sparse_count_dev")
+
+    def __init__(self, ctx, n_mixtures, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.PosteriorCfg()
+        self.L.amx_posterior_default_cfg(C.byref(cfg))
+        cfg.n_mixtures = int(n_mixtures)
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("StatePosteriorScorer: unknown parameter %r" % k)
+            setattr(cfg, k, v if isinstance(getattr(cfg, k), float) else int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_posterior_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.n_mixtures = cfg.n_mixtures
+        self.cfg = cfg
+
+    def close(self):
+        if self.h:
+            self.L.amx_posterior_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_filter(self, mixture, prior=None):
+        """the filter: mixtures and their priors (None: 0)"""
+        m = np.ascontiguousarray(mixture, dtype=np.int32)
+        p = None if prior is None else np.ascontiguousarray(prior, dtype=np.float64)
+        if p is not None and len(p) != len(m):
+            raise ValueError("StatePosteriorScorer.set_filter: %d priors for %d mixtures" % (len(p), len(m)))
+        _lib.check(self.L.amx_posterior_set_filter(self.h, len(m), m.ctypes.data, _ptr(p)))
+
+    def set_default_filter(self):
+        _lib.check(self.L.amx_posterior_set_default_filter(self.h))
+
+    def set_single_filter(self, mixture):
+        _lib.check(self.L.amx_posterior_set_single_filter(self.h, int(mixture)))
+
+    def set_disregard(self, numbers):
+        """disregard-densities: erased from the filter as MIXTURE indices, as the reference does"""
+        d = np.ascontiguousarray(numbers, dtype=np.int32)
+        _lib.check(self.L.amx_posterior_set_disregard(self.h, len(d), d.ctypes.data if len(d) else None))
+
+    def filter(self):
+        """(mixtures, priors) of the filter in effect, in increasing mixture order"""
+        n = C.c_int()
+        m, p = np.zeros(self.n_mixtures, np.int32), np.zeros(self.n_mixtures, np.float64)
+        _lib.check(self.L.amx_posterior_filter(self.h, C.byref(n), m.ctypes.data, p.ctypes.data))
+        return m[:n.value].copy(), p[:n.value].copy()
+
+    def set_topology(self, mix_offsets=None, dens_index=None, gmm=None):
+        """density-keyed mode: the CSR topology of the mixture set, or that of a GmmFeatureScorer"""
+        if gmm is not None:
+            _lib.check(self.L.amx_posterior_set_topology_gmm(self.h, gmm.h))
+            return
+        off = np.ascontiguousarray(mix_offsets, dtype=np.uint32)
+        dens = np.ascontiguousarray(dens_index, dtype=np.uint32)
+        if len(off) != self.n_mixtures + 1 or (len(off) and len(dens) != int(off[-1])):
+            raise ValueError("StatePosteriorScorer.set_topology: mix_offsets must hold n_mixtures + 1 offsets and dens_index mix_offsets[-1] numbers")
+        _lib.check(self.L.amx_posterior_set_topology(self.h, off.ctypes.data, dens.ctypes.data))
+
+    def topology_info(self):
+        """(monotone, shared density or -1)"""
+        mono, shared = C.c_int(), C.c_longlong()
+        _lib.check(self.L.amx_posterior_topology_info(self.h, C.byref(mono), C.byref(shared)))
+        return bool(mono.value), int(shared.value)
+
+    def _out(self, kw):
+        out = _lib.PosteriorOut()
+        for k, v in kw.items():
+            if k not in self.OUTPUTS and k not in ("posterior_f32_ld", "posterior_f64_ld", "sparse_capacity"):
+                raise TypeError("StatePosteriorScorer: unknown output %r" % k)
+            setattr(out, k, _ptr(v) if k in self.OUTPUTS else int(v))
+        if not out.posterior_f32_ld:
+            out.posterior_f32_ld = self.n_mixtures
+        if not out.posterior_f64_ld:
+            out.posterior_f64_ld = self.n_mixtures
+        return out
+
+    def posteriors(self, scores_dev, scores_ld, T, mode="mixture", best_density_dev=None, best_ld=None, margin_mixture_dev=None, count_no_minimum=True,
+                   **outputs):
+        """amx_posterior_dev: outputs are the fields of amx_posterior_out by name; returns the number of frames without a minimum, or None
+        without the synchronisation when count_no_minimum is False"""
+        out = self._out(outputs)
+        nm = C.c_ulonglong()
+        _lib.check(self.L.amx_posterior_dev(self.h, self.MODES[mode], _ptr(scores_dev), int(scores_ld), int(T), _ptr(best_density_dev),
+                                            int(best_ld if best_ld is not None else self.n_mixtures), _ptr(margin_mixture_dev), C.byref(out),
+                                            C.addressof(nm) if count_no_minimum else None))
+        return int(nm.value) if count_no_minimum else None
+
+    def list_posteriors(self, scores_dev, scores_ld, list_offsets, mixture_dev, prior_dev, posterior_f64_dev=None, posterior_f32_dev=None,
+                        count_no_minimum=True):
+        """amx_posterior_lists_dev: frame t has the candidates [list_offsets[t], list_offsets[t + 1]) of mixture_dev (int32) / prior_dev (f64)"""
+        off = np.ascontiguousarray(list_offsets, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError("StatePosteriorScorer.list_posteriors: list_offsets must hold T + 1 offsets")
+        nm = C.c_ulonglong()
+        _lib.check(self.L.amx_posterior_lists_dev(self.h, _ptr(scores_dev), int(scores_ld), len(off) - 1, off.ctypes.data, _ptr(mixture_dev), _ptr(prior_dev),
+                                                  _ptr(posterior_f64_dev), _ptr(posterior_f32_dev), C.addressof(nm) if count_no_minimum else None))
+        return int(nm.value) if count_no_minimum else None
+
+    def posteriors_gmm(self, gmm, feats_dev, T, mode="mixture", margin_mixture_dev=None, count_no_minimum=True, **outputs):
+        """gmm (a GmmFeatureScorer of the same context) scores feats_dev [T, dim] into matrices the handle owns, then posteriors"""
+        out = self._out(outputs)
+        nm = C.c_ulonglong()
+        _lib.check(self.L.amx_posterior_gmm_dev(self.h, gmm.h, gmm.mode, self.MODES[mode], _ptr(feats_dev), int(T), _ptr(margin_mixture_dev), C.byref(out),
+                                                C.addressof(nm) if count_no_minimum else None))
+        return int(nm.value) if count_no_minimum else None
+
+    @staticmethod
+    def sort_sparse(index, value, count):
+        """the adapter's sort for a topology that is not monotone (StatePosteriorFeatureScorerNode.cc:49-57): host arrays [T, capacity] and
+        [T] -> per frame (indices, values) in increasing index order"""
+        rows = []
+        for t in range(len(count)):
+            k = min(int(count[t]), index.shape[1])
+            order = np.argsort(index[t, :k], kind="stable")
+            rows.append((index[t, :k][order], value[t, :k][order]))
+        return rows
+
+
+class CombinedScorer:
+    """Mm::CombinedFeatureScorer: out[t][e] = sum over the models, in model order, of scale[i] * scores[i][t][table[e][i]] in f32.
+    table is [n_emissions, n_models]; n_mixtures[i] is the width of model i's matrix.  ctx None validates only."""
+
+    def __init__(self, ctx, n_mixtures, table, scale):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        nm = np.ascontiguousarray(n_mixtures, dtype=np.int32)
+        tb = np.ascontiguousarray(table, dtype=np.int32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32)
+        if tb.ndim != 2 or tb.shape[1] != len(nm) or len(sc) != len(nm):
+            raise ValueError("CombinedScorer: table must be [n_emissions, n_models] with one width and one scale per model")
+        h = C.c_void_p()
+        _lib.check(self.L.amx_combine_create(ctx.h if ctx is not None else None, len(nm), tb.shape[0], nm.ctypes.data, tb.ctypes.data, sc.ctypes.data,
+                                             C.byref(h)))
+        self.h = h
+        self.n_models, self.n_emissions = len(nm), tb.shape[0]
+
+    def close(self):
+        if self.h:
+            self.L.amx_combine_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def identity_columns(self):
+        """per model: whether its table column is 0, 1, 2, ... (read straight)"""
+        m = C.c_uint()
+        _lib.check(self.L.amx_combine_identity_columns(self.h, C.byref(m)))
+        return [bool((m.value >> i) & 1) for i in range(self.n_models)]
+
+    def combine(self, T, scores_dev, ld, out_dev, out_ld):
+        """amx_combine_dev: scores_dev is a list of the models' device matrices, ld their leading dimensions"""
+        if len(scores_dev) != self.n_models or len(ld) != self.n_models:
+            raise ValueError("CombinedScorer.combine: %d models" % self.n_models)
+        ptrs = (C.c_void_p * self.n_models)(*[_ptr(s) for s in scores_dev])
+        lds = np.ascontiguousarray(ld, dtype=np.int32)
+        _lib.check(self.L.amx_combine_dev(self.h, int(T), ptrs, lds.ctypes.data, _ptr(out_dev), int(out_ld)))
 
 
 def _quanteq_cfg(L, kw, who):

@@ -77,6 +77,20 @@ class BayesCfg(C.Structure):
                 ("window_right", C.c_int), ("single_frame", C.c_int)]
 
 
+class PosteriorCfg(C.Structure):
+    _fields_ = [("n_mixtures", C.c_int), ("scale", C.c_double), ("pruning_threshold", C.c_double), ("margin", C.c_double), ("viterbi", C.c_int)]
+
+
+class PosteriorOut(C.Structure):
+    _fields_ = [("posterior_f32_dev", C.c_void_p), ("posterior_f32_ld", C.c_int), ("posterior_f64_dev", C.c_void_p), ("posterior_f64_ld", C.c_int),
+                ("log_z_dev", C.c_void_p), ("min_dev", C.c_void_p), ("min_index_dev", C.c_void_p), ("n_survivors_dev", C.c_void_p),
+                ("sparse_index_dev", C.c_void_p), ("sparse_value_dev", C.c_void_p), ("sparse_count_dev", C.c_void_p), ("sparse_capacity", C.c_int)]
+
+
+AMX_POSTERIOR_MIXTURE, AMX_POSTERIOR_LIKELIHOOD, AMX_POSTERIOR_DENSITY = 0, 1, 2
+AMX_COMBINE_MAX_MODELS = 8
+
+
 class QuanteqCfg(C.Structure):
     _fields_ = [("quantiles", C.c_int), ("combination", C.c_int), ("estimate", C.c_int), ("mean", C.c_int), ("variance", C.c_int),
                 ("number_of_quantiles", C.c_int), ("overestimation_factor", C.c_float), ("delta_alpha", C.c_float), ("delta_gamma", C.c_float),
@@ -234,6 +248,25 @@ SIGNATURES = {
     "amx_bayes_classify_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "amx_bayes_scores_dev": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "amx_bayes_classify_gmm_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "amx_gmm_topology": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P]),
+    "amx_posterior_default_cfg": (None, [C.POINTER(PosteriorCfg)]),
+    "amx_posterior_create": (C.c_int, [_P, C.POINTER(PosteriorCfg), C.POINTER(_P)]),
+    "amx_posterior_destroy": (None, [_P]),
+    "amx_posterior_set_filter": (C.c_int, [_P, C.c_int, _P, _P]),
+    "amx_posterior_set_default_filter": (C.c_int, [_P]),
+    "amx_posterior_set_single_filter": (C.c_int, [_P, C.c_int]),
+    "amx_posterior_set_disregard": (C.c_int, [_P, C.c_int, _P]),
+    "amx_posterior_filter": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P]),
+    "amx_posterior_set_topology": (C.c_int, [_P, _P, _P]),
+    "amx_posterior_set_topology_gmm": (C.c_int, [_P, _P]),
+    "amx_posterior_topology_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "amx_posterior_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(PosteriorOut), _P]),
+    "amx_posterior_lists_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "amx_posterior_gmm_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(PosteriorOut), _P]),
+    "amx_combine_create": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(_P)]),
+    "amx_combine_destroy": (None, [_P]),
+    "amx_combine_identity_columns": (C.c_int, [_P, C.POINTER(C.c_uint)]),
+    "amx_combine_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
     "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
     "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
     "amx_quanteq_destroy": (None, [_P]),

@@ -233,6 +233,23 @@ __device__ __forceinline__ void nt_store(V v, V* p) {
 #endif
 }
 
+// whether the views in[T x in_w] (leading dimension in_ld) and out[T x out_w] share an element
+inline bool views_alias(const float* in, int in_ld, int in_w, const float* out, int out_ld, int out_w, long long T) {
+    if (T <= 0)
+        return false;
+    const float* in_end  = in + (T - 1) * (long long)in_ld + in_w;
+    const float* out_end = out + (T - 1) * (long long)out_ld + out_w;
+    if (in_end <= out || out_end <= in)
+        return false;
+    if (in_ld == out_ld) {
+        const long long ld = in_ld, delta = out - in;
+        const long long c  = ((delta % ld) + ld) % ld;  // column offset of `out` relative to `in`
+        if (c >= in_w && c + out_w <= ld)
+            return false;  // disjoint column ranges of the same matrix (also with a row shift)
+    }
+    return true;
+}
+
 inline int ceil_div(long a, long b) {
     return (int)((a + b - 1) / b);
 }

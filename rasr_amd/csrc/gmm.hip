@@ -2302,6 +2302,16 @@ int amx_gmm_dimension(const amx_gmm* h) {
     return h ? h->dim : 0;
 }
 
+int amx_gmm_topology(const amx_gmm* h, int* n_entries, uint32_t* mix_offsets, uint32_t* dens_index) {
+    AMX_REQUIRE(h && n_entries, AMX_ERR_INVALID, "amx_gmm_topology: NULL argument");
+    *n_entries = (int)h->h_k_dens.size();
+    if (mix_offsets)
+        std::copy(h->mix_off.begin(), h->mix_off.end(), mix_offsets);
+    if (dens_index)
+        std::copy(h->h_k_dens.begin(), h->h_k_dens.end(), dens_index);
+    return AMX_OK;
+}
+
 int amx_gmm_tables(const amx_gmm* h, float* m2lw, float* isr, float* lognorm) {
     AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_gmm_tables: NULL handle");
     if (m2lw)
