@@ -888,6 +888,84 @@ void amx_combine_destroy(amx_combine* h);
 int  amx_combine_identity_columns(const amx_combine* h, unsigned* mask); /* bit i: column i is read straight */
 int  amx_combine_dev(amx_combine* h, int T, const float* const* scores_dev /*[n_models]*/, const int* ld /*[n_models]*/, float* out_dev, int out_ld);
 
+/* ------------------------------------------------------------------ Viterbi alignment on the score matrix: search, traceback, labels */
+
+/* amx_align is one Search::Aligner in Viterbi mode (Search/Aligner.cc:41-470, 530-651; what Speech::AlignmentNode runs): the
+ * time-synchronous search over an epsilon-free acceptor whose arcs consume one frame each, on scores_dev[t * scores_ld + e] (f32, as any
+ * scorer of this library leaves it).  Only f32 additions and comparisons: nothing here depends on amx_set_contract.
+ *   expansion      per frame, per hypothesis in list order, per arc in arc order: sco = (score + weight) + emission (:234);
+ *                  emission = score_scale * scores[t][e], rounded once when score_scale != 1 (ScaledContextScorer::score)
+ *   recombination  the first candidate of a target creates its hypothesis and fixes its place in the frame's list; a later one replaces
+ *                  score, trace and label when old >= new (:144-167): the LAST of the candidates with the minimal score wins
+ *   pruning        survivors have score <= minimumScore() + threshold, order kept (:254-318, :594-601)
+ *   iteration      for (t = min; t <= max; t *= factor), restarting per pass (:603-630); a pass ends the loop when a final state is
+ *                  reached, the f64 average of the per-frame survivor counts is >= min_average_number_of_states and either
+ *                  increase_until_no_score_difference is 0 or t > min and Core::isAlmostEqual(score, previous score); factor <= 1: one pass.
+ *                  A pass that pruned nothing gives what every later pass gives: those are counted, not run.
+ *   result         the best final hypothesis by strict < over final weight + score in list order (the FIRST wins a tie, :408-419); per
+ *                  frame the arc's label and score[hyp] - score[trace] (:438); no final state reached: score FLT_MAX, no alignment.
+ * Limits of the search kernel (one workgroup per segment, the segment's states in LDS): at most AMX_ALIGN_MAX_STATES states and
+ * AMX_ALIGN_MAX_EMISSIONS distinct emission indices per segment, at most AMX_ALIGN_MAX_OUT_ARCS arcs out of a state. */
+#define AMX_ALIGN_MAX_STATES 2048
+#define AMX_ALIGN_MAX_EMISSIONS 4096
+#define AMX_ALIGN_MAX_OUT_ARCS 64
+#define AMX_ALIGN_MAX_PASSES 4096
+#define AMX_ALIGN_VITERBI 0
+#define AMX_ALIGN_BAUM_WELCH 1
+typedef struct {
+    float  min_acoustic_pruning;                /* 50 */
+    float  max_acoustic_pruning;                /* FLT_MAX */
+    float  increment_factor;                    /* 2 */
+    double min_average_number_of_states;        /* 0 */
+    int    increase_until_no_score_difference;  /* 1 */
+    int    n_best_pruning;                      /* INT_MAX; anything below is refused */
+    int    mode;                                /* AMX_ALIGN_VITERBI; AMX_ALIGN_BAUM_WELCH is refused */
+    float  score_scale;                         /* 1: the scale of the acoustic model's scaled feature scorer */
+} amx_align_cfg;
+/* The graphs of a batch, on the host.  States of segment s are [state_offsets[s], state_offsets[s + 1]); arc_target and initial_state are
+ * local to the segment.  Arcs of state i (global) are [arc_offsets[i], arc_offsets[i + 1]) in the reference's arc order. */
+typedef struct {
+    const int*           state_offsets;  /* [n_seg + 1] */
+    const int*           initial_state;  /* [n_seg] */
+    const unsigned char* is_final;       /* [states] */
+    const float*         final_weight;   /* [states], read where is_final */
+    const int*           arc_offsets;    /* [states + 1] */
+    const int*           arc_target;     /* [arcs] */
+    const int*           arc_emission;   /* [arcs] column of the score matrix */
+    const int*           arc_label;      /* [arcs] what comes out: the allophone-state id */
+    const float*         arc_weight;     /* [arcs] */
+} amx_align_graphs;
+typedef struct {
+    float              score;           /* alignmentScore(); FLT_MAX when no final state was reached */
+    int                reached_final;   /* 0 also for a segment that met a NaN */
+    int                n_iterations;    /* passes as the reference counts them, the ones not run included */
+    float              last_threshold;  /* the threshold of the last of them */
+    double             average_states;  /* average number of state hypotheses after pruning, of the last pass (NaN for 0 frames) */
+    unsigned long long state_sum;       /* its per-frame survivor counts added up */
+} amx_align_result;
+typedef struct amx_align amx_align;
+void amx_align_default_cfg(amx_align_cfg* cfg); /* the reference's defaults (:473-528) */
+/* Refused with AMX_ERR_UNSUPPORTED naming the parameter: mode = baum-welch; n_best_pruning < INT_MAX; an increment_factor that takes
+ * more than AMX_ALIGN_MAX_PASSES steps from min to max.  With AMX_ERR_INVALID: min > max, or factor <= 1 with min != max (:543-550); a
+ * threshold or scale that is NaN; min <= 0. */
+int  amx_align_create(amx_ctx* ctx /* nullable: validation only */, const amx_align_cfg* cfg, amx_align** out);
+void amx_align_destroy(amx_align* h);
+/* Aligner::feed(vector) + getAlignmentFsa for n_seg segments in one launch sequence, one readback at the end.  Segment s = frames
+ * [frame_offsets[s], frame_offsets[s + 1]) (host list, absolute rows) of scores_dev, label_dev, emission_dev and arc_score_dev.
+ *   label_dev[t]      the label of the arc aligned to frame t; emission_dev[t] its emission index (what amx_gmm_accumulate_dev,
+ *                     amx_scatter_accumulate_dev and margin_mixture_dev take); both -1 in a segment that reached no final state
+ *   arc_score_dev[t]  nullable: score[hyp] - score[trace] of that arc, 0 in such a segment
+ *   result[s]         host
+ *   counters          nullable, host: [0] segments that met a NaN, [1] passes run on the device, [2] passes counted without running
+ * Checked before anything is launched.  AMX_ERR_INVALID naming segment and index: an arc target, emission index or initial state out
+ * of range, a NaN arc or final weight, offsets that decrease.  AMX_ERR_UNSUPPORTED: a segment with more states, distinct emissions or
+ * arcs out of a state than the limits above.
+ * Where the reference is undefined: a NaN candidate score met by the search (a NaN emission, or inf - inf) would make the outcome depend
+ * on evaluation order; the segment is reported as not reached (n_iterations and last_threshold: the pass that met it) and counted. */
+int  amx_align_viterbi_dev(amx_align* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const amx_align_graphs* graphs,
+                           const float* scores_dev, int scores_ld, int n_columns, int32_t* label_dev, int32_t* emission_dev,
+                           float* arc_score_dev, amx_align_result* result /*[n_seg]*/, unsigned long long counters[3]);
+
 /* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
 
 /* amx_quanteq is one Signal::QuantileEqualization (Signal/QuantileEqualization.{hh,cc}) in SEGMENT MODE (length = right = INT_MAX): the

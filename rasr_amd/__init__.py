@@ -11,6 +11,7 @@ same reference interfaces for tests and benchmarks:
   NnBatchFeatureScorer Nn::BatchFeatureScorer (nn-batch-feature-scorer)
   ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
   BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
+  ViterbiAligner       Search::Aligner in Viterbi mode (Speech::AlignmentNode): search, traceback and labels on the score matrix
   StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
   CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
@@ -28,7 +29,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1445,6 +1446,88 @@ def _offsets(frame_offsets, who):
     if off.ndim != 1 or len(off) < 1:
         raise ValueError("%s: frame_offsets must hold n_seg + 1 offsets" % who)
     return off
+
+
+class ViterbiAligner:
+    """Search::Aligner in Viterbi mode (what Speech::AlignmentNode runs) for a batch of segments whose [frames x emissions] score matrix
+    is on the device.  Keyword names are the fields of amx_align_cfg (= the aligner's parameters); ctx None gives a handle that only
+    checks configurations and graphs."""
+
+    FLOATS = ("min_acoustic_pruning", "max_acoustic_pruning", "increment_factor", "min_average_number_of_states", "score_scale")
+
+    def __init__(self, ctx, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.AlignCfg()
+        self.L.amx_align_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("ViterbiAligner: unknown parameter %r" % k)
+            setattr(cfg, k, float(v) if k in self.FLOATS else int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_align_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_align_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def graphs(segments):
+        """the host tables of amx_align_graphs from one dict per segment: n_states, initial, final (bool per state), final_weight (per
+        state) and arcs, a list per source state of (target, emission, label, weight) in the reference's arc order.  Returns a dict of
+        numpy arrays named like the struct's fields."""
+        state_offsets, arc_offsets = [0], [0]
+        initial, is_final, final_weight, target, emission, label, weight = [], [], [], [], [], [], []
+        for g in segments:
+            n = int(g["n_states"])
+            if len(g["arcs"]) != n or len(g["final"]) != n or len(g["final_weight"]) != n:
+                raise ValueError("ViterbiAligner.graphs: a segment's tables do not have n_states entries")
+            state_offsets.append(state_offsets[-1] + n)
+            initial.append(int(g["initial"]))
+            is_final.extend(bool(f) for f in g["final"])
+            final_weight.extend(float(w) for w in g["final_weight"])
+            for arcs in g["arcs"]:
+                for t, e, l, w in arcs:
+                    target.append(int(t)), emission.append(int(e)), label.append(int(l)), weight.append(float(w))
+                arc_offsets.append(len(target))
+        return dict(state_offsets=np.array(state_offsets, np.int32), initial_state=np.array(initial, np.int32), is_final=np.array(is_final, np.uint8),
+                    final_weight=np.array(final_weight, np.float32), arc_offsets=np.array(arc_offsets, np.int32), arc_target=np.array(target, np.int32),
+                    arc_emission=np.array(emission, np.int32), arc_label=np.array(label, np.int32), arc_weight=np.array(weight, np.float32))
+
+    def align(self, frame_offsets, graphs, scores_dev, scores_ld, n_columns=None, label_dev=None, emission_dev=None, arc_score_dev=None):
+        """segment s = rows [frame_offsets[s], frame_offsets[s + 1]) of scores_dev.  graphs: what graphs() returns, or the list it takes.
+        label_dev, emission_dev (int32) and arc_score_dev (f32) hold one entry per row of the matrix up to frame_offsets[-1]; buffers
+        that are not given are created (torch, on the matrix's device).  Returns (label_dev, emission_dev, arc_score_dev, results,
+        counters): results is a list of dicts per segment, counters (segments that met a NaN, passes run, passes counted)."""
+        off = _offsets(frame_offsets, "ViterbiAligner.align")
+        if not isinstance(graphs, dict):
+            graphs = self.graphs(graphs)
+        n_seg = len(off) - 1
+        if len(graphs["state_offsets"]) != n_seg + 1:
+            raise ValueError("ViterbiAligner.align: %d segments but graphs of %d" % (n_seg, len(graphs["state_offsets"]) - 1))
+        keep = {k: np.ascontiguousarray(v) for k, v in graphs.items()}
+        g = _lib.AlignGraphs(**{k: v.ctypes.data for k, v in keep.items()})
+        if self.ctx is not None and int(off[-1]) > 0:
+            import torch
+            if label_dev is None:
+                label_dev = torch.empty(int(off[-1]), dtype=torch.int32, device=scores_dev.device)
+            if emission_dev is None:
+                emission_dev = torch.empty(int(off[-1]), dtype=torch.int32, device=scores_dev.device)
+            if arc_score_dev is None:
+                arc_score_dev = torch.empty(int(off[-1]), dtype=torch.float32, device=scores_dev.device)
+        res = (_lib.AlignResult * max(n_seg, 1))()
+        counters = np.zeros(3, np.uint64)
+        _lib.check(self.L.amx_align_viterbi_dev(self.h, n_seg, off.ctypes.data, C.byref(g), _ptr(scores_dev), int(scores_ld),
+                                                int(n_columns if n_columns is not None else scores_ld), _ptr(label_dev), _ptr(emission_dev),
+                                                _ptr(arc_score_dev), C.cast(res, C.c_void_p), counters.ctypes.data))
+        results = [dict(score=np.float32(r.score), reached=bool(r.reached_final), n_iterations=int(r.n_iterations),
+                        last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum))
+                   for r in res[:n_seg]]
+        return label_dev, emission_dev, arc_score_dev, results, tuple(int(c) for c in counters)
 
 
 def read_quantiles(path, dim, number_of_quantiles=4, pool=True):

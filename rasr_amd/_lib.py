@@ -87,6 +87,25 @@ class PosteriorOut(C.Structure):
                 ("sparse_index_dev", C.c_void_p), ("sparse_value_dev", C.c_void_p), ("sparse_count_dev", C.c_void_p), ("sparse_capacity", C.c_int)]
 
 
+class AlignCfg(C.Structure):
+    _fields_ = [("min_acoustic_pruning", C.c_float), ("max_acoustic_pruning", C.c_float), ("increment_factor", C.c_float),
+                ("min_average_number_of_states", C.c_double), ("increase_until_no_score_difference", C.c_int), ("n_best_pruning", C.c_int),
+                ("mode", C.c_int), ("score_scale", C.c_float)]
+
+
+class AlignGraphs(C.Structure):
+    _fields_ = [("state_offsets", C.c_void_p), ("initial_state", C.c_void_p), ("is_final", C.c_void_p), ("final_weight", C.c_void_p),
+                ("arc_offsets", C.c_void_p), ("arc_target", C.c_void_p), ("arc_emission", C.c_void_p), ("arc_label", C.c_void_p),
+                ("arc_weight", C.c_void_p)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("reached_final", C.c_int), ("n_iterations", C.c_int), ("last_threshold", C.c_float),
+                ("average_states", C.c_double), ("state_sum", C.c_ulonglong)]
+
+
+AMX_ALIGN_MAX_STATES, AMX_ALIGN_MAX_EMISSIONS, AMX_ALIGN_MAX_OUT_ARCS, AMX_ALIGN_MAX_PASSES = 2048, 4096, 64, 4096
+AMX_ALIGN_VITERBI, AMX_ALIGN_BAUM_WELCH = 0, 1
 AMX_POSTERIOR_MIXTURE, AMX_POSTERIOR_LIKELIHOOD, AMX_POSTERIOR_DENSITY = 0, 1, 2
 AMX_COMBINE_MAX_MODELS = 8
 
@@ -267,6 +286,10 @@ SIGNATURES = {
     "amx_combine_destroy": (None, [_P]),
     "amx_combine_identity_columns": (C.c_int, [_P, C.POINTER(C.c_uint)]),
     "amx_combine_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
+    "amx_align_default_cfg": (None, [C.POINTER(AlignCfg)]),
+    "amx_align_create": (C.c_int, [_P, C.POINTER(AlignCfg), C.POINTER(_P)]),
+    "amx_align_destroy": (None, [_P]),
+    "amx_align_viterbi_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(AlignGraphs), _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
     "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
     "amx_quanteq_destroy": (None, [_P]),
