@@ -919,7 +919,7 @@ typedef struct {
     double min_average_number_of_states;        /* 0 */
     int    increase_until_no_score_difference;  /* 1 */
     int    n_best_pruning;                      /* INT_MAX; anything below is refused */
-    int    mode;                                /* AMX_ALIGN_VITERBI; AMX_ALIGN_BAUM_WELCH is refused */
+    int    mode;                                /* AMX_ALIGN_VITERBI; AMX_ALIGN_BAUM_WELCH is refused here: amx_bw_create has it */
     float  score_scale;                         /* 1: the scale of the acoustic model's scaled feature scorer */
 } amx_align_cfg;
 /* The graphs of a batch, on the host.  States of segment s are [state_offsets[s], state_offsets[s + 1]); arc_target and initial_state are
@@ -945,7 +945,7 @@ typedef struct {
 } amx_align_result;
 typedef struct amx_align amx_align;
 void amx_align_default_cfg(amx_align_cfg* cfg); /* the reference's defaults (:473-528) */
-/* Refused with AMX_ERR_UNSUPPORTED naming the parameter: mode = baum-welch; n_best_pruning < INT_MAX; an increment_factor that takes
+/* Refused with AMX_ERR_UNSUPPORTED naming the parameter: mode = baum-welch (a handle of its own, amx_bw below); n_best_pruning < INT_MAX; an increment_factor that takes
  * more than AMX_ALIGN_MAX_PASSES steps from min to max.  With AMX_ERR_INVALID: min > max, or factor <= 1 with min != max (:543-550); a
  * threshold or scale that is NaN; min <= 0. */
 int  amx_align_create(amx_ctx* ctx /* nullable: validation only */, const amx_align_cfg* cfg, amx_align** out);
@@ -965,6 +965,75 @@ void amx_align_destroy(amx_align* h);
 int  amx_align_viterbi_dev(amx_align* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const amx_align_graphs* graphs,
                            const float* scores_dev, int scores_ld, int n_columns, int32_t* label_dev, int32_t* emission_dev,
                            float* arc_score_dev, amx_align_result* result /*[n_seg]*/, unsigned long long counters[3]);
+
+/* ------------------------------------------------------------------ Baum-Welch alignment on the score matrix: forward-backward, item lists */
+
+/* amx_bw is one Search::Aligner in mode baum-welch (Search/Aligner.cc:169-196, 215-318, 385-405, 447-461, 594-630, 653-735, 766-781;
+ * Fsa/Sssp.cc:67-202; Speech/Alignment.cc:426-578): the soft alignment of a batch of segments on the score matrix amx_align_viterbi_dev
+ * reads.  Per frame it leaves a list of (allophone-state label, emission index, posterior weight), what Aligner::getAlignment returns.
+ *   search         expansion, pruning rule and loop of thresholds are Viterbi's; a target's candidates score + (weight + emission) are
+ *                  combined in the log semiring.  Here: the f64 log-sum min - log1p(sum exp(min - c)) over the state's incoming arcs in
+ *                  the static by-target order, rounded to f32 once per state and frame (the reference collects in f32, pairwise, in list
+ *                  order).  These f32 scores decide pruning, iterations and the reported score (finalStatePotential) only.
+ *   posteriors     over the survivors of the last pass: forward and backward potentials in f64 (posterior64), arc weights
+ *                  f32 (weight + emission); an arc's -log p = fw[source] + w + bw[target] - total
+ *   items          exp(-.) summed per (frame, label) in a fixed order, divided by the frame's sum, rounded to f32; weights > 0 are kept.
+ *                  Within a frame: decreasing weight, then increasing label.
+ * A label must have one emission index within a segment (an acoustic model's emissionIndex() is a function of the label).
+ * Not built: min-weight pruning, partial sums, extractAlignment's gamma, alignment files, word lattices, the statistics channel. */
+#define AMX_BW_MAX_LABELS 4096 /* distinct labels per segment */
+typedef struct {
+    float  min_acoustic_pruning;                /* 50 */
+    float  max_acoustic_pruning;                /* FLT_MAX */
+    float  increment_factor;                    /* 2 */
+    double min_average_number_of_states;        /* 0 */
+    int    increase_until_no_score_difference;  /* 1 */
+    int    n_best_pruning;                      /* INT_MAX; anything below is refused */
+    float  score_scale;                         /* 1 */
+    float  min_weight;                          /* 0; above FLT_MIN is refused (prunePosterior's second stage) */
+    int    use_partial_sums;                    /* 0; 1 is refused */
+} amx_bw_cfg;
+typedef struct {
+    float              score;           /* alignmentScore(): the f32 finalStatePotential of the last pass; FLT_MAX when no final state was reached */
+    int                reached_final;   /* 0 also for a segment that met a NaN */
+    int                n_iterations;
+    float              last_threshold;
+    double             average_states;
+    unsigned long long state_sum;
+    long long          n_items;         /* items of the segment */
+    double             log_total;       /* bw[initial], -log of the trellis' total flow in f64; DBL_MAX where no final state was reached.  A reached
+                                         * segment without frames reports its initial state's final weight and has no items */
+} amx_bw_result;
+typedef struct amx_bw amx_bw;
+void amx_bw_default_cfg(amx_bw_cfg* cfg);
+/* The search parameters are checked as amx_align_create checks them.  AMX_ERR_UNSUPPORTED naming the parameter: use_partial_sums = 1,
+ * min_weight > FLT_MIN, n_best_pruning < INT_MAX, too many passes.  AMX_ERR_INVALID: a min_weight that is negative or not a number. */
+int  amx_bw_create(amx_ctx* ctx /* nullable: validation only */, const amx_bw_cfg* cfg, amx_bw** out);
+void amx_bw_destroy(amx_bw* h);
+/* Search, posteriors and item combination for n_seg segments; one readback at the end (a second one only when the handle's item store
+ * has to grow).  Segments, graphs, matrix and the checks before anything is launched are amx_align_viterbi_dev's; beyond them
+ * AMX_ERR_UNSUPPORTED for a segment with more than AMX_BW_MAX_LABELS distinct labels and AMX_ERR_INVALID for a label with two emission
+ * indices in one segment.
+ *   item_offsets_dev  int64 [frame_offsets[n_seg] + 1], device: the items of matrix row t are [item_offsets_dev[t], item_offsets_dev[t + 1])
+ *                     of the handle's item store (rows below frame_offsets[0] have none)
+ *   result[s]         host
+ *   counters          nullable, host: as amx_align_viterbi_dev
+ * n_seg = 0: nothing is launched and nothing is written, item_offsets_dev included; amx_bw_n_items is 0.
+ * Added rules: a NaN candidate, or inf - inf in a log-sum, ends the segment, which is reported as not reached and counted; a segment that
+ * reaches no final state has no items and score FLT_MAX; so has one without frames. */
+int  amx_bw_align_dev(amx_bw* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const amx_align_graphs* graphs, const float* scores_dev,
+                      int scores_ld, int n_columns, int64_t* item_offsets_dev, amx_bw_result* result /*[n_seg]*/, unsigned long long counters[3]);
+/* The items of the last amx_bw_align_dev call, copied out of the handle's store (device to device, on the context's stream): frame
+ * (the matrix row), label, emission index, weight; weight_f64_dev (nullable): the same values widened, what
+ * amx_gmm_accumulate_weighted_dev takes as weight_dev.  Ordered by frame, then decreasing weight, then label.  A capacity below the
+ * number of items is AMX_ERR_INVALID naming the needed count. */
+long long amx_bw_n_items(const amx_bw* h);
+int  amx_bw_items_dev(amx_bw* h, long long capacity, int32_t* frame_dev, int32_t* label_dev, int32_t* emission_dev, float* weight_dev,
+                      double* weight_f64_dev);
+/* dst[i * dst_ld + d] = src[row_dev[i] * src_ld + d], d < dim, i < n: the feature rows of the items, so that
+ * amx_gmm_accumulate_weighted_dev(..., T = n_items, mixture_dev = emission, weight_dev = weight_f64) takes them unchanged.  The row
+ * numbers are on the device and are not checked. */
+int  amx_gather_rows_dev(amx_ctx* ctx, const float* src_dev, int src_ld, int dim, long long n, const int32_t* row_dev, float* dst_dev, int dst_ld);
 
 /* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
 

@@ -12,6 +12,7 @@ same reference interfaces for tests and benchmarks:
   ScatterMatricesEstimator  Signal::ScatterMatricesEstimator (the LDA trainer's scatter-matrix pass)
   BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
   ViterbiAligner       Search::Aligner in Viterbi mode (Speech::AlignmentNode): search, traceback and labels on the score matrix
+  BaumWelchAligner     Search::Aligner in mode baum-welch: forward-backward on the score matrix, per-frame item lists with posterior weights
   StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
   CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
@@ -29,7 +30,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "ViterbiAligner", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1528,6 +1529,87 @@ class ViterbiAligner:
                         last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum))
                    for r in res[:n_seg]]
         return label_dev, emission_dev, arc_score_dev, results, tuple(int(c) for c in counters)
+
+
+class BaumWelchAligner:
+    """Search::Aligner in mode baum-welch for a batch of segments whose [frames x emissions] score matrix is on the device: forward
+    search with pruning, f64 forward-backward over the survivors, and per frame the list of (label, emission index, posterior weight).
+    Keyword names are the fields of amx_bw_cfg; ctx None gives a handle that only checks configurations and graphs."""
+
+    FLOATS = ("min_acoustic_pruning", "max_acoustic_pruning", "increment_factor", "min_average_number_of_states", "score_scale", "min_weight")
+    graphs = staticmethod(ViterbiAligner.graphs)
+
+    def __init__(self, ctx, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.BwCfg()
+        self.L.amx_bw_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("BaumWelchAligner: unknown parameter %r" % k)
+            setattr(cfg, k, float(v) if k in self.FLOATS else int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_bw_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_bw_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def align(self, frame_offsets, graphs, scores_dev, scores_ld, n_columns=None, item_offsets_dev=None, weight_f64=True):
+        """segment s = rows [frame_offsets[s], frame_offsets[s + 1]) of scores_dev.  graphs: what graphs() returns, or the list it takes.
+        Returns (items, item_offsets_dev, results, counters): items is a dict of device tensors frame, label, emission (int32), weight
+        (f32) and weight_f64 (None when not asked for), ordered by frame, then decreasing weight, then label; item_offsets_dev (int64,
+        one entry per matrix row up to frame_offsets[-1], plus one) says where a row's items lie; results is a list of dicts per segment."""
+        off = _offsets(frame_offsets, "BaumWelchAligner.align")
+        if not isinstance(graphs, dict):
+            graphs = self.graphs(graphs)
+        n_seg = len(off) - 1
+        if len(graphs["state_offsets"]) != n_seg + 1:
+            raise ValueError("BaumWelchAligner.align: %d segments but graphs of %d" % (n_seg, len(graphs["state_offsets"]) - 1))
+        keep = {k: np.ascontiguousarray(v) for k, v in graphs.items()}
+        g = _lib.AlignGraphs(**{k: v.ctypes.data for k, v in keep.items()})
+        torch = None
+        if self.ctx is not None:
+            import torch
+            if item_offsets_dev is None:
+                item_offsets_dev = torch.zeros(int(off[-1]) + 1, dtype=torch.int64, device=scores_dev.device)
+        res = (_lib.BwResult * max(n_seg, 1))()
+        counters = np.zeros(3, np.uint64)
+        _lib.check(self.L.amx_bw_align_dev(self.h, n_seg, off.ctypes.data, C.byref(g), _ptr(scores_dev), int(scores_ld),
+                                           int(n_columns if n_columns is not None else scores_ld), _ptr(item_offsets_dev), C.cast(res, C.c_void_p),
+                                           counters.ctypes.data))
+        results = [dict(score=np.float32(r.score), reached=bool(r.reached_final), n_iterations=int(r.n_iterations),
+                        last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum),
+                        n_items=int(r.n_items), log_total=float(r.log_total))
+                   for r in res[:n_seg]]
+        items = self.items(scores_dev.device, weight_f64) if self.ctx is not None else None
+        return items, item_offsets_dev, results, tuple(int(c) for c in counters)
+
+    def items(self, device, weight_f64=True, capacity=None):
+        """the item list of the last align() as device tensors of `capacity` (default: the number of items) entries"""
+        import torch
+        n = int(self.L.amx_bw_n_items(self.h))
+        cap = n if capacity is None else int(capacity)
+        out = dict(frame=torch.empty(cap, dtype=torch.int32, device=device), label=torch.empty(cap, dtype=torch.int32, device=device),
+                   emission=torch.empty(cap, dtype=torch.int32, device=device), weight=torch.empty(cap, dtype=torch.float32, device=device),
+                   weight_f64=torch.empty(cap, dtype=torch.float64, device=device) if weight_f64 else None)
+        _lib.check(self.L.amx_bw_items_dev(self.h, cap, _ptr(out["frame"]), _ptr(out["label"]), _ptr(out["emission"]), _ptr(out["weight"]),
+                                           _ptr(out["weight_f64"])))
+        return out
+
+
+def gather_rows(ctx, src_dev, row_dev, dst_dev=None):
+    """dst[i] = src[row_dev[i]] for an f32 matrix and int32 row numbers on the device (amx_gather_rows_dev)"""
+    import torch
+    n, dim = int(row_dev.numel()), int(src_dev.shape[1])
+    if dst_dev is None:
+        dst_dev = torch.empty((n, dim), dtype=torch.float32, device=src_dev.device)
+    _lib.check(_lib.lib().amx_gather_rows_dev(ctx.h, _ptr(src_dev), int(src_dev.stride(0)), dim, n, _ptr(row_dev), _ptr(dst_dev), int(dst_dev.stride(0))))
+    return dst_dev
 
 
 def read_quantiles(path, dim, number_of_quantiles=4, pool=True):

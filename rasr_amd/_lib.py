@@ -104,6 +104,18 @@ class AlignResult(C.Structure):
                 ("average_states", C.c_double), ("state_sum", C.c_ulonglong)]
 
 
+class BwCfg(C.Structure):
+    _fields_ = [("min_acoustic_pruning", C.c_float), ("max_acoustic_pruning", C.c_float), ("increment_factor", C.c_float),
+                ("min_average_number_of_states", C.c_double), ("increase_until_no_score_difference", C.c_int), ("n_best_pruning", C.c_int),
+                ("score_scale", C.c_float), ("min_weight", C.c_float), ("use_partial_sums", C.c_int)]
+
+
+class BwResult(C.Structure):
+    _fields_ = [("score", C.c_float), ("reached_final", C.c_int), ("n_iterations", C.c_int), ("last_threshold", C.c_float),
+                ("average_states", C.c_double), ("state_sum", C.c_ulonglong), ("n_items", C.c_longlong), ("log_total", C.c_double)]
+
+
+AMX_BW_MAX_LABELS = 4096
 AMX_ALIGN_MAX_STATES, AMX_ALIGN_MAX_EMISSIONS, AMX_ALIGN_MAX_OUT_ARCS, AMX_ALIGN_MAX_PASSES = 2048, 4096, 64, 4096
 AMX_ALIGN_VITERBI, AMX_ALIGN_BAUM_WELCH = 0, 1
 AMX_POSTERIOR_MIXTURE, AMX_POSTERIOR_LIKELIHOOD, AMX_POSTERIOR_DENSITY = 0, 1, 2
@@ -290,6 +302,13 @@ SIGNATURES = {
     "amx_align_create": (C.c_int, [_P, C.POINTER(AlignCfg), C.POINTER(_P)]),
     "amx_align_destroy": (None, [_P]),
     "amx_align_viterbi_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(AlignGraphs), _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "amx_bw_default_cfg": (None, [C.POINTER(BwCfg)]),
+    "amx_bw_create": (C.c_int, [_P, C.POINTER(BwCfg), C.POINTER(_P)]),
+    "amx_bw_destroy": (None, [_P]),
+    "amx_bw_n_items": (C.c_longlong, [_P]),
+    "amx_bw_align_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(AlignGraphs), _P, C.c_int, C.c_int, _P, _P, _P]),
+    "amx_bw_items_dev": (C.c_int, [_P, C.c_longlong, _P, _P, _P, _P, _P]),
+    "amx_gather_rows_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_longlong, _P, _P, C.c_int]),
     "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
     "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
     "amx_quanteq_destroy": (None, [_P]),
