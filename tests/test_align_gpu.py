@@ -6,7 +6,9 @@ here except the accumulate test's existing bar in the end-to-end test.
 Shapes.  The search kernel gives a segment one workgroup of 256 lanes and a lane the states lane, lane + 256, ...: the linear graphs of 3,
 70 and 130 states sit inside one wave, across waves and (2048 states, the limit) in every slot of a lane, where the arcs no longer fit
 into LDS and are read from memory.  The next frame's row is fetched one frame ahead: segments of 1, 2 and 3 frames end before, at and
-after the first fetched row is used."""
+after the first fetched row is used.  Every graph here is narrow (24 columns, at most 300 active hypotheses, 3 arcs into a state):
+active sets above 512, 64 arcs out of a state, hundreds to 4096 emissions, the arc count at which LDS is left and calls of hundreds of
+segments are in tests/test_align_wide_gpu.py."""
 import numpy as np
 import pytest
 
@@ -23,24 +25,24 @@ def _torch():
     return torch
 
 
-def device_align(ctx, graphs, off, scores, handle=None, ld=None, rows_before=0, **cfg):
-    """one amx_align_viterbi_dev call; the matrix is padded to `ld` columns and shifted down by `rows_before` rows when asked.  Returns
+def device_align(ctx, graphs, off, scores, handle=None, ld=None, rows_before=0, n_columns=N, **cfg):
+    """one amx_align_viterbi_dev call; the matrix (n_columns wide) is padded to `ld` columns and shifted down by `rows_before` rows when asked.  Returns
     (label, emission, arc_score) of the call's rows as numpy arrays, the per-segment results and the counters; rows and padding that the
     call must not touch are checked to hold what they held."""
     import rasr_amd
     torch = _torch()
     off = np.asarray(off, np.int64) + rows_before
-    ld = ld or N
+    ld = ld or n_columns
     rows = int(off[-1])
     host = np.full((max(rows, 1), ld), np.nan, np.float32)
-    host[rows_before:rows, :N] = scores
+    host[rows_before:rows, :n_columns] = scores
     dev = torch.from_numpy(host).cuda()
     label = torch.full((max(rows, 1),), -7, dtype=torch.int32, device="cuda")
     emission = torch.full((max(rows, 1),), -7, dtype=torch.int32, device="cuda")
     arc = torch.full((max(rows, 1),), -7.0, dtype=torch.float32, device="cuda")
     a = handle or rasr_amd.ViterbiAligner(ctx, **cfg)
     ctx.use_torch_stream()
-    _, _, _, results, counters = a.align(off, graphs, dev, ld, n_columns=N, label_dev=label, emission_dev=emission, arc_score_dev=arc)
+    _, _, _, results, counters = a.align(off, graphs, dev, ld, n_columns=n_columns, label_dev=label, emission_dev=emission, arc_score_dev=arc)
     torch.cuda.synchronize()
     if handle is None:
         a.close()

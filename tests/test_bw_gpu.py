@@ -12,7 +12,8 @@ project's bar on posteriors (tests/test_posterior.py).
 
 Shapes.  The kernels give a segment one workgroup of 256 lanes, a lane the states (and labels) lane, lane + 256, ...: graphs of 3, 70 and
 130 states sit inside one wave and across waves, 2048 states (the limit) fill every slot of a lane and two survivor words per wave; the
-items of a frame are sorted in LDS over the next power of two, from 1 item to 12."""
+items of a frame are sorted in LDS over the next power of two, from 1 item to 12.  Frames of 13 to 4096 items, equal weights beyond two
+items, 4096 labels and emissions, calls of more than 256 rows or segments and a first row above 256 are in tests/test_align_wide_gpu.py."""
 import numpy as np
 import pytest
 
@@ -31,21 +32,21 @@ def _torch():
     return torch
 
 
-def device_bw(ctx, graphs, off, scores, handle=None, ld=None, rows_before=0, **cfg):
-    """one amx_bw_align_dev call; the matrix is padded to `ld` columns and shifted down by `rows_before` rows when asked.  Returns the
+def device_bw(ctx, graphs, off, scores, handle=None, ld=None, rows_before=0, n_columns=N, **cfg):
+    """one amx_bw_align_dev call; the matrix (n_columns wide) is padded to `ld` columns and shifted down by `rows_before` rows when asked.  Returns the
     item arrays (frame relative to the call's first row), the offsets of the call's rows, the per-segment results and the counters."""
     import rasr_amd
     torch = _torch()
     off = np.asarray(off, np.int64) + rows_before
-    ld = ld or N
+    ld = ld or n_columns
     rows = int(off[-1])
     host = np.full((max(rows, 1), ld), np.nan, np.float32)
-    host[rows_before:rows, :N] = scores
+    host[rows_before:rows, :n_columns] = scores
     dev = torch.from_numpy(host).cuda()
     ioff = torch.full((rows + 1,), -7, dtype=torch.int64, device="cuda")
     a = handle or rasr_amd.BaumWelchAligner(ctx, **cfg)
     ctx.use_torch_stream()
-    items, _, results, counters = a.align(off, graphs, dev, ld, n_columns=N, item_offsets_dev=ioff)
+    items, _, results, counters = a.align(off, graphs, dev, ld, n_columns=n_columns, item_offsets_dev=ioff)
     torch.cuda.synchronize()
     got = {k: v.cpu().numpy() for k, v in items.items()}
     if handle is None:
