@@ -1395,6 +1395,112 @@ void amx_comm_destroy(amx_comm* c);
 int amx_counts_to_f64_dev(amx_ctx* ctx, const unsigned long long* counts_dev, double* out_dev, size_t n);
 int amx_f64_to_counts_dev(amx_ctx* ctx, const double* in_dev, unsigned long long* counts_dev, size_t n);
 
+/* ------------------------------------------------------------------ NN training statistics
+ * Nn::FeedForwardTrainer in batch mode (`estimator = dummy | dry-run`, the estimators the reference ships): forward, cross-entropy
+ * error signal from the aligned labels, error backpropagation, per-layer gradient sums -- the pass that writes an Nn::Statistics
+ * file for BatchEstimator -- and Nn::MeanAndVarianceTrainer's feature sums.  No update step, no regulariser.
+ *
+ * Per call of amx_nntrain_accumulate_dev (one mini-batch of the reference: Nn/FeedForwardTrainer.cc:215-269 processBatch_feedInput,
+ * :401-443 finishWithAlignment, :272-337 finishWithError in batch mode), for frame t with class e = emission_dev[t]:
+ *   output o = class_to_output[e]; a disregarded class (-1) never enters the batch (Nn/BufferedAlignedFeatureProcessor.cc:133-145):
+ *       the frame adds to nothing, observations included;
+ *   weight w = class_weights[o] (f32), then *= weight_dev[t] (f64), narrowed (:209-221); totalWeight += |w| (weights->asum());
+ *   CLASS_COUNTS        count[o] += 1 (Nn/FeedForwardTrainer.cc:525-529);
+ *   MEAN_AND_VARIANCE   sum += x * w, sumOfSquares += (x * x) * w on the RAW features, each product rounded to f32
+ *                       (Nn/NeuralNetworkTrainer.cc:465-493);
+ *   BASE                p = softmax of the top layer as amx_ffnn_forward_dev(..., AMX_NN_TOP_SOFTMAX) defines it; errors += (argMax(p)
+ *                       != o) with argMax = the first strictly greater value from the start value Core::Type<f32>::min
+ *                       (Math/FastMatrix.hh:899-909,1089-1101: a NaN never wins, a frame of -max/-inf/NaN only answers 0); objective
+ *                       += -(logf(p[o])) * w, the term in f32 (Nn/Criterion.cc:55-69, Math/FastMatrix.hh:1105-1130: std::log on a
+ *                       float); a p[o] that underflowed to 0 makes the objective +inf, and it is kept so, as the reference keeps it;
+ *   GRADIENT            E_top = (p - delta_o) * w (Nn/Criterion.cc:77-98, Math/FastMatrix.hh:1061-1070: p + (-1), then scal by w);
+ *                       for l = top .. 1: E_l is clipped to +-error_signal_clip (Nn/FeedForwardTrainer.cc:479-497,
+ *                       Math/FastMatrix.hh:1306-1311; not the lowest layer), E_{l-1} = (W_l^T E_l) (.) f'(Y_{l-1})
+ *                       (Nn/LinearLayer.cc:325-367; Math/FastMatrix.hh:1019-1057: sigmoid  e = (f32)((f64)e * ((f64)y * (1.0 - y))),
+ *                       tanh  e = (f32)((f64)e * (1.0 - (f64)(y * y))) with y * y an f32 product, rectified  e = 0 where y <= 0);
+ *                       G_l += X_l E_l^T, g_l += sum_t E_l[:, t] (:500-522), X_0 = the features behind the preprocessing layers.
+ *
+ * The accumulator is ONE caller-owned flat f64 device buffer of amx_nntrain_accumulator_size() doubles, zeroed by the caller, like
+ * amx_gmm_accumulator_size()'s: ranks combine it with amx_comm_all_reduce_f64_dev.  amx_nntrain_layout() gives the offset of every
+ * block; a block whose AMX_NNSTAT_* bit is not set has offset -1 and takes no room:
+ *   per layer: gradient [in x out] row-major (the order of the file's Math::Matrix), then the bias gradient [out]     (GRADIENT)
+ *   feature sum [feature_dim], sum of squares [feature_dim]                                                           (MEAN_AND_VARIANCE)
+ *   class counts [n_outputs], one per network output                                                                  (CLASS_COUNTS)
+ *   tail: nObservations, nClassificationErrors, totalWeight, objective (always; integers ride as f64, exact below 2^53)
+ * This is the reference's `double-precision-accumulator = true`: a call's gradient is formed in f32 from zero, widened and added
+ * (Nn/FeedForwardTrainer.cc:351-352, Nn/Statistics.hh:272-309), and the file narrows to f32 as finalize() does (:150-173).
+ * Summing across calls in f32 (the reference's other mode) is not offered.
+ *
+ * Order of every sum: fixed by the call alone (the frames, T, the network), never by tile choice, occupancy or earlier calls.  Frames
+ * are cut into chunks of AMX_NNTRAIN_CHUNK; within a chunk an element of X E^T, of the bias gradient and of the feature sums is one
+ * ascending-t f32 chain, the chunk partials are added in f32 in ascending order, and the total is widened into the buffer.  Objective
+ * terms are summed in f64.  The same call gives the same bits.
+ *
+ * Labels are checked on the device before anything is written: emission_dev[t] >= n_classes, or an output index >= n_outputs, makes
+ * the call return AMX_ERR_INVALID naming the first such frame (the reference `require`s), acc_dev untouched; a bad label never
+ * becomes an address.  At most AMX_NNTRAIN_MAX_FRAMES frames per call (split longer batches: the buffer adds up).  The cap bounds the
+ * handle's workspace: besides every layer's input and error signal [T x units] it keeps the chunk partials of the largest layer,
+ * ceil(T / AMX_NNTRAIN_CHUNK) x in x out f32 (padded to 128): 0.33 GB at T = 1024 and 1.3 GB at T = 4096 for a 2048 -> 10000 output layer.
+ *
+ * model: the struct the scorers take; precision must be AMX_PREC_FP32, log_prior / prior_scale are not read (a training network has
+ * no prior), the last layer is linear with the softmax on top.  Hidden activations NONE, RELU, SIGMOID, TANH; preprocessing layers of
+ * amx_ffnn_layers run first and are not trainable.  AMX_ERR_UNSUPPORTED with a message naming the layer: ELU, maxout, any other
+ * precision.  Every layer is trained: amx_ffnn_model has no per-layer `trainable` switch, so a network with a frozen layer cannot be
+ * described and gets a gradient block for that layer too (the caller ignores it).  model == NULL is allowed when the mask has neither BASE nor GRADIENT (MeanAndVarianceTrainer needs no network): the
+ * dimensions then come from cfg.feature_dim and cfg.n_outputs. */
+typedef struct amx_nntrain amx_nntrain;
+enum { AMX_NNSTAT_CLASS_COUNTS = 1, AMX_NNSTAT_MEAN_AND_VARIANCE = 2, AMX_NNSTAT_BASE = 4, AMX_NNSTAT_GRADIENT = 8 };
+#define AMX_NNTRAIN_CHUNK 256
+#define AMX_NNTRAIN_MAX_FRAMES 4096
+#define AMX_NNTRAIN_MAX_LAYERS 16
+typedef struct {
+    int          statistics;        /* AMX_NNSTAT_* mask (default BASE | GRADIENT) */
+    float        error_signal_clip; /* `error-signal-clip`; Core::Type<f32>::max = off (default) */
+    const float* class_weights;     /* nullable [n_outputs] (`class-weights-file`); NULL = 1 */
+    int          feature_dim;       /* model == NULL only: the feature dimension */
+    int          n_outputs;         /* model == NULL only: the number of network outputs (class counts) */
+    int          n_classes;         /* model == NULL only: length of class_to_output (ignored when that is NULL) */
+    const int*   class_to_output;   /* model == NULL only: as amx_ffnn_model.class_to_output, nullable */
+} amx_nntrain_cfg;
+typedef struct {
+    int  n_layers, feature_dim, n_outputs;
+    int  in_dim[AMX_NNTRAIN_MAX_LAYERS], out_dim[AMX_NNTRAIN_MAX_LAYERS];
+    long gradient_weights[AMX_NNTRAIN_MAX_LAYERS], gradient_bias[AMX_NNTRAIN_MAX_LAYERS]; /* offsets in doubles, -1 = absent */
+    long feature_sum, feature_square_sum, class_counts;
+    long tail; /* nObservations, nClassificationErrors, totalWeight, objective */
+    long size;
+} amx_nntrain_layout_info;
+void amx_nntrain_default_cfg(amx_nntrain_cfg* cfg);
+/* ctx == NULL gives a host-only handle (layout, files, prior, mean and deviation); amx_nntrain_accumulate_dev on it is AMX_ERR_STATE */
+int  amx_nntrain_create(amx_ctx* ctx, const amx_ffnn_model* model, const amx_ffnn_layers* layers, const amx_nntrain_cfg* cfg, amx_nntrain** out);
+void amx_nntrain_destroy(amx_nntrain* h);
+long amx_nntrain_accumulator_size(const amx_nntrain* h);
+int  amx_nntrain_layout(const amx_nntrain* h, amx_nntrain_layout_info* info);
+/* feats_dev [T x feats_stride] f32, emission_dev [T] class indices (`emission_dev` of the aligners; nullable when the mask is
+ * MEAN_AND_VARIANCE alone), weight_dev nullable [T] f64 alignment weights.  The call waits for the label check only. */
+int  amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats_dev, int feats_stride, int T, const uint32_t* emission_dev,
+                                const double* weight_dev, double* acc_dev);
+/* Nn::Statistics<f32> files (Nn/Statistics.cc:345-389,584-604): 16-byte magic "NNSTAT" + C/# M/# B/# G/# + S + "#####", u32 version 2,
+ * u32 nObservations, f32 totalWeight; BASE: u32 errors, f32 objective; CLASS_COUNTS: u32 n, then (class, count) pairs of the classes
+ * seen, ascending; MEAN_AND_VARIANCE: two Math::Vector<f32> (u32 size, elements); GRADIENT: u32 nLayers, per layer u32 nStreams = 1,
+ * Math::Matrix<f32> [in x out] (u32 rows, u32 columns, u32 rows, per row u32 columns + elements) and Math::Vector<f32> [out].
+ * write narrows the f64 buffer to f32 (u32 for the integers).  read OVERWRITES acc_host with the file's values; the file's magic must
+ * carry exactly the handle's mask, version 2 and the handle's shapes (AMX_ERR_INVALID), precision letter D is AMX_ERR_UNSUPPORTED.
+ * combine (Nn/Statistics.cc:514-536, Nn/Statistics.hh:272-309): the first file read, the others added IN f32 in the order given, as
+ * Statistics<f32>::combine does, then widened into acc_host. */
+int  amx_nnstat_write(const amx_nntrain* h, const double* acc_host, const char* path);
+int  amx_nnstat_read(const amx_nntrain* h, const char* path, double* acc_host);
+int  amx_nnstat_combine(const amx_nntrain* h, const char* const* paths, int n, double* acc_host);
+/* Nn::Prior::setFromClassCounts (Nn/Prior.cc:128-156): v = max(count, back-off count) as u32, as f32 times the class weight; log of
+ * v / sum(v) (std::log on a float, the sum sequential in f32), Core::Type<f32>::min where v == 0.  log_prior [n_outputs].
+ * back_off_count must be a whole number >= 0 (`back-off-count` is a u32 there).  Needs CLASS_COUNTS. */
+int  amx_prior_from_class_counts(const amx_nntrain* h, const double* acc_host, float back_off_count, float* log_prior);
+/* Nn::Statistics<f32>::finalize + MeanAndVarianceTrainer::writeMeanAndStandardDeviation (Nn/Statistics.cc:146-173,
+ * Nn/NeuralNetworkTrainer.cc:447-462) on the narrowed sums: a = (f32)(1.0 / totalWeight); mean = sum * a; stddev = sqrt(sumOfSquares
+ * * a + (-1 * (mean * mean))), every step in f32.  mean, stddev [feature_dim]: what `mean-and-variance-normalization` reads
+ * (amx_nn_vector_write_f32).  Needs MEAN_AND_VARIANCE. */
+int  amx_nnstat_mean_and_deviation(const amx_nntrain* h, const double* acc_host, float* mean, float* stddev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "FeedForwardTrainer", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1724,3 +1725,162 @@ def prior_from_mixture_set(model):
     out = np.zeros(st.n_mix, np.float32)
     _lib.check(_lib.lib().amx_prior_from_mixture_set(C.byref(st), out.ctypes.data))
     return out
+
+
+class FeedForwardTrainer:
+    """Nn::FeedForwardTrainer in batch mode and Nn::MeanAndVarianceTrainer: the statistics pass over aligned frames into ONE flat f64
+    accumulator (include/amx.h, "NN training statistics").  Ws[l] is [out, in] as NnBatchFeatureScorer takes it; Ws=None builds no
+    network (class counts and mean and variance only; give feature_dim / n_outputs).  ctx may be None for host-only use (files, prior,
+    mean and deviation)."""
+
+    FLAGS = {"class-counts": _lib.AMX_NNSTAT_CLASS_COUNTS, "mean-and-variance": _lib.AMX_NNSTAT_MEAN_AND_VARIANCE,
+             "base": _lib.AMX_NNSTAT_BASE, "gradient": _lib.AMX_NNSTAT_GRADIENT}
+
+    def __init__(self, ctx, Ws=None, biases=None, activations=None, statistics=("base", "gradient"), error_signal_clip=None, class_weights=None,
+                 class_to_output=None, preprocessing=None, maxout=None, feature_dim=0, n_outputs=0, precision="fp32"):
+        self.ctx, self.L = ctx, _lib.lib()
+        mask = statistics if isinstance(statistics, int) else sum(self.FLAGS[s] for s in set(statistics))
+        cfg = _lib.NnTrainCfg()
+        self.L.amx_nntrain_default_cfg(C.byref(cfg))
+        cfg.statistics = mask
+        if error_signal_clip is not None:
+            cfg.error_signal_clip = error_signal_clip
+        self._cw = None if class_weights is None else np.ascontiguousarray(class_weights, dtype=np.float32)
+        self._map = None if class_to_output is None else np.ascontiguousarray(class_to_output, dtype=np.int32)
+        cfg.class_weights = _ptr(self._cw)
+        h = C.c_void_p()
+        if Ws is None:
+            cfg.feature_dim, cfg.n_outputs = int(feature_dim), int(n_outputs)
+            cfg.n_classes, cfg.class_to_output = (0 if self._map is None else len(self._map)), _ptr(self._map)
+            expect = cfg.n_outputs
+            model = ext = None
+        else:
+            n = len(Ws)
+            self._Ws = [np.ascontiguousarray(w, dtype=np.float32) for w in Ws]
+            self._bs = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+            self._ind = np.array([w.shape[1] for w in self._Ws], np.int32)
+            self._outd = np.array([w.shape[0] for w in self._Ws], np.int32)
+            self._act = np.array(activations, np.int32)
+            Wp = (C.c_void_p * n)(*[w.ctypes.data for w in self._Ws])
+            Bp = (C.c_void_p * n)(*[b.ctypes.data for b in self._bs])
+            st = _lib.FfnnModel(n, self._ind.ctypes.data, self._outd.ctypes.data, C.cast(Wp, C.c_void_p), C.cast(Bp, C.c_void_p), self._act.ctypes.data,
+                                None, 0.0, {"fp32": AMX_PREC_FP32, "bf16": AMX_PREC_BF16, "bf16x3": _lib.AMX_PREC_BF16X3, "f16mx": _lib.AMX_PREC_F16MX}[precision],
+                                0 if self._map is None else len(self._map), _ptr(self._map), None)
+            model = C.byref(st)
+            ext = None
+            if preprocessing or maxout:
+                self._ext = NnBatchFeatureScorer._layers(self, n, preprocessing or [], maxout or {})
+                ext = C.byref(self._ext)
+            expect = int(self._outd[-1])
+        if self._cw is not None and len(self._cw) != expect:
+            raise ValueError("class_weights has %d entries, the network %d outputs" % (len(self._cw), expect))
+        _lib.check(self.L.amx_nntrain_create(None if ctx is None else ctx.h, model, ext, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.mask = mask
+        lay = _lib.NnTrainLayout()
+        _lib.check(self.L.amx_nntrain_layout(h, C.byref(lay)))
+        self.layout = lay
+        self.n_layers, self.feature_dim, self.n_outputs = lay.n_layers, lay.feature_dim, lay.n_outputs
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amx_nntrain_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulator_size(self):
+        return int(self.L.amx_nntrain_accumulator_size(self.h))
+
+    def accumulate_dev(self, feats_dev, feats_stride, T, emission_dev, acc_dev, weight_dev=None):
+        """one mini-batch of at most AMX_NNTRAIN_MAX_FRAMES frames: feats_dev f32 [T x feats_stride], emission_dev u32 [T] class
+        indices (the aligners' emission_dev), weight_dev f64 [T] or None, acc_dev f64 [accumulator_size()]"""
+        if self.ctx is None:
+            raise RuntimeError("FeedForwardTrainer.accumulate_dev: created without a context")
+        _lib.check(self.L.amx_nntrain_accumulate_dev(self.h, _ptr(feats_dev), int(feats_stride), int(T), _ptr(emission_dev), _ptr(weight_dev), _ptr(acc_dev)))
+
+    def accumulate(self, feats, emission, acc_dev, weights=None):
+        """the same for numpy arrays or device tensors of any length: numpy inputs are uploaded, and the frames go through
+        accumulate_dev in slices of AMX_NNTRAIN_MAX_FRAMES (the buffer adds up)"""
+        import torch
+        dev = "cuda:%d" % self.ctx.device if hasattr(self.ctx, "device") else "cuda"
+
+        def up(a, dtype, view=None):
+            if a is None or hasattr(a, "data_ptr"):
+                return a
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return torch.from_numpy(a if view is None else a.view(view)).to(dev)
+        f, e, w = up(feats, np.float32), up(emission, np.uint32, np.int32), up(weights, np.float64)
+        T, ld = int(f.shape[0]), int(f.stride(0))
+        step = _lib.AMX_NNTRAIN_MAX_FRAMES
+        torch.cuda.synchronize()   # the uploads and the caller's buffer are torch's work, the pass runs on the context's stream
+        for t0 in range(0, T, step):
+            n = min(step, T - t0)
+            self.accumulate_dev(f[t0:], ld, n, None if e is None else e[t0:], acc_dev, None if w is None else w[t0:])
+        self.ctx.synchronize()
+
+    def _host(self, acc):
+        if not isinstance(acc, np.ndarray):
+            acc = acc.detach().cpu().numpy()
+        a = np.ascontiguousarray(acc, dtype=np.float64)
+        if a.size != self.accumulator_size():
+            raise ValueError("accumulator has %d entries, expected %d" % (a.size, self.accumulator_size()))
+        return a
+
+    def statistics(self, acc):
+        """the blocks of a flat accumulator (device tensor or numpy) as a dict: n_observations, n_classification_errors, total_weight,
+        objective; class_counts [n_outputs]; feature_sum, feature_square_sum [feature_dim]; gradient_weights (per layer [in, out], the
+        file's order) and gradient_bias (per layer [out]) -- those the handle's statistics hold"""
+        a, y = self._host(acc), self.layout
+        d = {"n_observations": int(a[y.tail]), "n_classification_errors": int(a[y.tail + 1]), "total_weight": float(a[y.tail + 2]),
+             "objective": float(a[y.tail + 3])}
+        if y.class_counts >= 0:
+            d["class_counts"] = a[y.class_counts:y.class_counts + y.n_outputs].astype(np.int64)
+        if y.feature_sum >= 0:
+            d["feature_sum"] = a[y.feature_sum:y.feature_sum + y.feature_dim].copy()
+            d["feature_square_sum"] = a[y.feature_square_sum:y.feature_square_sum + y.feature_dim].copy()
+        if self.mask & _lib.AMX_NNSTAT_GRADIENT:
+            d["gradient_weights"] = [a[y.gradient_weights[l]:y.gradient_weights[l] + y.in_dim[l] * y.out_dim[l]].reshape(y.in_dim[l], y.out_dim[l]).copy()
+                                     for l in range(y.n_layers)]
+            d["gradient_bias"] = [a[y.gradient_bias[l]:y.gradient_bias[l] + y.out_dim[l]].copy() for l in range(y.n_layers)]
+        return d
+
+    def write(self, acc, path):
+        """flat accumulator -> Nn::Statistics<f32> file (`statistics-filename`), narrowed to single precision"""
+        a = self._host(acc)
+        _lib.check(self.L.amx_nnstat_write(self.h, a.ctypes.data, os.fsencode(path)))
+
+    def read(self, path):
+        """Nn::Statistics<f32> file of this handle's statistics and shapes -> flat accumulator (numpy f64)"""
+        a = np.zeros(self.accumulator_size(), np.float64)
+        _lib.check(self.L.amx_nnstat_read(self.h, os.fsencode(path), a.ctypes.data))
+        return a
+
+
+def combine_nn_statistics(trainer, paths):
+    """Nn::Statistics<f32>::combine: the first file read, the others added in single precision in the order given -> flat accumulator"""
+    names = [os.fsencode(p) for p in paths]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    a = np.zeros(trainer.accumulator_size(), np.float64)
+    _lib.check(trainer.L.amx_nnstat_combine(trainer.h, arr, len(names), a.ctypes.data))
+    return a
+
+
+def prior_from_class_counts(trainer, acc, back_off_count=1):
+    """Nn::Prior::setFromClassCounts: log prior per network output from the accumulator's class counts and the trainer's class weights"""
+    a = trainer._host(acc)
+    out = np.zeros(trainer.n_outputs, np.float32)
+    _lib.check(trainer.L.amx_prior_from_class_counts(trainer.h, a.ctypes.data, float(back_off_count), out.ctypes.data))
+    return out
+
+
+def mean_and_deviation(trainer, acc):
+    """MeanAndVarianceTrainer::writeMeanAndStandardDeviation: (mean, standard deviation), f32 [feature_dim], from the accumulator's sums"""
+    a = trainer._host(acc)
+    mean, dev = np.zeros(trainer.feature_dim, np.float32), np.zeros(trainer.feature_dim, np.float32)
+    _lib.check(trainer.L.amx_nnstat_mean_and_deviation(trainer.h, a.ctypes.data, mean.ctypes.data, dev.ctypes.data))
+    return mean, dev

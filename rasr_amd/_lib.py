@@ -165,6 +165,22 @@ class FfnnLayers(C.Structure):
                 ("maxout_groups", C.c_void_p), ("maxout_sizes", C.c_void_p)]
 
 
+AMX_NNSTAT_CLASS_COUNTS, AMX_NNSTAT_MEAN_AND_VARIANCE, AMX_NNSTAT_BASE, AMX_NNSTAT_GRADIENT = 1, 2, 4, 8
+AMX_NNTRAIN_CHUNK, AMX_NNTRAIN_MAX_FRAMES, AMX_NNTRAIN_MAX_LAYERS = 256, 4096, 16
+
+
+class NnTrainCfg(C.Structure):
+    _fields_ = [("statistics", C.c_int), ("error_signal_clip", C.c_float), ("class_weights", C.c_void_p), ("feature_dim", C.c_int),
+                ("n_outputs", C.c_int), ("n_classes", C.c_int), ("class_to_output", C.c_void_p)]
+
+
+class NnTrainLayout(C.Structure):
+    _fields_ = [("n_layers", C.c_int), ("feature_dim", C.c_int), ("n_outputs", C.c_int),
+                ("in_dim", C.c_int * AMX_NNTRAIN_MAX_LAYERS), ("out_dim", C.c_int * AMX_NNTRAIN_MAX_LAYERS),
+                ("gradient_weights", C.c_long * AMX_NNTRAIN_MAX_LAYERS), ("gradient_bias", C.c_long * AMX_NNTRAIN_MAX_LAYERS),
+                ("feature_sum", C.c_long), ("feature_square_sum", C.c_long), ("class_counts", C.c_long), ("tail", C.c_long), ("size", C.c_long)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against amx.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -382,6 +398,17 @@ SIGNATURES = {
     "amx_comm_destroy": (None, [_P]),
     "amx_counts_to_f64_dev": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "amx_f64_to_counts_dev": (C.c_int, [_P, _P, _P, C.c_size_t]),
+    "amx_nntrain_default_cfg": (None, [C.POINTER(NnTrainCfg)]),
+    "amx_nntrain_create": (C.c_int, [_P, C.POINTER(FfnnModel), C.POINTER(FfnnLayers), C.POINTER(NnTrainCfg), C.POINTER(_P)]),
+    "amx_nntrain_destroy": (None, [_P]),
+    "amx_nntrain_accumulator_size": (C.c_long, [_P]),
+    "amx_nntrain_layout": (C.c_int, [_P, C.POINTER(NnTrainLayout)]),
+    "amx_nntrain_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "amx_nnstat_write": (C.c_int, [_P, _P, C.c_char_p]),
+    "amx_nnstat_read": (C.c_int, [_P, C.c_char_p, _P]),
+    "amx_nnstat_combine": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, _P]),
+    "amx_prior_from_class_counts": (C.c_int, [_P, _P, C.c_float, _P]),
+    "amx_nnstat_mean_and_deviation": (C.c_int, [_P, _P, _P, _P]),
 }
 AMX_COMM_ID_BYTES = 128
 
