@@ -1035,6 +1035,81 @@ int  amx_bw_items_dev(amx_bw* h, long long capacity, int32_t* frame_dev, int32_t
  * numbers are on the device and are not checked. */
 int  amx_gather_rows_dev(amx_ctx* ctx, const float* src_dev, int src_ld, int dim, long long n, const int32_t* row_dev, float* dst_dev, int dst_ld);
 
+/* ------------------------------------------------------------------ Linear-segmentation alignment: delimiter search, flat start */
+
+/* amx_linseg is one Speech::LinearSegmenter (Speech/AlignmentWithLinearSegmentation.cc:30-350; the node speech-linear-segmentation, what
+ * AlignmentWithLinearSegmentationNode::work runs per segment): the first alignment of a training, made without a model.  A two-Gaussian
+ * silence / speech / silence delimiter (Bridle, Sedgwick, ICASSP'77) runs over ONE f32 value per frame, the energy stream, and the
+ * segment's flat allophone-state sequence is spread linearly over the speech part with the silence state on both sides.  Per segment of
+ * N frames with n_states states:
+ *   checks       no states or N = 0: NO_STATES (isAlignmentValid, :311-313, :413-417); N < minimum_segment_length: TOO_SHORT (:316-317);
+ *                N > maximum_segment_length: TOO_LONG (:318-319); then delimitation and spread; index - previousIndex > 2: JUMP
+ *                (:333-336); a last index that is not n_states - 1: MISMATCH (:340-344)
+ *   feed         (:61-71) x widened to f64; M_[i] = M_[i-1] + x, Q_[i] = Q_[i-1] + (x * x + f / 2) / f (penalty f = 0: + x * x): two
+ *                sequential f64 chains in frame order, M_[0] = Q_[0] = 0
+ *   likelihood   (:103-120) logLikelihood(ib, ie) as written: s1 = (f64)(u32)(ib - 1 + N - ie), the variances floored at 0.5, the double
+ *                logarithm, and DBL_MAX unless (m1 / s1) < (m2 / s2) and (f32)(ie - ib) >= minimum_speech_proportion * (f32)N (an f32 product)
+ *   delimiter    (:145-182) proportion == 1: (0, N - 1); N == 1: (0, 0); else number_of_iterations times ib over [2, iEnd - 1) against iEnd,
+ *                then ie over [iBeg + 1, N - 1) against iBeg, in u32 arithmetic, x_min carried across the iterations, a candidate wins
+ *                by strict <: of equal candidates the first.  Starts: iBeg = 1, iEnd = N - 1, x_min = DBL_MAX.
+ *   sietill      should_use_sietill (:200-245): iBeg = 1, iEnd = N; per iteration x_min = DBL_MAX, ib over [2, N) except iEnd with
+ *                logLikelihood(min(iEnd, ib), max(ib, iEnd)), then ie over [2, N) except iBeg likewise, then the pair is put in order.  No
+ *                N == 1 shortcut, and iEnd may stay N: the speech part then ends with the segment's last frame.
+ *   spread       (:325-347) begin = iBeg - 1, end = iEnd - 1; slope = (f32)(n_states - 1) / (f32)max(end - begin, 1);
+ *                index = (u32)round(slope * (f32)(t - begin)) for t in [begin, end]; the silence label on [0, begin) and (end, N)
+ * Added rule (the reference raises an error when Q_ overflows, :69-70, and is undefined on NaN): an energy that is not finite, or an M_ or
+ * Q_ that leaves the finite range, gives NONFINITE.  Any reason but OK writes -1 to every label_dev / emission_dev row of the segment, which
+ * amx_gmm_accumulate_dev and amx_scatter_accumulate_dev skip.
+ * amx_set_contract selects which build of the reference is followed: its -march=native build contracts logLikelihood's `xsil + xspe`
+ * (xspe's product s2 * log(.) goes into the sum as one fused multiply-add); tests/golden/ref_linseg.npz records which arrays the two
+ * builds compute differently.  It contracts feed's `xx * xx + f_ / 2.0` as well, which changes no bit: xx is a widened f32, its square is
+ * exact in f64.
+ * The logarithm is the device library's double log (at most 1 ulp from the exact value), glibc's is the reference's: a delimitation whose
+ * winning candidate is closer than 2^-48 of the larger |s * log(.)| term to another one may differ.
+ * Not built: the flat model itself (the adapter walks the allophone-state graph builder's automaton, setModel :293-305), the silence
+ * index, model and alignment caches, timestamps, the statistics channel. */
+enum { AMX_LINSEG_OK = 0, AMX_LINSEG_TOO_SHORT, AMX_LINSEG_TOO_LONG, AMX_LINSEG_NO_STATES, AMX_LINSEG_JUMP,
+       AMX_LINSEG_MISMATCH, AMX_LINSEG_NONFINITE, AMX_LINSEG_N_REASONS };
+typedef struct {
+    int    number_of_iterations;        /* 3    delimiter.number-of-iterations (:81-84) */
+    double penalty;                     /* 100  delimiter.penalty, 0 = none (:86-89) */
+    float  minimum_speech_proportion;   /* 0.7  delimiter.minimum-speech-proportion, within [0, 1] (:91-94) */
+    int    should_use_sietill;          /* 0    (:259-262) */
+    int    minimum_segment_length;      /* 1    (:254-257) */
+    int    maximum_segment_length;      /* INT_MAX (:249-252) */
+} amx_linseg_cfg;
+typedef struct {
+    int    reason;                      /* AMX_LINSEG_* */
+    int    speech_begin, speech_end;    /* 0-based, inclusive; -1 when not computed */
+    double score;                       /* the final x_min; DBL_MAX if no candidate ever won, a shortcut was taken or nothing was computed */
+} amx_linseg_result;
+typedef struct { /* host: the flat model of every segment, LinearSegmenter::setModel's states_ */
+    const int* state_offsets;  /* [n_seg + 1] */
+    const int* state_label;    /* [states] allophone-state ids in path order */
+    const int* state_emission; /* [states] emission index of each */
+    int        silence_label, silence_emission;
+} amx_linseg_models;
+typedef struct amx_linseg amx_linseg;
+void amx_linseg_default_cfg(amx_linseg_cfg* cfg);
+/* AMX_ERR_INVALID naming the field: a penalty or proportion that is not a number, a negative penalty, a proportion outside [0, 1],
+ * negative iterations or lengths.  AMX_ERR_UNSUPPORTED: more than 4096 iterations (the kernel stops at the first iteration that changes
+ * nothing, which every later one would repeat; the limit bounds a search that never settles). */
+int  amx_linseg_create(amx_ctx* ctx /* nullable: validation only */, const amx_linseg_cfg* cfg, amx_linseg** out);
+void amx_linseg_destroy(amx_linseg* h);
+/* The whole node for n_seg segments in one launch, one readback at the end.  Segment s = frames [frame_offsets[s], frame_offsets[s + 1])
+ * (host list, absolute rows): its energies are energy_dev[t * energy_ld], its labels label_dev[t] and emission_dev[t] (int32).
+ *   result[s]   host
+ *   counters    nullable, host: counters[r] = segments of this call with reason r
+ * Checked before anything is launched, AMX_ERR_INVALID naming the field: offsets that are negative or decrease, state offsets that do not
+ * start at 0 or decrease, a negative label or emission index, energy_ld < 1, NULL buffers where there are frames; frame_offsets[n_seg]
+ * must stay below 2^31.  A handle without a context returns AMX_ERR_STATE after these checks. */
+int  amx_linseg_align_dev(amx_linseg* h, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const amx_linseg_models* models,
+                          const float* energy_dev, int energy_ld /* floats between two frames' values */,
+                          int32_t* label_dev, int32_t* emission_dev, amx_linseg_result* result /*[n_seg]*/,
+                          unsigned long long counters[AMX_LINSEG_N_REASONS] /* nullable */);
+/* Debug read of the handle's workspace after a call: M_ and Q_ of segment s of that call, N + 1 doubles each (host buffers, nullable). */
+int  amx_linseg_chains(amx_linseg* h, int segment, double* m, double* q);
+
 /* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
 
 /* amx_quanteq is one Signal::QuantileEqualization (Signal/QuantileEqualization.{hh,cc}) in SEGMENT MODE (length = right = INT_MAX): the

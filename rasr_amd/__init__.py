@@ -30,7 +30,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "FeedForwardTrainer", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
@@ -1530,6 +1530,81 @@ class ViterbiAligner:
                         last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum))
                    for r in res[:n_seg]]
         return label_dev, emission_dev, arc_score_dev, results, tuple(int(c) for c in counters)
+
+
+class LinearSegmenter:
+    """Speech::LinearSegmenter (the node speech-linear-segmentation) for a batch of segments whose energy is a column of a feature matrix on
+    the device: the first alignment of a training, made without a model.  Keyword names are the fields of amx_linseg_cfg (= the
+    segmenter's and its delimiter's parameters); ctx None gives a handle that only checks configurations and segment tables."""
+
+    FLOATS = ("penalty", "minimum_speech_proportion")
+    REASONS = ("ok", "too_short", "too_long", "no_states", "jump", "mismatch", "nonfinite")
+
+    def __init__(self, ctx, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.LinsegCfg()
+        self.L.amx_linseg_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("LinearSegmenter: unknown parameter %r" % k)
+            setattr(cfg, k, float(v) if k in self.FLOATS else int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_linseg_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_linseg_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def models(segments, silence_label, silence_emission):
+        """the host tables of amx_linseg_models from one (labels, emissions) pair per segment: the flat model's allophone-state ids in
+        path order and the emission index of each.  Returns a dict named like the struct's fields."""
+        offsets, label, emission = [0], [], []
+        for lab, emi in segments:
+            if len(lab) != len(emi):
+                raise ValueError("LinearSegmenter.models: %d labels but %d emission indices" % (len(lab), len(emi)))
+            label.extend(int(v) for v in lab), emission.extend(int(v) for v in emi)
+            offsets.append(len(label))
+        return dict(state_offsets=np.array(offsets, np.int32), state_label=np.array(label, np.int32), state_emission=np.array(emission, np.int32),
+                    silence_label=int(silence_label), silence_emission=int(silence_emission))
+
+    def align(self, frame_offsets, models, energy_dev, energy_ld=1, label_dev=None, emission_dev=None):
+        """segment s = rows [frame_offsets[s], frame_offsets[s + 1]); the energy of row t is energy_dev[t * energy_ld] (f32, on the device:
+        a column of a feature matrix with energy_ld its row length).  models: what models() returns.  label_dev and emission_dev (int32)
+        hold one entry per row up to frame_offsets[-1]; buffers that are not given are created (torch, on the energies' device).
+        Returns (label_dev, emission_dev, results, counters): results a list of dicts per segment (reason, its name, speech_begin,
+        speech_end, score), counters the segments by reason."""
+        off = _offsets(frame_offsets, "LinearSegmenter.align")
+        n_seg = len(off) - 1
+        if len(models["state_offsets"]) != n_seg + 1:
+            raise ValueError("LinearSegmenter.align: %d segments but models of %d" % (n_seg, len(models["state_offsets"]) - 1))
+        keep = {k: np.ascontiguousarray(models[k], np.int32) for k in ("state_offsets", "state_label", "state_emission")}
+        m = _lib.LinsegModels(keep["state_offsets"].ctypes.data, keep["state_label"].ctypes.data, keep["state_emission"].ctypes.data,
+                              int(models["silence_label"]), int(models["silence_emission"]))
+        if self.ctx is not None and int(off[-1]) > 0:
+            import torch
+            if label_dev is None:
+                label_dev = torch.empty(int(off[-1]), dtype=torch.int32, device=energy_dev.device)
+            if emission_dev is None:
+                emission_dev = torch.empty(int(off[-1]), dtype=torch.int32, device=energy_dev.device)
+        res = (_lib.LinsegResult * max(n_seg, 1))()
+        counters = np.zeros(_lib.AMX_LINSEG_N_REASONS, np.uint64)
+        _lib.check(self.L.amx_linseg_align_dev(self.h, n_seg, off.ctypes.data, C.byref(m), _ptr(energy_dev), int(energy_ld), _ptr(label_dev),
+                                               _ptr(emission_dev), C.cast(res, C.c_void_p), counters.ctypes.data))
+        results = [dict(reason=int(r.reason), reason_name=self.REASONS[r.reason], speech_begin=int(r.speech_begin), speech_end=int(r.speech_end),
+                        score=float(r.score)) for r in res[:n_seg]]
+        return label_dev, emission_dev, results, tuple(int(c) for c in counters)
+
+    def chains(self, segment, frames):
+        """debug: M_ and Q_ (frames + 1 doubles each) of a segment of the last call, read from the handle's workspace"""
+        m, q = np.zeros(frames + 1, np.float64), np.zeros(frames + 1, np.float64)
+        _lib.check(self.L.amx_linseg_chains(self.h, int(segment), m.ctypes.data, q.ctypes.data))
+        return m, q
 
 
 class BaumWelchAligner:

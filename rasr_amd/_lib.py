@@ -115,6 +115,22 @@ class BwResult(C.Structure):
                 ("average_states", C.c_double), ("state_sum", C.c_ulonglong), ("n_items", C.c_longlong), ("log_total", C.c_double)]
 
 
+class LinsegCfg(C.Structure):
+    _fields_ = [("number_of_iterations", C.c_int), ("penalty", C.c_double), ("minimum_speech_proportion", C.c_float), ("should_use_sietill", C.c_int),
+                ("minimum_segment_length", C.c_int), ("maximum_segment_length", C.c_int)]
+
+
+class LinsegResult(C.Structure):
+    _fields_ = [("reason", C.c_int), ("speech_begin", C.c_int), ("speech_end", C.c_int), ("score", C.c_double)]
+
+
+class LinsegModels(C.Structure):
+    _fields_ = [("state_offsets", C.c_void_p), ("state_label", C.c_void_p), ("state_emission", C.c_void_p), ("silence_label", C.c_int),
+                ("silence_emission", C.c_int)]
+
+
+(AMX_LINSEG_OK, AMX_LINSEG_TOO_SHORT, AMX_LINSEG_TOO_LONG, AMX_LINSEG_NO_STATES, AMX_LINSEG_JUMP, AMX_LINSEG_MISMATCH, AMX_LINSEG_NONFINITE,
+ AMX_LINSEG_N_REASONS) = range(8)
 AMX_BW_MAX_LABELS = 4096
 AMX_ALIGN_MAX_STATES, AMX_ALIGN_MAX_EMISSIONS, AMX_ALIGN_MAX_OUT_ARCS, AMX_ALIGN_MAX_PASSES = 2048, 4096, 64, 4096
 AMX_ALIGN_VITERBI, AMX_ALIGN_BAUM_WELCH = 0, 1
@@ -325,6 +341,11 @@ SIGNATURES = {
     "amx_bw_align_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(AlignGraphs), _P, C.c_int, C.c_int, _P, _P, _P]),
     "amx_bw_items_dev": (C.c_int, [_P, C.c_longlong, _P, _P, _P, _P, _P]),
     "amx_gather_rows_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_longlong, _P, _P, C.c_int]),
+    "amx_linseg_default_cfg": (None, [C.POINTER(LinsegCfg)]),
+    "amx_linseg_create": (C.c_int, [_P, C.POINTER(LinsegCfg), C.POINTER(_P)]),
+    "amx_linseg_destroy": (None, [_P]),
+    "amx_linseg_align_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(LinsegModels), _P, C.c_int, _P, _P, _P, _P]),
+    "amx_linseg_chains": (C.c_int, [_P, C.c_int, _P, _P]),
     "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
     "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
     "amx_quanteq_destroy": (None, [_P]),
