@@ -1473,7 +1473,7 @@ int amx_f64_to_counts_dev(amx_ctx* ctx, const double* in_dev, unsigned long long
 /* ------------------------------------------------------------------ NN training statistics
  * Nn::FeedForwardTrainer in batch mode (`estimator = dummy | dry-run`, the estimators the reference ships): forward, cross-entropy
  * error signal from the aligned labels, error backpropagation, per-layer gradient sums -- the pass that writes an Nn::Statistics
- * file for BatchEstimator -- and Nn::MeanAndVarianceTrainer's feature sums.  No update step, no regulariser.
+ * file for BatchEstimator -- and Nn::MeanAndVarianceTrainer's feature sums.  The update step and the regulariser: "NN mini-batch training" below.
  *
  * Per call of amx_nntrain_accumulate_dev (one mini-batch of the reference: Nn/FeedForwardTrainer.cc:215-269 processBatch_feedInput,
  * :401-443 finishWithAlignment, :272-337 finishWithError in batch mode), for frame t with class e = emission_dev[t]:
@@ -1575,6 +1575,141 @@ int  amx_prior_from_class_counts(const amx_nntrain* h, const double* acc_host, f
  * * a + (-1 * (mean * mean))), every step in f32.  mean, stddev [feature_dim]: what `mean-and-variance-normalization` reads
  * (amx_nn_vector_write_f32).  Needs MEAN_AND_VARIANCE. */
 int  amx_nnstat_mean_and_deviation(const amx_nntrain* h, const double* acc_host, float* mean, float* stddev);
+
+/* ------------------------------------------------------------------ NN mini-batch training
+ * Nn::FeedForwardTrainer with `batch-mode = false` on the handle above: what runs on every mini-batch besides the statistics pass --
+ * the regulariser on the objective and on the gradient, Statistics::finalize, the estimator's step on the weights and
+ * `accumulate-multiple-batches` -- and Nn::BatchEstimator on a combined statistics buffer.  The statistics of a group of mini-batches
+ * are single precision and live in the handle, beside the weight image W [out x in] the forward GEMM reads and the transposed image
+ * W^T [in x out] the backward GEMM reads; the step updates both images in one pass, nothing travels to the host.
+ *
+ * Per mini-batch (amx_nntrain_step_accumulate_dev), with A = accumulate_multiple_batches and n the running mini-batch count
+ * (Nn/FeedForwardTrainer.cc:215-269,272-337):
+ *   1. n += 1; if (n - 1) % A == 0 the group's statistics are reset (:235-238);
+ *   2. observations, total weight, errors and the forward pass as amx_nntrain_accumulate_dev defines them; the objective of the call
+ *      (its terms summed in f64, as there) is narrowed and added to the group's f32 objective;
+ *   3. objective += regularizer.objectiveFunction(network, (f32)T) (:290-296, Nn/Regularizer.cc:74-94,129-149,182-212): over the
+ *      trainable layers with regularization_constant c > 0, in f32,  tmp = norm(b); tmp += norm(W); tmp *= c (l1: norm = asum) or
+ *      tmp = (f32)((f64)tmp * (c / 2.0)) (l2: norm = dot; centered-l2: of b - b_c, W - W_c); obj += tmp; the result T * obj.  T = the
+ *      frames that entered the batch.  norm is a two-stage f64 sum in a fixed order (segments of 4096 elements of the padded image, the
+ *      segment sums added by one workgroup), narrowed to f32 where asum / dot return;
+ *   4. error backpropagation and the gradient as there; the call's total -- the same f32 bits that amx_nntrain_accumulate_dev widens
+ *      -- is added to the group's statistic with one f32 add;
+ *   5. regularizer.addGradient(network, statistics, (f32)nObservations) (:331-336, Nn/Regularizer.cc:97-119,152-165,215-234), per
+ *      element one fused multiply-add as saxpy computes it:  G = fmaf(c * factor, W, G) (l2), fmaf(c * factor, sign(W), G) (l1),
+ *      fmaf(c * factor, W, G) then fmaf(-(c * factor), W_c, .) (centered-l2), the bias alike.  factor is the group's RUNNING number of
+ *      observations, this call included, so with A > 1 it grows from call to call, as in the reference.  It is fused into the kernel
+ *      that adds the call's gradient.
+ * The step (amx_nntrain_step_estimate_dev; amx_nntrain_step_dev runs it when n % A == 0, :339-349):
+ *   6. Statistics::finalize (Nn/Statistics.cc:146-161): with normalize_by_observations and nObservations != 1, every gradient element
+ *      *= (f32)(1.0 / (f32)nObservations) (sscal: one product) and objective = (f32)((f64)objective * (1.0 / (f32)nObservations));
+ *   7. the estimator, the text of Nn::MeanNormalizedSgd::estimate and MeanNormalizedSgdL1Clipping::estimate
+ *      (Nn/MeanNormalizedSgdEstimator.cc:51-126,136-153).  Per trainable layer l, with m the activation mean of what feeds it when that
+ *      keeps statistics (see below):  G[i][o] = fmaf(m[i], -g[o], G[i][o])  (addOuterProduct(m, g, -1): sger rounds alpha * y first);
+ *      W = fmaf(-(eta * eta_l), G, W);  g[o] = g[o] - sum_i G[i][o] m[i]  (multiply(m, g, transposed, -1, 1): sgemv, the sum in the order
+ *      given below);  b = fmaf(-((eta * eta_bias) * eta_l), g, b).  Without statistics the two terms with m are skipped.
+ *      With log_step_size  step_l = (0 + asum(G) * (eta * eta_l)) + asum(g) * ((eta * eta_bias) * eta_l);  the l1-clipping estimator
+ *      then moves every weight and bias towards zero by v = (c_l * eta) * eta_l (Math/FastMatrix.hh:1291-1303, Math/FastVector.hh:
+ *      500-509:  w > 0: max(0, w - v),  w < 0: min(0, w + v),  a zero of either sign stays).  The gradient blocks hold the finalized
+ *      gradient afterwards.  These two are the only update rules the reference's tree carries; its createEstimator
+ *      (Nn/Estimator.cc:87-104) offers `dummy` and `dry-run` only, so the text defines the arithmetic, not a reachable configuration.
+ *      update_input_layer_weights: the reference's loop over a layer's input streams runs to nPredecessors(), and a layer fed by the
+ *      feature stream has none (Nn/NetworkTopology.cc:58-83, Nn/NeuralNetwork.cc:157-166), so as the text stands the first layer of a
+ *      network without preprocessing layers gets its bias updated and its weights never (nor do they count in step_l).  1 (default)
+ *      updates them like every other layer's; 0 gives the text as it stands.
+ * Activation statistics (Nn/NeuralNetwork.cc:423, Nn/NeuralNetworkLayer.cc:189-334): after the forward pass of a mini-batch of T frames
+ * that entered it, a layer whose smoothing is not no-statistics updates per output unit, y its output:
+ *   none               sum += sum_t y,  sumSq += sum_t y * y,  nObs += T;
+ *   exponential-trace  on its first batch sum = sum_t ((f32)1 / T) y and sumSq = sum_t (f32)(1.0 / T) y * y (each unless an initial mean
+ *                      / deviation was given); then on every batch, the first included, sum = f * sum; sum += sum_t (((f32)1 - f) / T) y,
+ *                      sumSq alike; nObs counts as 1.
+ *   initial mean and deviation (`old-activations-*-file`): on the first batch nObs = 1 (trace) or T, sum = mean * nObs,
+ *                      sumSq = (dev * dev + mean * mean) * nObs, every step in f32.
+ *   mean = fmaf((f32)(1.0 / nObs), sum, 0);  variance = fmaf((f32)(1.0 / nObs), sumSq, -1 * (mean * mean)), then * 1 and + 0
+ *   (`activation-variance-interpolation` is 1, its default).
+ * The sums are the loops  at(row) += scale * m  and  at(row) += scale * m * m  of Math/FastVector.hh:461-478, contraction sites of the
+ * reference's default build: with amx_set_contract(AMX_CONTRACT_FMA) acc = fmaf(scale, y, acc) and acc = fmaf(scale * y, y, acc), with
+ * AMX_CONTRACT_OFF acc + scale * y and acc + (scale * y) * y; scale * y is rounded in both.  Order: frames ascending; the chain of the
+ * call's first AMX_NNTRAIN_CHUNK frames starts from the value the sum holds (the reference's own chain for a mini-batch of up to 256
+ * frames), every further chunk's chain starts from zero and the chunk totals are added in ascending order.
+ * The output layer keeps no statistics (nothing reads them).  The layer that feeds layer 0 is the last preprocessing layer, when there
+ * is one: input_smoothing.
+ * sum_i G[i][o] m[i]: per 32-row tile one ascending chain of fused multiply-adds from zero, the tile totals added in ascending order.
+ *
+ * asum(G), asum(g): the 32 x 32 tiles of the update kernel sum |G| in f32 in a fixed order, the tile sums are added in f64 by one
+ * workgroup in an order the layer's shape fixes, narrowed to f32.  No float atomics anywhere: the same calls give the same bits.
+ *
+ * amx_nntrain_estimate is Nn::BatchEstimator (Nn/BatchEstimator.cc:50-101) on a flat f64 buffer of this handle's layout
+ * (amx_nnstat_read / amx_nnstat_combine, or an all-reduced acc_dev copied out): the buffer narrowed to f32 as the file narrows it
+ * becomes the group's statistics, then the regulariser's objective and gradient with factor = nObservations, finalize, the estimator. */
+enum { AMX_NNSTEP_REG_NONE = 0, AMX_NNSTEP_REG_L1 = 1, AMX_NNSTEP_REG_L2 = 2, AMX_NNSTEP_REG_CENTERED_L2 = 3 };
+enum { AMX_NNSTEP_STAT_NO_STATISTICS = 0, AMX_NNSTEP_STAT_NONE = 1, AMX_NNSTEP_STAT_EXPONENTIAL_TRACE = 2 };
+enum { AMX_NNSTEP_MEAN_NORMALIZED_SGD = 0, AMX_NNSTEP_MEAN_NORMALIZED_SGD_L1_CLIPPING = 1 };
+typedef struct {
+    float               learning_rate;               /* `initial-learning-rate` (default 1) */
+    float               bias_learning_rate;          /* `bias-learning-rate` (default 1) */
+    const float*        layer_learning_rate;         /* nullable [n_layers] (`learning-rate` of a layer); NULL = 1 */
+    const float*        regularization_constant;     /* nullable [n_layers] (`regularization-constant`); NULL = 0 */
+    const int*          trainable;                   /* nullable [n_layers] (`trainable`); NULL = every layer */
+    int                 regularizer;                 /* AMX_NNSTEP_REG_* (default none) */
+    const float* const* center_W;                    /* centered-l2: [n_layers] of [out x in], the layout of amx_ffnn_model.W */
+    const float* const* center_bias;                 /* centered-l2: [n_layers] of [out] */
+    const int*          center_in_dim;               /* centered-l2: [n_layers], the centre's shapes (checked against the network's) */
+    const int*          center_out_dim;
+    int                 estimator;                   /* AMX_NNSTEP_MEAN_NORMALIZED_SGD* (default the plain one) */
+    int                 accumulate_multiple_batches; /* A >= 1 (default 1) */
+    int                 normalize_by_observations;   /* `normalize-by-num-observations` (default 1) */
+    int                 log_step_size;               /* `log-step-size`: fill amx_nnstep_info.step_size (default 0) */
+    int                 update_input_layer_weights;  /* see above (default 1) */
+    const int*          statistics_smoothing;        /* nullable [n_layers] AMX_NNSTEP_STAT_* of each layer's output; NULL = no-statistics */
+    const float*        trace_factor;                /* nullable [n_layers] `exponential-trace-interpolation-factor`; NULL = 0.5 */
+    const float* const* initial_activation_mean;     /* nullable [n_layers] of nullable [out]: `old-activations-mean-file` */
+    const float* const* initial_activation_stddev;   /* the same for `old-activations-standard-deviation-file`; given together with the mean */
+    int                 input_smoothing;             /* AMX_NNSTEP_STAT_* of the last preprocessing layer; must be 0 without one */
+    float               input_trace_factor;          /* default 0.5 */
+    const float*        input_initial_mean;          /* nullable [feature_dim] */
+    const float*        input_initial_stddev;
+} amx_nnstep_cfg;
+typedef struct {
+    long  minibatch;               /* n: step_accumulate calls since amx_nntrain_set_estimator */
+    int   updated;                 /* 1 when the group was finalized and the estimator ran */
+    long  n_observations;          /* of the current group */
+    long  n_classification_errors;
+    float total_weight;
+    float objective;               /* criterion + regulariser, the reference's objectiveFunction_; finalized when updated */
+    float criterion_objective;     /* the same chain without the regulariser's terms */
+    float step_size[AMX_NNTRAIN_MAX_LAYERS]; /* log_step_size and updated: step_l; 0 otherwise */
+} amx_nnstep_info;
+void amx_nnstep_default_cfg(amx_nnstep_cfg* cfg);
+/* Needs a handle with a network whose statistics are exactly BASE | GRADIENT.  Copies what cfg points to, allocates the group's f32
+ * statistics and the centre images, and resets the mini-batch counter; may be called again.  AMX_ERR_INVALID with a message naming the
+ * field or the layer: a regularization constant < 0, A < 1, a learning rate that is not finite, a centre that is missing or of another
+ * shape, no network.  A host-only handle takes the configuration (and its refusals) but cannot step. */
+int  amx_nntrain_set_estimator(amx_nntrain* h, const amx_nnstep_cfg* cfg);
+/* steps 1-5; arguments as amx_nntrain_accumulate_dev's, 1 <= T.  AMX_ERR_STATE on a host-only handle or before set_estimator */
+int  amx_nntrain_step_accumulate_dev(amx_nntrain* h, const float* feats_dev, int feats_stride, int T, const uint32_t* emission_dev,
+                                     const double* weight_dev);
+/* steps 6-7 on the current group, whatever the counter says */
+int  amx_nntrain_step_estimate_dev(amx_nntrain* h);
+/* the two together under the counter rule; info nullable.  Filling info costs one small device-to-host copy at the end of the call,
+ * besides the wait for the label check that every pass has. */
+int  amx_nntrain_step_dev(amx_nntrain* h, const float* feats_dev, int feats_stride, int T, const uint32_t* emission_dev,
+                          const double* weight_dev, amx_nnstep_info* info);
+/* the current group as amx_nntrain_step_dev reports it (waits for the stream) */
+int  amx_nntrain_step_info(amx_nntrain* h, amx_nnstep_info* info);
+/* Nn::BatchEstimator, see above.  acc_host: amx_nntrain_accumulator_size() doubles */
+int  amx_nntrain_estimate(amx_nntrain* h, const double* acc_host, amx_nnstep_info* info);
+/* Read-back (each waits for the stream).  image 0 = the forward image W, 1 = the transposed one, both returned as W [out x in] and
+ * bias [out] (either nullable); a host-only handle returns what it was created with.  Step statistics: the group's gradient G [in x
+ * out] (the order of the file's Math::Matrix) and bias gradient g [out], after the step the finalized gradient. */
+int  amx_nntrain_get_parameters(amx_nntrain* h, int layer, int image, float* W, float* bias);
+int  amx_nntrain_get_step_statistics(amx_nntrain* h, int layer, float* G, float* g);
+/* getActivationMean / getActivationVariance of `layer`'s output, [out] each (either nullable); layer -1 = the last preprocessing layer
+ * ([feature_dim]).  AMX_ERR_STATE when that layer keeps no statistics or has seen no mini-batch yet. */
+int  amx_nntrain_get_activation_statistics(amx_nntrain* h, int layer, float* mean, float* variance);
+/* the input of `layer` (= the output of what feeds it) as the last pass left it: X [T x in], rows of frames that did not enter the
+ * batch included (their inputs were packed as zeros).  T <= the frames of that pass. */
+int  amx_nntrain_get_layer_input(amx_nntrain* h, int layer, int T, float* X);
 
 #ifdef __cplusplus
 }

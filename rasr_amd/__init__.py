@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -1934,6 +1934,178 @@ class FeedForwardTrainer:
         a = np.zeros(self.accumulator_size(), np.float64)
         _lib.check(self.L.amx_nnstat_read(self.h, os.fsencode(path), a.ctypes.data))
         return a
+
+
+class MiniBatchTrainer(FeedForwardTrainer):
+    """Nn::FeedForwardTrainer with batch-mode = false and Nn::BatchEstimator (include/amx.h, "NN mini-batch training"): the statistics
+    pass of FeedForwardTrainer into the handle's own single-precision statistics, the regulariser, finalize and the estimator's step
+    on the device.  The statistics are always base + gradient."""
+
+    REGULARIZERS = {None: _lib.AMX_NNSTEP_REG_NONE, "none": _lib.AMX_NNSTEP_REG_NONE, "l1": _lib.AMX_NNSTEP_REG_L1, "l2": _lib.AMX_NNSTEP_REG_L2,
+                    "centered-l2": _lib.AMX_NNSTEP_REG_CENTERED_L2}
+    SMOOTHING = {None: _lib.AMX_NNSTEP_STAT_NO_STATISTICS, "no-statistics": _lib.AMX_NNSTEP_STAT_NO_STATISTICS, "none": _lib.AMX_NNSTEP_STAT_NONE,
+                 "exponential-trace": _lib.AMX_NNSTEP_STAT_EXPONENTIAL_TRACE}
+    ESTIMATORS = {"mean-normalized-sgd": _lib.AMX_NNSTEP_MEAN_NORMALIZED_SGD,
+                  "mean-normalized-sgd-l1-clipping": _lib.AMX_NNSTEP_MEAN_NORMALIZED_SGD_L1_CLIPPING}
+
+    def __init__(self, ctx, Ws, biases, activations, **kw):
+        kw.setdefault("statistics", ("base", "gradient"))
+        super().__init__(ctx, Ws, biases, activations, **kw)
+
+    def set_estimator(self, learning_rate=1.0, bias_learning_rate=1.0, layer_learning_rate=None, regularization_constant=None, trainable=None,
+                      regularizer=None, center=None, estimator="mean-normalized-sgd", accumulate_multiple_batches=1, normalize_by_observations=True,
+                      log_step_size=False, update_input_layer_weights=True, statistics_smoothing=None, trace_factor=None, initial_activations=None,
+                      input_smoothing=None, input_trace_factor=0.5, input_initial_activations=None):
+        """center: (Ws, biases) of the centred-L2 regulariser's centre, Ws[l] [out, in].  statistics_smoothing: per layer None /
+        "no-statistics", "none" or "exponential-trace" (the output layer keeps none); trace_factor per layer; initial_activations: per
+        layer None or (mean, standard deviation) of its output; the input_* arguments are the same for the last preprocessing layer.
+        Resets the mini-batch counter and the activation statistics."""
+        cfg = _lib.NnStepCfg()
+        self.L.amx_nnstep_default_cfg(C.byref(cfg))
+        n = self.n_layers
+        cfg.learning_rate, cfg.bias_learning_rate = float(learning_rate), float(bias_learning_rate)
+
+        def per_layer(v, dtype, what):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, dtype=dtype)
+            if a.shape != (n,):
+                raise ValueError("%s has shape %s, the network %d layers" % (what, a.shape, n))
+            return a
+        keep = [per_layer(layer_learning_rate, np.float32, "layer_learning_rate"), per_layer(regularization_constant, np.float32, "regularization_constant"),
+                per_layer(trainable, np.int32, "trainable")]
+        cfg.layer_learning_rate, cfg.regularization_constant, cfg.trainable = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2])
+        cfg.regularizer = regularizer if isinstance(regularizer, int) else self.REGULARIZERS[regularizer]
+        cfg.estimator = estimator if isinstance(estimator, int) else self.ESTIMATORS[estimator]
+        if center is not None:
+            cw = [np.ascontiguousarray(w, dtype=np.float32) for w in center[0]]
+            cb = [np.ascontiguousarray(b, dtype=np.float32) for b in center[1]]
+            if len(cw) != n or len(cb) != n:
+                raise ValueError("the centre has %d / %d layers, the network %d" % (len(cw), len(cb), n))
+            if any(b.shape != (w.shape[0],) for w, b in zip(cw, cb)):
+                raise ValueError("a centre bias does not match its weights")
+            ind, outd = np.array([w.shape[1] for w in cw], np.int32), np.array([w.shape[0] for w in cw], np.int32)
+            Wp, Bp = (C.c_void_p * n)(*[w.ctypes.data for w in cw]), (C.c_void_p * n)(*[b.ctypes.data for b in cb])
+            keep += [cw, cb, ind, outd, Wp, Bp]
+            cfg.center_W, cfg.center_bias = C.cast(Wp, C.c_void_p), C.cast(Bp, C.c_void_p)
+            cfg.center_in_dim, cfg.center_out_dim = ind.ctypes.data, outd.ctypes.data
+        self._smoothing = [self.SMOOTHING[m] for m in (statistics_smoothing or [None] * n)]
+        if len(self._smoothing) != n:
+            raise ValueError("statistics_smoothing has %d entries, the network %d layers" % (len(self._smoothing), n))
+        keep.append(np.array(self._smoothing, np.int32))
+        cfg.statistics_smoothing = keep[-1].ctypes.data
+        keep.append(per_layer(trace_factor, np.float32, "trace_factor"))
+        cfg.trace_factor = _ptr(keep[-1])
+        if initial_activations is not None:
+            means = [None if a is None else np.ascontiguousarray(a[0], dtype=np.float32) for a in initial_activations]
+            devs = [None if a is None else np.ascontiguousarray(a[1], dtype=np.float32) for a in initial_activations]
+            for l, m in enumerate(means):
+                if m is not None and (m.shape != (self.layout.out_dim[l],) or devs[l].shape != m.shape):
+                    raise ValueError("initial_activations[%d] does not match the layer's %d outputs" % (l, self.layout.out_dim[l]))
+            Mp = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in means])
+            Dp = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in devs])
+            keep += [means, devs, Mp, Dp]
+            cfg.initial_activation_mean, cfg.initial_activation_stddev = C.cast(Mp, C.c_void_p), C.cast(Dp, C.c_void_p)
+        self._input_smoothing = self.SMOOTHING[input_smoothing]
+        cfg.input_smoothing, cfg.input_trace_factor = self._input_smoothing, float(input_trace_factor)
+        if input_initial_activations is not None:
+            im, idv = (np.ascontiguousarray(a, dtype=np.float32) for a in input_initial_activations)
+            if im.shape != (self.feature_dim,) or idv.shape != im.shape:
+                raise ValueError("input_initial_activations does not match the %d features" % self.feature_dim)
+            keep += [im, idv]
+            cfg.input_initial_mean, cfg.input_initial_stddev = im.ctypes.data, idv.ctypes.data
+        cfg.accumulate_multiple_batches = int(accumulate_multiple_batches)
+        cfg.normalize_by_observations, cfg.log_step_size = int(bool(normalize_by_observations)), int(bool(log_step_size))
+        cfg.update_input_layer_weights = int(bool(update_input_layer_weights))
+        _lib.check(self.L.amx_nntrain_set_estimator(self.h, C.byref(cfg)))
+
+    def _info(self, st):
+        return {"minibatch": int(st.minibatch), "updated": bool(st.updated), "n_observations": int(st.n_observations),
+                "n_classification_errors": int(st.n_classification_errors), "total_weight": float(st.total_weight), "objective": float(st.objective),
+                "criterion_objective": float(st.criterion_objective), "step_size": np.array(st.step_size[:self.n_layers], np.float32)}
+
+    def step_accumulate_dev(self, feats_dev, feats_stride, T, emission_dev, weight_dev=None):
+        """one mini-batch into the group's statistics (arguments as accumulate_dev's, without the buffer)"""
+        _lib.check(self.L.amx_nntrain_step_accumulate_dev(self.h, _ptr(feats_dev), int(feats_stride), int(T), _ptr(emission_dev), _ptr(weight_dev)))
+
+    def step_estimate_dev(self):
+        """finalize the group and run the estimator on it, whatever the mini-batch counter says"""
+        _lib.check(self.L.amx_nntrain_step_estimate_dev(self.h))
+
+    def step_dev(self, feats_dev, feats_stride, T, emission_dev, weight_dev=None, info=True):
+        """step_accumulate_dev, then step_estimate_dev when the counter is a multiple of accumulate_multiple_batches; returns the
+        group's info dict (one small device-to-host copy) unless info is False"""
+        st = _lib.NnStepInfo()
+        _lib.check(self.L.amx_nntrain_step_dev(self.h, _ptr(feats_dev), int(feats_stride), int(T), _ptr(emission_dev), _ptr(weight_dev),
+                                               C.byref(st) if info else None))
+        return self._info(st) if info else None
+
+    def step_info(self):
+        st = _lib.NnStepInfo()
+        _lib.check(self.L.amx_nntrain_step_info(self.h, C.byref(st)))
+        return self._info(st)
+
+    def estimate(self, acc):
+        """Nn::BatchEstimator on a flat accumulator (read(), combine_nn_statistics(), or an all-reduced device buffer)"""
+        a, st = self._host(acc), _lib.NnStepInfo()
+        _lib.check(self.L.amx_nntrain_estimate(self.h, a.ctypes.data, C.byref(st)))
+        return self._info(st)
+
+    def parameters(self, image=0):
+        """[(W [out, in], bias [out])] per layer; image 0 = what the forward GEMM reads, 1 = the transposed image of the backward GEMM"""
+        y, res = self.layout, []
+        for l in range(self.n_layers):
+            W, b = np.zeros((y.out_dim[l], y.in_dim[l]), np.float32), np.zeros(y.out_dim[l], np.float32)
+            _lib.check(self.L.amx_nntrain_get_parameters(self.h, l, int(image), W.ctypes.data, b.ctypes.data))
+            res.append((W, b))
+        return res
+
+    def step_statistics(self):
+        """[(G [in, out], g [out])] per layer: the group's gradient, after a step the finalized gradient"""
+        y, res = self.layout, []
+        for l in range(self.n_layers):
+            G, g = np.zeros((y.in_dim[l], y.out_dim[l]), np.float32), np.zeros(y.out_dim[l], np.float32)
+            _lib.check(self.L.amx_nntrain_get_step_statistics(self.h, l, G.ctypes.data, g.ctypes.data))
+            res.append((G, g))
+        return res
+
+    def activation_statistics(self):
+        """{layer: (mean, variance)} of the layers that keep statistics (getActivationMean / getActivationVariance); layer -1 is the
+        last preprocessing layer"""
+        res = {}
+        modes = [getattr(self, "_input_smoothing", 0)] + list(getattr(self, "_smoothing", []))[:-1]
+        for p, mode in enumerate(modes):
+            if mode == _lib.AMX_NNSTEP_STAT_NO_STATISTICS:
+                continue
+            n = self.layout.in_dim[p]
+            mean, var = np.zeros(n, np.float32), np.zeros(n, np.float32)
+            _lib.check(self.L.amx_nntrain_get_activation_statistics(self.h, p - 1, mean.ctypes.data, var.ctypes.data))
+            res[p - 1] = (mean, var)
+        return res
+
+    def layer_input(self, layer, T):
+        """the input of `layer` as the last pass left it, [T, in] (rows of frames that did not enter the batch included)"""
+        X = np.zeros((int(T), self.layout.in_dim[layer]), np.float32)
+        _lib.check(self.L.amx_nntrain_get_layer_input(self.h, int(layer), int(T), X.ctypes.data))
+        return X
+
+    def save(self, prefix):
+        """every layer's parameter matrix [out x (1 + in)], column 0 the bias, as `parameters-new` writes it: <prefix>-layer-<l+1>.bin
+        (read_nn_matrix / layer_from_parameters read it back); for a layer that keeps activation statistics also
+        <prefix>-layer-<l+1>-activation-mean.xml and -activation-standard-deviation.xml (`new-activations-*-file`: the mean and the
+        square root of the variance; layer 0 in the names is the last preprocessing layer); returns the parameter paths"""
+        paths = []
+        for l, (W, b) in enumerate(self.parameters()):
+            paths.append("%s-layer-%d.bin" % (prefix, l + 1))
+            write_nn_matrix("bin:" + paths[-1], np.concatenate([b[:, None], W], axis=1))
+        if self.ctx is not None:
+            for l, (mean, var) in self.activation_statistics().items():
+                with np.errstate(invalid="ignore"):
+                    dev = np.sqrt(var, dtype=np.float32)
+                for what, v in (("mean", mean), ("standard-deviation", dev)):
+                    path = "%s-layer-%d-activation-%s.xml" % (prefix, l + 1, what)
+                    _lib.check(self.L.amx_nn_vector_write_f32(os.fsencode(path), len(v), v.ctypes.data))
+        return paths
 
 
 def combine_nn_statistics(trainer, paths):

@@ -197,6 +197,27 @@ class NnTrainLayout(C.Structure):
                 ("feature_sum", C.c_long), ("feature_square_sum", C.c_long), ("class_counts", C.c_long), ("tail", C.c_long), ("size", C.c_long)]
 
 
+AMX_NNSTEP_REG_NONE, AMX_NNSTEP_REG_L1, AMX_NNSTEP_REG_L2, AMX_NNSTEP_REG_CENTERED_L2 = 0, 1, 2, 3
+AMX_NNSTEP_MEAN_NORMALIZED_SGD, AMX_NNSTEP_MEAN_NORMALIZED_SGD_L1_CLIPPING = 0, 1
+AMX_NNSTEP_STAT_NO_STATISTICS, AMX_NNSTEP_STAT_NONE, AMX_NNSTEP_STAT_EXPONENTIAL_TRACE = 0, 1, 2
+
+
+class NnStepCfg(C.Structure):
+    _fields_ = [("learning_rate", C.c_float), ("bias_learning_rate", C.c_float), ("layer_learning_rate", C.c_void_p),
+                ("regularization_constant", C.c_void_p), ("trainable", C.c_void_p), ("regularizer", C.c_int), ("center_W", C.c_void_p),
+                ("center_bias", C.c_void_p), ("center_in_dim", C.c_void_p), ("center_out_dim", C.c_void_p), ("estimator", C.c_int),
+                ("accumulate_multiple_batches", C.c_int), ("normalize_by_observations", C.c_int), ("log_step_size", C.c_int),
+                ("update_input_layer_weights", C.c_int), ("statistics_smoothing", C.c_void_p), ("trace_factor", C.c_void_p),
+                ("initial_activation_mean", C.c_void_p), ("initial_activation_stddev", C.c_void_p), ("input_smoothing", C.c_int),
+                ("input_trace_factor", C.c_float), ("input_initial_mean", C.c_void_p), ("input_initial_stddev", C.c_void_p)]
+
+
+class NnStepInfo(C.Structure):
+    _fields_ = [("minibatch", C.c_long), ("updated", C.c_int), ("n_observations", C.c_long), ("n_classification_errors", C.c_long),
+                ("total_weight", C.c_float), ("objective", C.c_float), ("criterion_objective", C.c_float),
+                ("step_size", C.c_float * AMX_NNTRAIN_MAX_LAYERS)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against amx.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -430,6 +451,17 @@ SIGNATURES = {
     "amx_nnstat_combine": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, _P]),
     "amx_prior_from_class_counts": (C.c_int, [_P, _P, C.c_float, _P]),
     "amx_nnstat_mean_and_deviation": (C.c_int, [_P, _P, _P, _P]),
+    "amx_nnstep_default_cfg": (None, [C.POINTER(NnStepCfg)]),
+    "amx_nntrain_set_estimator": (C.c_int, [_P, C.POINTER(NnStepCfg)]),
+    "amx_nntrain_step_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "amx_nntrain_step_estimate_dev": (C.c_int, [_P]),
+    "amx_nntrain_step_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(NnStepInfo)]),
+    "amx_nntrain_step_info": (C.c_int, [_P, C.POINTER(NnStepInfo)]),
+    "amx_nntrain_estimate": (C.c_int, [_P, _P, C.POINTER(NnStepInfo)]),
+    "amx_nntrain_get_parameters": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "amx_nntrain_get_step_statistics": (C.c_int, [_P, C.c_int, _P, _P]),
+    "amx_nntrain_get_activation_statistics": (C.c_int, [_P, C.c_int, _P, _P]),
+    "amx_nntrain_get_layer_input": (C.c_int, [_P, C.c_int, C.c_int, _P]),
 }
 AMX_COMM_ID_BYTES = 128
 

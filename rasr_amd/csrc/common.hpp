@@ -50,6 +50,20 @@ public:
     DevBuf() = default;
     DevBuf(const DevBuf&)            = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept
+            : p_(o.p_), cap_(o.cap_) {
+        o.p_   = nullptr;
+        o.cap_ = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p_ = o.p_, cap_ = o.cap_;
+            o.p_   = nullptr;
+            o.cap_ = 0;
+        }
+        return *this;
+    }
     ~DevBuf() { release(); }
     T*     get() const { return p_; }
     size_t capacity() const { return cap_; }

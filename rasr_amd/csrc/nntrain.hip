@@ -15,9 +15,9 @@
 //   E W          nntrain_gemm_bwd_kernel: the forward kernel's loop on the transposed weight image, derivative and clip in the epilogue
 //   X E^T        nntrain_gemm_tn_kernel: both operands have t as the slow axis, one workgroup per (tile, frame chunk), f32 MFMA bound;
 //                nntrain_reduce_kernel adds the chunk partials in ascending order and widens into the caller's buffer
+//                (nntrain_reduce_step_kernel: the same total into the f32 statistic of mini-batch training, nnstep.hip)
 //   column sums  nntrain_colsum_kernel: bias gradient and the weighted feature sums, one ascending-t chain per column and chunk
-#include "common.hpp"
-#include "ffnn_f32.hpp"
+#include "nntrain.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -369,6 +369,43 @@ __global__ __launch_bounds__(256) void nntrain_reduce_kernel(const float* __rest
     }
 }
 
+// The same total for mini-batch training (nnstep.hip): added to the group's f32 statistic G with ONE f32 add (a group's first call
+// adds to zero), then the regulariser's axpy on the sum (Nn/Regularizer.cc:97-119,152-165,215-234), one fused multiply-add per
+// element as saxpy computes it.  W has G's indexing (the transposed weight image for a layer's gradient, the bias for its bias
+// gradient); Wc the centre.  factor = the group's running observations, this call's included: both counts are read from the device.
+// c == 0: no regulariser for this block.
+__global__ __launch_bounds__(256) void nntrain_reduce_step_kernel(const float* __restrict__ part, int n_chunks, size_t chunk_stride, int rows, int cols, int ld,
+                                                                 float* __restrict__ G, int ldg, int reset, const float* __restrict__ W,
+                                                                 const float* __restrict__ Wc, int regularizer, float c,
+                                                                 const double* __restrict__ group_tail, const double* __restrict__ call_tail) {
+    const long long total = (long long)rows * cols;
+    float           cf    = 0.f;
+    if (c > 0.f && regularizer != AMX_NNSTEP_REG_NONE) {
+        const float factor = (float)(unsigned)(group_tail[0] + call_tail[0]);  // T(statistics.nObservations()): a u32 as f32
+        cf                 = c * factor;
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int    r = (int)(i / cols), col = (int)(i - (long long)r * cols);
+        const size_t at = (size_t)r * ldg + col;
+        float        s = 0.f;
+        for (int q = 0; q < n_chunks; ++q)
+            s = s + part[(size_t)q * chunk_stride + (size_t)r * ld + col];
+        float v = n_chunks > 0 ? (reset ? 0.f : G[at]) + s : G[at];  // n_chunks == 0: the statistic as it is (amx_nntrain_estimate)
+        if (c > 0.f) {
+            const float w = W[at];
+            if (regularizer == AMX_NNSTEP_REG_L2)
+                v = fmaf(cf, w, v);
+            else if (regularizer == AMX_NNSTEP_REG_L1)  // sign (Math/CudaMatrixKernels.cu:897-902): in == 0 ? 0 : copysignf(1.0, in)
+                v = fmaf(cf, w == 0.f ? 0.f : copysignf(1.f, w), v);
+            else if (regularizer == AMX_NNSTEP_REG_CENTERED_L2) {
+                v = fmaf(cf, w, v);
+                v = fmaf(-cf, Wc[at], v);
+            }
+        }
+        G[at] = v;
+    }
+}
+
 // ---- column sums over the frames of one chunk, one ascending-t f32 chain per column: part[c][col]
 // MODE 0: src as it is (bias gradient: rows of dropped frames are zero); MODE 1: x * w; MODE 2: (x * x) * w, each product rounded to
 // f32, frames that did not enter the batch skipped (Nn/NeuralNetworkTrainer.cc:465-493)
@@ -402,29 +439,6 @@ inline int pad128(int n) {
 }  // namespace amx
 
 // ------------------------------------------------------------------------------------ handle
-
-struct amx_nntrain {
-    amx_ctx* ctx  = nullptr;
-    int      mask = 0;
-    float    clip = FLT_MAX;
-    int      L = 0, feature_dim = 0, n_outputs = 0, n_classes = 0;
-    std::vector<int>   in, out, act, Pin, Pout;
-    std::vector<int>   class_to_output;  // empty = identity
-    std::vector<float> class_weights;    // [n_outputs]
-    amx_nntrain_layout_info lay{};
-    // device images
-    std::vector<amx::DevBuf<float>> d_W, d_WT, d_bias;  // [Pout x Pin], [Pin x Pout], [Pout], zero padded
-    amx::DevBuf<int>   d_c2o;
-    amx::DevBuf<float> d_cw;
-    amx::PreOps        pre{};
-    std::vector<amx::DevBuf<float>> d_pre_mean, d_pre_rstd;
-    // workspace of a call, grown to the largest call so far
-    std::vector<amx::DevBuf<float>> d_x, d_E;  // layer inputs [Tpad x Pin], error signals [Tpad x Pout]
-    amx::DevBuf<float>    d_top, d_rowstat, d_w, d_obj, d_part;
-    amx::DevBuf<int>      d_label;
-    amx::DevBuf<unsigned> d_err, d_bad;
-    amx::DevBuf<unsigned, true> h_bad;
-};
 
 namespace {
 
@@ -579,6 +593,11 @@ int amx_nntrain_create(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
     if (cfg->class_weights)
         h->class_weights.assign(cfg->class_weights, cfg->class_weights + h->n_outputs);
     make_layout(h.get());
+    if (!ctx && m)  // amx_nntrain_get_parameters on a host-only handle
+        for (int l = 0; l < h->L; ++l) {
+            h->host_W.emplace_back(m->W[l], m->W[l] + (size_t)h->in[l] * h->out[l]);
+            h->host_bias.emplace_back(m->bias[l], m->bias[l] + h->out[l]);
+        }
 
     if (ctx) {
         AMX_HIP(hipSetDevice(ctx->device));
@@ -640,16 +659,21 @@ int amx_nntrain_layout(const amx_nntrain* h, amx_nntrain_layout_info* info) {
     return AMX_OK;
 }
 
-int amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats, int ldf, int T, const uint32_t* emission, const double* weight, double* acc) {
-    AMX_REQUIRE(h && acc, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: NULL argument");
-    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "amx_nntrain_accumulate_dev: the handle was created without a context");
-    AMX_REQUIRE(T >= 0 && T <= AMX_NNTRAIN_MAX_FRAMES, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: T = %d (0..%d frames per call)", T, AMX_NNTRAIN_MAX_FRAMES);
+}  // extern "C"
+
+namespace amx {
+
+int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint32_t* emission, const double* weight, double* acc, const StepSink* sink,
+                 const char* who) {
+    AMX_REQUIRE(h && (acc || sink), AMX_ERR_INVALID, "%s: NULL argument", who);
+    AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "%s: the handle was created without a context", who);
+    AMX_REQUIRE(T >= 0 && T <= AMX_NNTRAIN_MAX_FRAMES, AMX_ERR_INVALID, "%s: T = %d (0..%d frames per call)", who, T, AMX_NNTRAIN_MAX_FRAMES);
     const bool want_net  = (h->mask & (AMX_NNSTAT_BASE | AMX_NNSTAT_GRADIENT)) != 0;
     const bool want_grad = (h->mask & AMX_NNSTAT_GRADIENT) != 0, want_base = (h->mask & AMX_NNSTAT_BASE) != 0;
     const bool want_mv   = (h->mask & AMX_NNSTAT_MEAN_AND_VARIANCE) != 0, want_cc = (h->mask & AMX_NNSTAT_CLASS_COUNTS) != 0;
-    AMX_REQUIRE(emission || h->mask == AMX_NNSTAT_MEAN_AND_VARIANCE, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: emission_dev is NULL");
+    AMX_REQUIRE(emission || h->mask == AMX_NNSTAT_MEAN_AND_VARIANCE, AMX_ERR_INVALID, "%s: emission_dev is NULL", who);
     if (want_net || want_mv)
-        AMX_REQUIRE(feats && ldf >= h->feature_dim, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: feats_dev is NULL or feats_stride %d < %d", ldf, h->feature_dim);
+        AMX_REQUIRE(feats && ldf >= h->feature_dim, AMX_ERR_INVALID, "%s: feats_dev is NULL or feats_stride %d < %d", who, ldf, h->feature_dim);
     if (T == 0)
         return AMX_OK;
     hipStream_t st   = h->ctx->stream;
@@ -685,10 +709,12 @@ int amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats, int ldf, int 
     AMX_HIP(hipMemcpyAsync(h->h_bad.get(), h->d_bad.get(), 4, hipMemcpyDeviceToHost, st));
     AMX_HIP(hipStreamSynchronize(st));
     const unsigned bad = *h->h_bad.get();
-    AMX_REQUIRE(bad == 0xffffffffu, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: frame %u: the label is out of range (%d classes, %d network outputs)", bad,
+    AMX_REQUIRE(bad == 0xffffffffu, AMX_ERR_INVALID, "%s: frame %u: the label is out of range (%d classes, %d network outputs)", who, bad,
                 h->n_classes, n_out);
     const int*   label = h->d_label.get();
     const float* w     = h->d_w.get();
+    if (sink && sink->reset && sink->group_block)  // a new group starts from zero: only now, so that a refused call leaves everything as it was
+        AMX_HIP(hipMemsetAsync(sink->group_block, 0, sink->group_bytes, st));
 
     // 2. feature sums on the raw features
     if (want_mv) {
@@ -762,7 +788,7 @@ int amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats, int ldf, int 
 
     // 5. class counts and the tail
     hipLaunchKernelGGL(amx::nntrain_tail_kernel, dim3(1), dim3(256), 0, st, T, label, w, (const unsigned*)(want_base ? h->d_err.get() : nullptr),
-                       (const float*)h->d_obj.get(), want_cc ? acc + y.class_counts : (double*)nullptr, acc + y.tail);
+                       (const float*)h->d_obj.get(), want_cc ? acc + y.class_counts : (double*)nullptr, sink ? sink->call_tail : acc + y.tail);
     AMX_HIP(hipGetLastError());
 
     if (want_grad) {
@@ -802,17 +828,38 @@ int amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats, int ldf, int 
                 }
                 amx::ScopedKernelTimer timer(h->ctx, "nntrain_gradient_sums");
                 const long long total = (long long)h->in[l] * h->out[l];
-                hipLaunchKernelGGL(amx::nntrain_reduce_kernel, dim3((int)std::min<long long>(16384, (total + 255) / 256)), dim3(256), 0, st, (const float*)h->d_part.get(),
-                                   tn_chunks, (size_t)Kp * Np, h->in[l], h->out[l], Np, acc + y.gradient_weights[l]);
+                const dim3      rgrid((int)std::min<long long>(16384, (total + 255) / 256));
+                if (sink)
+                    hipLaunchKernelGGL(amx::nntrain_reduce_step_kernel, rgrid, dim3(256), 0, st, (const float*)h->d_part.get(), tn_chunks, (size_t)Kp * Np, h->in[l],
+                                       h->out[l], Np, sink->G[l], Np, sink->reset, (const float*)h->d_WT[l].get(), sink->WTc[l], sink->regularizer, sink->c[l],
+                                       sink->group_tail, (const double*)sink->call_tail);
+                else
+                    hipLaunchKernelGGL(amx::nntrain_reduce_kernel, rgrid, dim3(256), 0, st, (const float*)h->d_part.get(), tn_chunks, (size_t)Kp * Np, h->in[l], h->out[l],
+                                       Np, acc + y.gradient_weights[l]);
                 hipLaunchKernelGGL(amx::nntrain_colsum_kernel<0>, dim3((h->out[l] + 255) / 256, n_chunks), dim3(256), 0, st, (const float*)h->d_E[l].get(), Np, T, h->out[l],
                                    label, w, h->d_part.get());
-                hipLaunchKernelGGL(amx::nntrain_reduce_kernel, dim3(std::min(1024, (h->out[l] + 255) / 256)), dim3(256), 0, st, (const float*)h->d_part.get(), n_chunks,
-                                   (size_t)h->out[l], 1, h->out[l], h->out[l], acc + y.gradient_bias[l]);
+                const dim3 bgrid(std::min(1024, (h->out[l] + 255) / 256));
+                if (sink)
+                    hipLaunchKernelGGL(amx::nntrain_reduce_step_kernel, bgrid, dim3(256), 0, st, (const float*)h->d_part.get(), n_chunks, (size_t)h->out[l], 1, h->out[l],
+                                       h->out[l], sink->g[l], h->out[l], sink->reset, (const float*)h->d_bias[l].get(), sink->bc[l], sink->regularizer, sink->c[l],
+                                       sink->group_tail, (const double*)sink->call_tail);
+                else
+                    hipLaunchKernelGGL(amx::nntrain_reduce_kernel, bgrid, dim3(256), 0, st, (const float*)h->d_part.get(), n_chunks, (size_t)h->out[l], 1, h->out[l],
+                                       h->out[l], acc + y.gradient_bias[l]);
             }
             AMX_HIP(hipGetLastError());
         }
     }
     return AMX_OK;
+}
+
+}  // namespace amx
+
+extern "C" {
+
+int amx_nntrain_accumulate_dev(amx_nntrain* h, const float* feats, int ldf, int T, const uint32_t* emission, const double* weight, double* acc) {
+    AMX_REQUIRE(h && acc, AMX_ERR_INVALID, "amx_nntrain_accumulate_dev: NULL argument");
+    return amx::nntrain_pass(h, feats, ldf, T, emission, weight, acc, nullptr, "amx_nntrain_accumulate_dev");
 }
 
 }  // extern "C"
@@ -1016,6 +1063,36 @@ int read_stat(const amx_nntrain* h, const char* path, NnStat* s, const char* who
 }
 
 }  // namespace
+
+namespace amx {
+
+int nntrain_add_regularizer(amx_nntrain* h, const StepSink* sink) {
+    hipStream_t st = h->ctx->stream;
+    for (int l = 0; l < h->L; ++l) {
+        if (!(sink->c[l] > 0.f))
+            continue;
+        const long long total = (long long)h->in[l] * h->out[l];
+        hipLaunchKernelGGL(nntrain_reduce_step_kernel, dim3((int)std::min<long long>(16384, (total + 255) / 256)), dim3(256), 0, st, (const float*)nullptr, 0, (size_t)0,
+                           h->in[l], h->out[l], h->Pout[l], sink->G[l], h->Pout[l], 0, (const float*)h->d_WT[l].get(), sink->WTc[l], sink->regularizer, sink->c[l],
+                           sink->group_tail, (const double*)sink->call_tail);
+        hipLaunchKernelGGL(nntrain_reduce_step_kernel, dim3(std::min(1024, (h->out[l] + 255) / 256)), dim3(256), 0, st, (const float*)nullptr, 0, (size_t)0, 1, h->out[l],
+                           h->out[l], sink->g[l], h->out[l], 0, (const float*)h->d_bias[l].get(), sink->bc[l], sink->regularizer, sink->c[l], sink->group_tail,
+                           (const double*)sink->call_tail);
+    }
+    AMX_HIP(hipGetLastError());
+    return AMX_OK;
+}
+
+int nntrain_narrow_gradient(const amx_nntrain* h, const double* acc, std::vector<std::vector<float>>* gw, std::vector<std::vector<float>>* gb, uint32_t* n_obs,
+                            uint32_t* n_err, float* total_weight, float* objective, const char* who) {
+    NnStat s;
+    AMX_TRY(narrow(h, acc, &s, who));
+    *gw = std::move(s.gw), *gb = std::move(s.gb);
+    *n_obs = s.n_obs, *n_err = s.n_err, *total_weight = s.total_weight, *objective = s.objective;
+    return AMX_OK;
+}
+
+}  // namespace amx
 
 extern "C" {
 
