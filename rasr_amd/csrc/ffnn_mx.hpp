@@ -1323,6 +1323,17 @@ __global__ __launch_bounds__(C::THREADS) void gemm_mx_kernel(const char* __restr
                         v[4 * g + 1]    = activate<ACT>(acc[i][j][4 * g + 1] + b4.y);
                         v[4 * g + 2]    = activate<ACT>(acc[i][j][4 * g + 2] + b4.z);
                         v[4 * g + 3]    = activate<ACT>(acc[i][j][4 * g + 3] + b4.w);
+                        // units beyond the layer are the next layer's padded k: zero, like every padded k (the head of the file).  Their
+                        // accumulator and bias are zero, and so is every activation of zero but the sigmoid's 0.5 -- which the weights'
+                        // zero columns kept out of the sum, but not out of the block maximum: a frame whose live values in the layer's last
+                        // K-tile were all below 0.5 had q and r taken one exponent too coarse (tests/test_ffnn_split_exact_gpu.py)
+                        if constexpr (ACT == AMX_ACT_SIGMOID) {
+                            const int nu = n0 + wn * WNR + 32 * i + 8 * g + 4 * hh;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (nu + e >= n_valid)
+                                    v[4 * g + e] = 0.f;
+                        }
                     }
 #pragma unroll
                     for (int u = 0; u < 16; ++u)
