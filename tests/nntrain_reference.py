@@ -302,9 +302,14 @@ NETWORKS = {"a": [24, 40, 33, 50], "b": [7, 130, 129]}
 FRAMES = (1, 31, 127, 128, 129, 300)
 
 
+def dims_of(name):
+    """a key of NETWORKS, or the dimensions themselves (tests/nn_wide_cases.py keeps its networks out of NETWORKS)"""
+    return NETWORKS[name] if isinstance(name, str) else [int(d) for d in name]
+
+
 def network(name, acts, seed):
     """weights N(0, 1 / in) and small biases; acts: the hidden activations"""
-    dims = NETWORKS[name]
+    dims = dims_of(name)
     rng = np.random.Generator(np.random.PCG64(seed))
     Ws = [(rng.standard_normal((n, i)) / np.sqrt(i) * 1.5).astype(F32) for i, n in zip(dims[:-1], dims[1:])]
     bs = [(rng.standard_normal(n) * 0.1).astype(F32) for n in dims[1:]]
@@ -323,7 +328,7 @@ def frames(dims, T, seed, n_classes=None, positive=False):
 
 def variant(name, acts, T, seed, frame_weights=False, class_weights=False, disregard=False, pre=False, clip=None):
     """(Net, feats, emission, weights): one configuration of the GPU tests"""
-    dims = NETWORKS[name]
+    dims = dims_of(name)
     Ws, bs, a = network(name, acts, seed)
     rng = np.random.Generator(np.random.PCG64(seed + 77))
     c2o, n_classes = None, dims[-1]

@@ -4,6 +4,11 @@ rasr_amd.MiniBatchTrainer against the plain restatement of tests/nnstep_referenc
 Shapes.  Networks 24-40-33-50 and 7-130-129: no dimension is a multiple of the 128 padding or of the update kernel's 32 x 32 tile, 130
 and 129 leave a nearly empty last tile in both directions of the transpose.  T = 1, 129, 300: below a tile, past one, and two frame
 chunks with a padded tail.
+What these shapes do not reach: a layer has at most 64 update tiles and 16 norm segments of 4096, so nnstep_stepsize_kernel and
+nnstep_sum_kernel take one trip over their partial sums; nnstep_bias_kernel runs one block; the bias term with activation statistics
+adds the column partials of at most eight tile rows; the activation sums and the chunk partials of a gradient never see a third frame
+chunk; no network has one layer only.  tests/test_nn_wide_gpu.py (cases: tests/nn_wide_cases.py) runs the step on 300-40-260-700 and on
+1030-1100 (1296 update tiles, 324 norm segments, five bias blocks) with 513 frames per mini-batch.
 
 Bars.  Element-wise results are exact given identical inputs read back from the device: the finalized gradient, the new weights in both
 images, the biases, the clipped weights, the regularised gradient, the outer product with an activation mean, and the activation

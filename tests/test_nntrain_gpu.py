@@ -5,6 +5,12 @@ Shapes.  Networks 24-40-33-50 and 7-130-129: no dimension is a multiple of the 1
 second one.  T = 1, 31, 127, 128, 129, 300: the tile edge from both sides and, at 300, two frame chunks (AMX_NNTRAIN_CHUNK = 256) with a
 padded tail.  Every hidden activation set runs plain at every T and with one option per T (frame weights, class weights, disregarded
 classes, preprocessing layers, the clip) and all of them at T = 300.
+What these shapes do not reach: with at most 130 outputs and 24 features every 256-strided loop (softmax, arg-max, error signal, column
+sums) takes one trip, so waves 2 and 3 of the arg-max hold no candidate and its cross-wave tie rule is never decided; the tile grids are
+1 x 1, 1 x 2 and 2 x 2, never with more k-tiles than n-tiles and never three to a side; a call has two frame chunks at most and stays far
+below AMX_NNTRAIN_MAX_FRAMES; every network has hidden layers; the labels are random, so nearly every frame is a classification error
+whatever the arg-max says.  tests/test_nn_wide_gpu.py (cases: tests/nn_wide_cases.py) runs the same pass on 300-40-260-700 and
+1030-1100 with 513 to 4096 frames and labels of which half are right.
 
 Bars.  Counts, observations, classification errors and the total weight are exact.  Gradients, bias gradients, feature sums and the
 objective are held to the bars tests/golden/make_nntrain_golden.py measured and stored in tests/golden/ref_nntrain.npz (4 x the
