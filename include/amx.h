@@ -1110,6 +1110,118 @@ int  amx_linseg_align_dev(amx_linseg* h, int n_seg, const long* frame_offsets /*
 /* Debug read of the handle's workspace after a call: M_ and Q_ of segment s of that call, N + 1 doubles each (host buffers, nullable). */
 int  amx_linseg_chains(amx_linseg* h, int segment, double* m, double* q);
 
+/* ------------------------------------------------------------------ Decision-tree state tying: device example sums and split search */
+
+/* The step between a monophone and a triphone system: Speech::FeatureAccumulator builds one Cart::Example per allophone state from the
+ * aligned corpus (Speech/DecisionTreeTrainer.cc:54-90), Cart::DecisionTreeTrainer grows the tree (Cart/DecisionTreeTrainer.cc:353-801)
+ * with StateTyingDecisionTreeTrainer::LogLikelihoodGain as its scorer (Speech/DecisionTreeTrainer.cc:134-250).
+ *
+ * ACCUMULATION.  The accumulator is ONE caller-owned flat f64 device buffer [n_labels x (1 + 2 dim)], zeroed by the caller before the
+ * first call; row id = [nObs, sum[dim], sumSq[dim]] is the Example of allophone state id (Cart/Example.hh: FloatBox(2, nCols)).  Ranks
+ * combine it with amx_comm_all_reduce_f64_dev.  Per frame t with id = label_dev[t] (what amx_align_*, amx_bw_* and amx_linseg_align_dev
+ * leave there) and weight w (weight_dev NULL: 1), processAlignedFeature (:58-90):
+ *     id == -1 or w == 0: nothing;  nObs[id] += w;  sum[id][c] += (f64)x * w;  sumSq[id][c] += (f64)(x * x) * w   (x * x an f32 product;
+ *     Mm::Weight is f64, Mm/Types.hh:30)
+ * Per (id, c) this is one chain over the frames in ascending order that CONTINUES from the value in the buffer: a corpus fed in order,
+ * cut into calls anywhere, gives the reference's bits.  No floating-point atomics; nothing depends on the launch.  The two `+= . * w`
+ * are contraction sites of the reference's default build: amx_set_contract(AMX_CONTRACT_FMA) makes them fused multiply-adds.  With
+ * w = 1 both settings give the same bits (the product is exact).
+ * Labels are checked on the device before anything is written: an id outside [0, n_labels) other than -1 returns AMX_ERR_INVALID naming
+ * the first such frame, acc_dev untouched (amx_nntrain_accumulate_dev's convention).  The call synchronises the context's stream.
+ * Expected cost (not a measurement): the longest label's chain, silence, at one dependent f64 operation per frame. */
+size_t amx_cart_accumulator_size(int n_labels, int dim);   /* doubles */
+int    amx_cart_accumulate_dev(amx_ctx* ctx, const float* feats_dev, int feats_stride /* floats between two frames */, int dim, int T,
+                               const int32_t* label_dev, const double* weight_dev /* nullable, [T] */, int n_labels, double* acc_dev);
+
+/* TRAINING.  Questions, property maps and the XML files of examples and trees stay with the adapter (Cart::Question and its kin are
+ * RASR objects): it evaluates every question once on every example and hands over bits.
+ *   problem   n_examples rows of the accumulator (the caller drops labels it has not seen): n_obs[E], values[E x 2 dim] (sum, then sumSq),
+ *             and answers[n_questions x ceil(E / 32)], bit (e & 31) of word e / 32 of row q = (question q (properties of e) == TRUE).
+ *             Host arrays; the library uploads them once per training.
+ *   plan      TrainingPlan (Cart/DecisionTreeTrainer.hh:130-170): max_leaves and steps, each with an action, min_obs, min_gain and a
+ *             list of rows of `answers` (its questions, in the order of its question list); variance_clipping is the scorer's.
+ *             randomize is nRandomQuestion: above 1 it is AMX_ERR_UNSUPPORTED (the reference seeds the choice with time(0), :219).
+ * What is followed operation by operation:
+ *   lists     a node's example list is ordered; a split is a stable partition (:498-504); rollbackSplit leaves left + right concatenated
+ *             for the next step (:599-611); a node's question-id list loses the used entry by swap with the back (:575-576), so ties in
+ *             the gain depend on that order
+ *   counts    nLeftObs / nRightObs and the root's nObs are u32 that take f64 additions: every addition truncates (:360, :458, :462)
+ *   skips     node.nObs < 2 * minObs (u32 product): no split (:398); a side below minObs (:471); strict: a side of 0 observations or a
+ *             gain of 0 (:473, :486); gain < minGain (:484); a negative gain is skipped, and counted as an error unless f32(gain) is
+ *             within 20 ulps of 0 (:479-483; the reference's error() goes on as well)
+ *   winner    SplitHypothesesManager::push with one slot (:249-258): the first question with the strictly largest gain
+ *   queue     Core::PriorityQueue's own heap moves (Core/PriorityQueue.hh:55-108), equal gains included; the leaf limit
+ *             nLeaf + nodes + splits < maxLeaves before each commit (:635, :662, :670); split, partition and cluster (:622-676)
+ *   numbers   order numbers in insertSplit (:534-535); class ids in commitNode's pre-order (:706-726) with the RIGHT child first: the two
+ *             recursive calls are arguments of one call (:712-714), their order is the compiler's, and the reference's GCC build
+ *             evaluates them from the right (found by tests/golden/make_cart_golden.py, held by tests/golden/ref_cart.npz)
+ *   score     logLikelihood (Speech/DecisionTreeTrainer.cc:205-232): plain f64 chains in list order from +0.0, mu = s / n,
+ *             var = q / n - mu * mu, clipped, ll an ascending chain of ::log, (0.5 n)(d + d log(pi + pi) + ll); gain = father - (left + right).
+ *             amx_set_contract(AMX_CONTRACT_FMA): var = fma(-mu, mu, q / n) and d + d * log(.) = fma(d, log(.), d), the sites a
+ *             contracting build fuses.
+ * The sums and counts of every (node, question) come from the device (cart.hip), in the reference's order.  The device's log is not
+ * glibc's, so its gain is a SCREEN: a question goes through the host's ::log -- on the device's sums -- unless the screen decides it by
+ * more than a margin derived from the log's error bound.  exact_all = 1 sends every question through the host
+ * (the slow reference mode, and the check on the margin).  splitNode depends on the node's list, its question list and the step alone,
+ * so the children of queued splits are evaluated ahead of the queue in wide launches; this changes no result.
+ * Refused: AMX_ERR_INVALID naming the field for NULL arrays, sizes below their minimum, a negative or non-finite n_obs, an unknown action,
+ * a question row outside the matrix; AMX_ERR_UNSUPPORTED for randomize > 1, dim > 1024 and a total n_obs of 2^32 or more (the reference
+ * counts in 32 bits).  ctx == NULL: AMX_ERR_STATE after these checks. */
+enum { AMX_CART_SPLIT = 0, AMX_CART_PARTITION = 1, AMX_CART_CLUSTER = 2 };
+typedef struct {
+    int             n_examples, dim, n_questions;
+    const double*   n_obs;    /* [E] */
+    const double*   values;   /* [E x 2 dim] */
+    const uint32_t* answers;  /* [Q x ceil(E / 32)] */
+} amx_cart_problem;
+typedef struct {
+    int        action;        /* AMX_CART_* */
+    unsigned   min_obs;       /* 0 */
+    double     min_gain;      /* 0 */
+    int        randomize;     /* 1 */
+    int        n_questions;
+    const int* questions;     /* rows of answers */
+} amx_cart_step;
+typedef struct {
+    unsigned             max_leaves;          /* UINT_MAX */
+    int                  n_steps;
+    const amx_cart_step* steps;
+    double               variance_clipping;   /* 0 */
+    int                  exact_all;           /* 0 */
+} amx_cart_plan;
+typedef struct { /* in `order` */
+    int      step, row;       /* the question: the step and its row of answers; -1, -1 for a leaf */
+    int      left, right;     /* orders of the children; -1 for a leaf */
+    unsigned depth, n_obs;
+    double   score;
+    int      class_id;        /* -1 for an inner node */
+} amx_cart_node;
+typedef struct { /* one committed split (insertSplit's log message) */
+    int      node, step, row;
+    unsigned depth;
+    double   gain, total_gain;
+} amx_cart_commit;
+typedef struct { /* QuestionStatistic (Cart/DecisionTreeTrainer.cc:140-156) of every question of every step that ran */
+    int      step, row;
+    unsigned count;
+    double   min_gain, sum_gain, max_gain;
+    unsigned min_depth, sum_depth, max_depth;
+} amx_cart_qstat;
+typedef struct {
+    int      n_nodes, n_leaves, n_commits, n_question_stats, n_examples;
+    unsigned n_obs;
+    double   initial_score, total_gain;
+    unsigned long long negative_gain_errors, items_screened, items_reevaluated, launches;
+} amx_cart_info;
+typedef struct amx_cart_tree amx_cart_tree;
+int  amx_cart_train(amx_ctx* ctx, const amx_cart_problem* problem, const amx_cart_plan* plan, amx_cart_tree** out);
+void amx_cart_tree_destroy(amx_cart_tree* tree);
+int  amx_cart_tree_info(const amx_cart_tree* tree, amx_cart_info* info);
+/* host buffers, each nullable: nodes[n_nodes], classes[n_examples] (example -> class id), log[n_commits], question_stats[n_question_stats] */
+int  amx_cart_tree_get(const amx_cart_tree* tree, amx_cart_node* nodes, int32_t* classes, amx_cart_commit* log, amx_cart_qstat* question_stats);
+/* the split search's launch shape for a dimension: examples per LDS stage, questions per workgroup (tests pick their sizes around them) */
+void amx_cart_kernel_shape(int dim, int* stage_examples, int* tile_questions);
+
 /* ------------------------------------------------------------------ Quantile equalisation: device grid search, quantile files, apply */
 
 /* amx_quanteq is one Signal::QuantileEqualization (Signal/QuantileEqualization.{hh,cc}) in SEGMENT MODE (length = right = INT_MAX): the

@@ -1607,6 +1607,108 @@ class LinearSegmenter:
         return m, q
 
 
+class CartExampleAccumulator:
+    """Speech::FeatureAccumulator on the device: one Cart::Example per allophone state, row id = [nObs, sum[dim], sumSq[dim]] of one flat f64
+    device buffer [n_labels x (1 + 2 dim)] (`acc`, a torch tensor that ranks may all-reduce).  Feed the aligned corpus in order, cut into
+    calls anywhere: every (label, component) is one chain over the frames in ascending order that continues across calls."""
+
+    def __init__(self, ctx, n_labels, dim):
+        import torch
+        self.L, self.ctx, self.n_labels, self.dim = _lib.lib(), ctx, int(n_labels), int(dim)
+        size = int(self.L.amx_cart_accumulator_size(self.n_labels, self.dim))
+        if size == 0:
+            raise ValueError("CartExampleAccumulator: n_labels %d, dim %d" % (self.n_labels, self.dim))
+        self.acc = torch.zeros(size, dtype=torch.float64, device="cuda:%d" % ctx.device)
+
+    def accumulate(self, feats_dev, label_dev, weight_dev=None, feats_stride=None):
+        """feats_dev [T x dim] f32 (or rows feats_stride floats apart), label_dev [T] int32 as the aligners leave it (-1: skipped),
+        weight_dev [T] f64 or None (weight 1)"""
+        T = int(label_dev.shape[0])
+        stride = int(feats_stride) if feats_stride is not None else (int(feats_dev.stride(0)) if feats_dev.dim() == 2 else self.dim)
+        _lib.check(self.L.amx_cart_accumulate_dev(self.ctx.h, _ptr(feats_dev), stride, self.dim, T, _ptr(label_dev), _ptr(weight_dev), self.n_labels,
+                                                  _ptr(self.acc)))
+
+    def rows(self):
+        """the accumulator on the host, [n_labels x (1 + 2 dim)]"""
+        return self.acc.cpu().numpy().reshape(self.n_labels, 1 + 2 * self.dim)
+
+    def examples(self):
+        """(ids, n_obs, values) of the labels that were seen: what DecisionTreeTrainer.train takes"""
+        r = self.rows()
+        ids = np.nonzero(r[:, 0] != 0)[0]
+        return ids, np.ascontiguousarray(r[ids, 0]), np.ascontiguousarray(r[ids, 1:])
+
+
+class DecisionTreeTrainer:
+    """Cart::DecisionTreeTrainer with StateTyingDecisionTreeTrainer::LogLikelihoodGain: the sums of every (node, question) on the device,
+    the tree logic as the reference writes it.  The questions stay with the caller: `answers` holds question(properties of example) == TRUE
+    for every question and example, as a bool matrix [Q x E] or packed by pack_answers."""
+
+    ACTIONS = {"split": _lib.AMX_CART_SPLIT, "partition": _lib.AMX_CART_PARTITION, "cluster": _lib.AMX_CART_CLUSTER}
+
+    def __init__(self, ctx, max_leaves=0xffffffff, variance_clipping=0.0, exact_all=False):
+        self.L, self.ctx = _lib.lib(), ctx
+        self.max_leaves, self.variance_clipping, self.exact_all = int(max_leaves), float(variance_clipping), bool(exact_all)
+
+    @staticmethod
+    def pack_answers(answers):
+        """bool [Q x E] -> uint32 [Q x ceil(E / 32)], bit (e & 31) of word e // 32"""
+        a = np.asarray(answers, dtype=bool)
+        q, e = a.shape
+        pad = np.zeros((q, (e + 31) // 32 * 32), np.uint8)
+        pad[:, :e] = a
+        return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little").view("<u4"))
+
+    @staticmethod
+    def kernel_shape(dim):
+        """(examples per LDS stage, questions per workgroup) of the split search for this dimension"""
+        s, q = C.c_int(), C.c_int()
+        _lib.lib().amx_cart_kernel_shape(int(dim), C.addressof(s), C.addressof(q))
+        return s.value, q.value
+
+    def train(self, n_obs, values, answers, steps):
+        """n_obs [E] f64, values [E x 2 dim] f64 (sum, then sumSq), answers as above; steps: dicts with action ("split" | "partition" |
+        "cluster"), questions (rows of answers), and optionally min_obs, min_gain, randomize.  Returns a dict: nodes (in `order`), classes,
+        log, question_stats (structured arrays) and the fields of amx_cart_info."""
+        n_obs = np.ascontiguousarray(n_obs, np.float64)
+        values = np.ascontiguousarray(values, np.float64)
+        E = len(n_obs)
+        if values.ndim != 2 or values.shape[0] != E or values.shape[1] % 2:
+            raise ValueError("DecisionTreeTrainer.train: values must be [%d x 2 dim]" % E)
+        answers = np.asarray(answers)
+        bits = self.pack_answers(answers) if answers.dtype == bool else np.ascontiguousarray(answers, np.uint32)
+        if bits.ndim != 2 or bits.shape[1] != (E + 31) // 32:
+            raise ValueError("DecisionTreeTrainer.train: answers must be [Q x %d] words" % ((E + 31) // 32))
+        keep, arr = [], (_lib.CartStep * max(len(steps), 1))()
+        for i, st in enumerate(steps):
+            unknown = set(st) - {"action", "questions", "min_obs", "min_gain", "randomize"}
+            if unknown:
+                raise TypeError("DecisionTreeTrainer.train: step %d: unknown field %r" % (i, sorted(unknown)[0]))
+            q = np.ascontiguousarray(st["questions"], np.int32)
+            keep.append(q)
+            action = self.ACTIONS.get(st["action"], st["action"]) if isinstance(st["action"], str) else st["action"]
+            if isinstance(action, str):
+                raise ValueError("DecisionTreeTrainer.train: step %d: unknown action %r" % (i, action))
+            arr[i] = _lib.CartStep(int(action), int(st.get("min_obs", 0)), float(st.get("min_gain", 0.0)), int(st.get("randomize", 1)), len(q), q.ctypes.data)
+        pb = _lib.CartProblem(E, values.shape[1] // 2, bits.shape[0], n_obs.ctypes.data, values.ctypes.data, bits.ctypes.data)
+        plan = _lib.CartPlan(self.max_leaves, len(steps), C.cast(arr, C.c_void_p), self.variance_clipping, int(self.exact_all))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_cart_train(self.ctx.h if self.ctx is not None else None, C.byref(pb), C.byref(plan), C.byref(h)))
+        try:
+            info = _lib.CartInfo()
+            _lib.check(self.L.amx_cart_tree_info(h, C.byref(info)))
+            nodes = np.zeros(info.n_nodes, np.dtype(_lib.CartNode))
+            classes = np.zeros(info.n_examples, np.int32)
+            log = np.zeros(info.n_commits, np.dtype(_lib.CartCommit))
+            qstats = np.zeros(info.n_question_stats, np.dtype(_lib.CartQstat))
+            _lib.check(self.L.amx_cart_tree_get(h, nodes.ctypes.data, classes.ctypes.data, log.ctypes.data, qstats.ctypes.data))
+        finally:
+            self.L.amx_cart_tree_destroy(h)
+        out = dict(nodes=nodes, classes=classes, log=log, question_stats=qstats)
+        out.update({k: getattr(info, k) for k, _ in _lib.CartInfo._fields_})
+        return out
+
+
 class BaumWelchAligner:
     """Search::Aligner in mode baum-welch for a batch of segments whose [frames x emissions] score matrix is on the device: forward
     search with pruning, f64 forward-backward over the survivors, and per frame the list of (label, emission index, posterior weight).

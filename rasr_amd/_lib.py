@@ -129,6 +129,40 @@ class LinsegModels(C.Structure):
                 ("silence_emission", C.c_int)]
 
 
+class CartProblem(C.Structure):
+    _fields_ = [("n_examples", C.c_int), ("dim", C.c_int), ("n_questions", C.c_int), ("n_obs", C.c_void_p), ("values", C.c_void_p), ("answers", C.c_void_p)]
+
+
+class CartStep(C.Structure):
+    _fields_ = [("action", C.c_int), ("min_obs", C.c_uint), ("min_gain", C.c_double), ("randomize", C.c_int), ("n_questions", C.c_int),
+                ("questions", C.c_void_p)]
+
+
+class CartPlan(C.Structure):
+    _fields_ = [("max_leaves", C.c_uint), ("n_steps", C.c_int), ("steps", C.c_void_p), ("variance_clipping", C.c_double), ("exact_all", C.c_int)]
+
+
+class CartNode(C.Structure):
+    _fields_ = [("step", C.c_int), ("row", C.c_int), ("left", C.c_int), ("right", C.c_int), ("depth", C.c_uint), ("n_obs", C.c_uint),
+                ("score", C.c_double), ("class_id", C.c_int)]
+
+
+class CartCommit(C.Structure):
+    _fields_ = [("node", C.c_int), ("step", C.c_int), ("row", C.c_int), ("depth", C.c_uint), ("gain", C.c_double), ("total_gain", C.c_double)]
+
+
+class CartQstat(C.Structure):
+    _fields_ = [("step", C.c_int), ("row", C.c_int), ("count", C.c_uint), ("min_gain", C.c_double), ("sum_gain", C.c_double), ("max_gain", C.c_double),
+                ("min_depth", C.c_uint), ("sum_depth", C.c_uint), ("max_depth", C.c_uint)]
+
+
+class CartInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_int), ("n_leaves", C.c_int), ("n_commits", C.c_int), ("n_question_stats", C.c_int), ("n_examples", C.c_int),
+                ("n_obs", C.c_uint), ("initial_score", C.c_double), ("total_gain", C.c_double), ("negative_gain_errors", C.c_ulonglong),
+                ("items_screened", C.c_ulonglong), ("items_reevaluated", C.c_ulonglong), ("launches", C.c_ulonglong)]
+
+
+AMX_CART_SPLIT, AMX_CART_PARTITION, AMX_CART_CLUSTER = range(3)
 (AMX_LINSEG_OK, AMX_LINSEG_TOO_SHORT, AMX_LINSEG_TOO_LONG, AMX_LINSEG_NO_STATES, AMX_LINSEG_JUMP, AMX_LINSEG_MISMATCH, AMX_LINSEG_NONFINITE,
  AMX_LINSEG_N_REASONS) = range(8)
 AMX_BW_MAX_LABELS = 4096
@@ -367,6 +401,13 @@ SIGNATURES = {
     "amx_linseg_destroy": (None, [_P]),
     "amx_linseg_align_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(LinsegModels), _P, C.c_int, _P, _P, _P, _P]),
     "amx_linseg_chains": (C.c_int, [_P, C.c_int, _P, _P]),
+    "amx_cart_accumulator_size": (C.c_size_t, [C.c_int, C.c_int]),
+    "amx_cart_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    "amx_cart_train": (C.c_int, [_P, C.POINTER(CartProblem), C.POINTER(CartPlan), C.POINTER(_P)]),
+    "amx_cart_tree_destroy": (None, [_P]),
+    "amx_cart_tree_info": (C.c_int, [_P, C.POINTER(CartInfo)]),
+    "amx_cart_tree_get": (C.c_int, [_P, _P, _P, _P, _P]),
+    "amx_cart_kernel_shape": (None, [C.c_int, _P, _P]),
     "amx_quanteq_default_cfg": (None, [C.POINTER(QuanteqCfg)]),
     "amx_quanteq_create": (C.c_int, [_P, C.c_int, C.POINTER(QuanteqCfg), _P, C.POINTER(_P)]),
     "amx_quanteq_destroy": (None, [_P]),
