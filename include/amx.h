@@ -1823,6 +1823,100 @@ int  amx_nntrain_get_activation_statistics(amx_nntrain* h, int layer, float* mea
  * batch included (their inputs were packed as zeros).  T <= the frames of that pass. */
 int  amx_nntrain_get_layer_input(amx_nntrain* h, int layer, int T, float* X);
 
+/* ------------------------------------------------------------------ constrained MLLR (CMLLR), one affine feature transform per key */
+
+/* Speech::AffineFeatureTransformEstimator over Mm::AffineFeatureTransformAccumulator (Mm/AffineFeatureTransformAccumulator.cc): the
+ * corpus pass on the device (cmllr.hip), files / combine / estimate / score on the host (cmllr_host.cpp, no device needed), and the
+ * application of the transforms with the key chosen per segment.  Criteria naive and mmi-prime; hlda is refused.
+ *
+ * A handle is created on an amx_gmm handle, which supplies means, diagonal variances, the density -> (mean, covariance) indices and
+ * nCovariances.  feature_dim F is the width of the accumulated stream, model_dim M the model's dimension; F >= M (F < M is refused),
+ * F <= 255, n_keys <= 65535 (a key is one row of the kernels' grid; AMX_ERR_UNSUPPORTED beyond), at most 2^30 frames per call.  The gmm
+ * handle must outlive the cmllr handle.
+ *
+ * The accumulator is ONE flat f64 buffer the caller owns and zeroes, amx_cmllr_accumulator_size(h) doubles; per key, with R = F + 1
+ * and `tri` = R (R + 1) / 2 the row-major UPPER triangle (j <= k) of an R x R matrix:
+ *     [beta | k: M x R | mean: R | cov: tri | G: M x tri]
+ * G only when the model has more than one covariance (amx_cmllr_shape.pooled == 0); a pooled model keeps its variance vector and
+ * finalize derives G from cov (:124-133).  Ranks combine the buffer with amx_comm_all_reduce_f64_dev.
+ *
+ * Arithmetic of one frame x (f32, xi = [1, x] widened to f64) aligned to density d with mean m, variance v (f32, widened), :40-121:
+ *     beta += 1 | w;  k[i][j] += m_i / v_i * xi_j [* w];  mean[j] += xi_j [* w];  cov[j][k] += xi_j * xi_k [* w];
+ *     G[i][j][k] += xi_j * xi_k / v_i [* w]           (left to right, the division is an IEEE division, no reciprocal)
+ * amx_set_contract(AMX_CONTRACT_FMA) makes the last multiplication of each `+= a * b` one fused multiply-add with the addition, the
+ * sites the reference's -march=native build contracts (tests/golden/ref_cmllr.npz holds both builds).  Per (key, cell) the sum is
+ * ONE chain over the key's frames in ascending frame order that continues from the value in the buffer: no floating-point atomics,
+ * nothing depends on the launch shape, and a corpus fed in order and cut into calls anywhere gives the same bits. */
+typedef struct amx_cmllr amx_cmllr;
+typedef struct {
+    int feature_dim, model_dim, n_keys;
+    int pooled;            /* 1: the model has ONE covariance, no G block */
+} amx_cmllr_shape;
+int  amx_cmllr_create(amx_gmm* gmm, int feature_dim, int n_keys, amx_cmllr** out);
+void amx_cmllr_destroy(amx_cmllr* h);
+/* shape (nullable) and, for a pooled model, the variance vector [model_dim] (nullable; untouched otherwise) */
+int  amx_cmllr_describe(const amx_cmllr* h, amx_cmllr_shape* shape, float* pooled_variance);
+long amx_cmllr_accumulator_size(const amx_cmllr* h);                 /* doubles, all keys; 0 for NULL */
+long amx_cmllr_key_size(const amx_cmllr_shape* shape);               /* doubles of ONE key; 0 for a bad shape */
+/* frames per LDS stage, cells of the triangle per workgroup and model components per workgroup of the G kernel (any pointer nullable) */
+void amx_cmllr_kernel_shape(int* stage_frames, int* tile_cells, int* tile_components);
+/* Kernel selection for A/B runs and tests: the G kernel with 16 (default) or 48 model components per workgroup and lane -- 48 is the shape
+ * in which a lane keeps all accumulators of a 45-dimensional model.  Both give the same bits (tests/test_cmllr_gpu.py); DESIGN.md
+ * section 4.18 has their times.  Any other value: AMX_ERR_INVALID. */
+int  amx_cmllr_set_tile(amx_cmllr* h, int tile_components);
+/* feats_dev [frame x feats_ld] (feats_ld >= F); segment s covers frames [frame_offsets[s], frame_offsets[s + 1]) and adds to key
+ * seg_key[s] (both host arrays); emission_dev[t] int32 as the aligners leave it, -1 skips the frame; the density is
+ * best_density_dev[t * best_density_ld + emission] or best_density_dev[t] when best_density_ld == 0 (amx_gmm_accumulate_dev's
+ * convention); weight_dev nullable f64 (a weight of exactly 0 still adds its zeros, as the reference does).
+ * Checked on the device BEFORE anything is written: an emission index outside the model other than -1, a density outside its
+ * mixture, a non-finite feature or weight -- AMX_ERR_INVALID naming the first such frame, acc_dev untouched.  Refused on the host: a
+ * key outside [0, n_keys), decreasing offsets, NULL buffers where there are frames.  Waits for the stream. */
+int  amx_cmllr_accumulate_dev(amx_cmllr* h, const float* feats_dev, int feats_ld, int n_seg, const long* frame_offsets, const int* seg_key,
+                              const int32_t* emission_dev, const uint32_t* best_density_dev, int best_density_ld, const double* weight_dev,
+                              double* acc_dev);
+/* y = A_key [1, x] per frame without materialising [1, x]: transforms_dev [n_keys x M x (F + 1)] f32, has_transform [n_keys] (host;
+ * 0: the key's segments get the identity rows y_i = x_i, what estimate's early return gives, and *n_identity_segments (nullable)
+ * counts them).  The dot product is amx_matrix_multiply_dev's (k ascending from the offset column, fused under AMX_CONTRACT_FMA): the
+ * result equals that entry point run per segment on the extended features in every bit.  Overlapping views are rejected. */
+int  amx_cmllr_apply_dev(amx_ctx* ctx, const float* transforms_dev, const int* has_transform, int n_keys, int model_dim, int feature_dim,
+                         const float* in_dev, int in_ld, int n_seg, const long* frame_offsets, const int* seg_key, float* out_dev, int out_ld,
+                         int* n_identity_segments);
+
+/* ---- host side (cmllr_host.cpp): `acc` is ONE key's part of the flat buffer, amx_cmllr_key_size(shape) doubles, host memory;
+ * pooled_variance [M] f32 is read when shape->pooled (amx_cmllr_describe). */
+/* The reference's binary accumulator behind Core::IoRef's type-name tag (Core/IoRef.hh:119-122, :367-377), little endian:
+ *   u32 36 "affine-feature-transform-accumulator" | u32 F | u32 M | f64 beta | vector<Matrix<f64>> G | vector<Vector<f64>> k |
+ *   Vector<f64> mean | Matrix<f64> cov | vector<f32> globalModelVariance | u8 globalVarianceOptimization (0xff | 0)
+ * as the accumulating pass leaves it: upper triangles filled, lower ones zero; a pooled model's G matrices are 0 x 0.
+ * read: the file's F, M and pooled flag must equal the shape's (and its variance vector pooled_variance); a wrong tag, a truncated
+ * file or a G / cov with a non-zero lower triangle (a finalized accumulator) is AMX_ERR_INVALID. */
+int  amx_cmllr_accumulator_write(const amx_cmllr_shape* shape, const float* pooled_variance, const double* acc, const char* path);
+int  amx_cmllr_accumulator_read(const amx_cmllr_shape* shape, const float* pooled_variance, const char* path, double* acc);
+/* combine (:345-365): acc += other * weight, member by member; its verify()s as errors (dimensions, pooled against non-pooled, unequal
+ * variance vectors) */
+int  amx_cmllr_combine(const amx_cmllr_shape* shape, const float* pooled_variance, double* acc, const amx_cmllr_shape* other_shape,
+                       const float* other_variance, const double* other_acc, double weight);
+enum { AMX_CMLLR_NAIVE = 0, AMX_CMLLR_MMI_PRIME = 1, AMX_CMLLR_HLDA = 2 };
+/* finalize (:123-143) + estimate (:177-311), operation by operation in f64, the inverse by an LU with partial pivoting (the reference
+ * calls dgetrf / dgetri; see DESIGN.md section 4.18 for the measured distance).  initial: nullable (identity, :169-174), M x
+ * initial_cols with initial_cols == F (a zero column is put in front) or F + 1.  transform_out [M x (F + 1)] f32; transform64_out
+ * (nullable) the same before the narrowing; iterations_out (nullable) [iterations x M x (F + 1)] f64 the transform after every
+ * iteration (mmi-prime).  *estimated (nullable) = 0 when beta < min_obs_weight returned the initial transform (:204-205).
+ * AMX_CMLLR_HLDA: AMX_ERR_UNSUPPORTED.  A singular G or pseudo-inverse: AMX_ERR_INVALID. */
+int  amx_cmllr_estimate(const amx_cmllr_shape* shape, const float* pooled_variance, const double* acc, int iterations, double min_obs_weight,
+                        int criterion, const float* initial, int initial_cols, float* transform_out, double* transform64_out,
+                        double* iterations_out, int* estimated);
+/* finalize + score (:313-343) of an M x (F + 1) f32 transform: jacobian - distance / beta */
+int  amx_cmllr_score(const amx_cmllr_shape* shape, const float* pooled_variance, const double* acc, const float* transform, int criterion,
+                     double* score_out);
+/* The transform file the estimator writes per key (`os << transform` on a Core::XmlOutputStream, Speech/AffineFeatureTransformEstimator.cc:
+ * 124-132; Math/Matrix.hh:641-647): the XML declaration, <matrix-f32 nRows nColumns>, one line per row with every value in scientific
+ * notation with six digits and a space behind it, the closing tag -- byte for byte the reference's (tests/golden/ref_cmllr.npz).  A
+ * non-finite element is refused.  read takes what an XML parser takes (declaration and comments in front, either quote, any white
+ * space) and is also how an `initial-transform` is read; *data: rows x cols floats, amx_free(). */
+int  amx_cmllr_transform_write(const char* path, int rows, int cols, const float* transform);
+int  amx_cmllr_transform_read(const char* path, int* rows, int* cols, float** data);
+
 #ifdef __cplusplus
 }
 #endif

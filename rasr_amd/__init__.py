@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -2233,3 +2233,195 @@ def mean_and_deviation(trainer, acc):
     mean, dev = np.zeros(trainer.feature_dim, np.float32), np.zeros(trainer.feature_dim, np.float32)
     _lib.check(trainer.L.amx_nnstat_mean_and_deviation(trainer.h, a.ctypes.data, mean.ctypes.data, dev.ctypes.data))
     return mean, dev
+
+
+_CMLLR_CRITERIA = {"naive": _lib.AMX_CMLLR_NAIVE, "mmi-prime": _lib.AMX_CMLLR_MMI_PRIME, "hlda": _lib.AMX_CMLLR_HLDA}
+
+
+class AffineFeatureTransformEstimator:
+    """Speech::AffineFeatureTransformEstimator over Mm::AffineFeatureTransformAccumulator (CMLLR): per key the flat f64 accumulator
+    [beta | k: M x (F + 1) | mean: F + 1 | cov: upper triangle of order F + 1 | G: M x that triangle (non-pooled models only)], its corpus
+    pass on the device, its files, combine, estimate and score.
+
+    With a GmmFeatureScorer created on a context the estimator accumulates; for host-only use (files, combine, estimate, score) pass
+    gmm=None and model_dim, and pooled_variance (f32 [model_dim]) when the model has one covariance."""
+
+    def __init__(self, gmm, feature_dim, n_keys=1, model_dim=None, pooled_variance=None):
+        self.L = _lib.lib()
+        self.gmm, self.h = gmm, None
+        self.shape = _lib.CmllrShape()
+        self.pooled_variance = None
+        if gmm is not None:
+            h = C.c_void_p()
+            _lib.check(self.L.amx_cmllr_create(gmm.h, int(feature_dim), int(n_keys), C.byref(h)))
+            self.h = h
+            _lib.check(self.L.amx_cmllr_describe(h, C.byref(self.shape), None))
+            if self.shape.pooled:
+                self.pooled_variance = np.zeros(self.shape.model_dim, np.float32)
+                _lib.check(self.L.amx_cmllr_describe(h, None, self.pooled_variance.ctypes.data))
+        else:
+            if pooled_variance is not None:
+                self.pooled_variance = np.ascontiguousarray(pooled_variance, dtype=np.float32)
+                model_dim = len(self.pooled_variance) if model_dim is None else model_dim
+            if model_dim is None:
+                raise ValueError("AffineFeatureTransformEstimator: without a scorer, model_dim or pooled_variance says what the model's dimension is")
+            self.shape = _lib.CmllrShape(int(feature_dim), int(model_dim), int(n_keys), 0 if pooled_variance is None else 1)
+            if self.key_size() == 0:   # the shape is refused: let the library say why
+                _lib.check(self.L.amx_cmllr_score(C.byref(self.shape), None, None, None, 0, None))
+        self.feature_dim, self.model_dim, self.n_keys, self.pooled = self.shape.feature_dim, self.shape.model_dim, self.shape.n_keys, bool(self.shape.pooled)
+
+    def close(self):
+        if self.h:
+            self.L.amx_cmllr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def key_size(self):
+        """doubles of ONE key's part of the accumulator (0: the shape is refused)"""
+        return int(self.L.amx_cmllr_key_size(C.byref(self.shape)))
+
+    def accumulator_size(self):
+        return self.key_size() * self.n_keys
+
+    @staticmethod
+    def kernel_shape():
+        """(frames per LDS stage, triangle cells per workgroup, model components per workgroup) of the G kernel"""
+        s, c, m = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_cmllr_kernel_shape(C.byref(s), C.byref(c), C.byref(m))
+        return s.value, c.value, m.value
+
+    def set_tile(self, tile_components):
+        """A/B runs and tests: the G kernel with 16 (default) or 48 model components per workgroup; the same bits either way"""
+        if self.h is None:
+            raise RuntimeError("AffineFeatureTransformEstimator.set_tile: created without a scorer")
+        _lib.check(self.L.amx_cmllr_set_tile(self.h, int(tile_components)))
+
+    def accumulate_dev(self, feats_dev, feats_ld, frame_offsets, seg_key, emission_dev, best_density_dev, acc_dev, best_density_ld=0, weight_dev=None):
+        """add the segments' frames to their keys: emission_dev int32 (-1 skips a frame), best_density_dev u32 (matrix with best_density_ld
+        columns, or one per frame with 0), weight_dev f64 or None, acc_dev f64 [accumulator_size()]"""
+        if self.h is None:
+            raise RuntimeError("AffineFeatureTransformEstimator.accumulate_dev: created without a scorer")
+        off = _offsets(frame_offsets, "AffineFeatureTransformEstimator.accumulate_dev")
+        keys = np.ascontiguousarray(seg_key, dtype=np.int32)
+        if len(keys) != len(off) - 1:
+            raise ValueError("seg_key holds %d keys for %d segments" % (len(keys), len(off) - 1))
+        _lib.check(self.L.amx_cmllr_accumulate_dev(self.h, _ptr(feats_dev), int(feats_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(emission_dev),
+                                                   _ptr(best_density_dev), int(best_density_ld), _ptr(weight_dev), _ptr(acc_dev)))
+
+    def _key(self, acc_host, key):
+        a = np.ascontiguousarray(acc_host, dtype=np.float64).reshape(-1)
+        n = self.key_size()
+        if a.size == n and key in (0, None):
+            return a
+        if a.size != n * self.n_keys or key is None or not 0 <= key < self.n_keys:
+            raise ValueError("accumulator has %d entries (%d per key, %d keys), key %r" % (a.size, n, self.n_keys, key))
+        return a[key * n:(key + 1) * n]
+
+    def members(self, acc_host, key=0):
+        """dict(beta, k [M, F+1], mean [F+1], cov [F+1, F+1] upper triangle, G [M, F+1, F+1] upper triangles or None) of one key"""
+        a, M, R = self._key(acc_host, key), self.model_dim, self.feature_dim + 1
+        iu = np.triu_indices(R)
+        tri = len(iu[0])
+        out = dict(beta=a[0], k=a[1:1 + M * R].reshape(M, R).copy(), mean=a[1 + M * R:1 + M * R + R].copy(), G=None)
+        p = 1 + M * R + R
+        cov = np.zeros((R, R))
+        cov[iu] = a[p:p + tri]
+        out["cov"] = cov
+        if not self.pooled:
+            G = np.zeros((M, R, R))
+            for i in range(M):
+                G[i][iu] = a[p + tri * (i + 1):p + tri * (i + 2)]
+            out["G"] = G
+        return out
+
+    def write(self, acc_host, path, key=0):
+        """one key's accumulator as the reference's binary accumulator file (type tag first)"""
+        a = self._key(acc_host, key)
+        _lib.check(self.L.amx_cmllr_accumulator_write(C.byref(self.shape), _ptr(self.pooled_variance), a.ctypes.data, os.fsencode(path)))
+
+    def read(self, path):
+        """accumulator file -> one key's flat accumulator; the file must be of this estimator's shape"""
+        n = self.key_size()
+        a = np.zeros(max(n, 1), np.float64)
+        _lib.check(self.L.amx_cmllr_accumulator_read(C.byref(self.shape), _ptr(self.pooled_variance), os.fsencode(path), a.ctypes.data))
+        return a[:n]
+
+    def combine(self, acc_host, other, other_acc, weight=1.0, key=0, other_key=0):
+        """combine(other, weight): a copy of this key's accumulator plus weight times the other estimator's"""
+        a = self._key(acc_host, key).copy()
+        b = other._key(other_acc, other_key)
+        _lib.check(self.L.amx_cmllr_combine(C.byref(self.shape), _ptr(self.pooled_variance), a.ctypes.data, C.byref(other.shape),
+                                            _ptr(other.pooled_variance), b.ctypes.data, float(weight)))
+        return a
+
+    def estimate(self, acc_host, key=0, iterations=10, min_observation_weight=2000.0, criterion="mmi-prime", initial=None, details=False):
+        """finalize + estimate: the transform f32 [M, F + 1]; details=True: (transform, dict(estimated, transform64, iterations))"""
+        a, M, R = self._key(acc_host, key), self.model_dim, self.feature_dim + 1
+        ini, cols = None, 0
+        if initial is not None:
+            ini = np.ascontiguousarray(initial, dtype=np.float32)
+            if ini.ndim != 2 or ini.shape[0] != M:
+                raise ValueError("the initial transform must have %d rows" % M)
+            cols = ini.shape[1]
+        out, out64 = np.zeros((M, R), np.float32), np.zeros((M, R), np.float64)
+        its = np.zeros((max(int(iterations), 0), M, R), np.float64)
+        est = C.c_int(0)
+        _lib.check(self.L.amx_cmllr_estimate(C.byref(self.shape), _ptr(self.pooled_variance), a.ctypes.data, int(iterations), float(min_observation_weight),
+                                             _CMLLR_CRITERIA[criterion], _ptr(ini), cols, out.ctypes.data, out64.ctypes.data,
+                                             its.ctypes.data if its.size else None, C.byref(est)))
+        return (out, dict(estimated=bool(est.value), transform64=out64, iterations=its)) if details else out
+
+    def score(self, acc_host, transform, key=0, criterion="mmi-prime"):
+        a = self._key(acc_host, key)
+        t = np.ascontiguousarray(transform, dtype=np.float32)
+        if t.shape != (self.model_dim, self.feature_dim + 1):
+            raise ValueError("the transform must be [%d, %d]" % (self.model_dim, self.feature_dim + 1))
+        s = C.c_double()
+        _lib.check(self.L.amx_cmllr_score(C.byref(self.shape), _ptr(self.pooled_variance), a.ctypes.data, t.ctypes.data, _CMLLR_CRITERIA[criterion], C.byref(s)))
+        return s.value
+
+
+def write_transform(path, transform):
+    """a transform f32 [rows, columns] as the XML matrix file the reference's estimator writes per key (`transform-directory`)"""
+    t = np.ascontiguousarray(transform, dtype=np.float32)
+    if t.ndim != 2:
+        raise ValueError("write_transform: a matrix is wanted")
+    _lib.check(_lib.lib().amx_cmllr_transform_write(os.fsencode(path), t.shape[0], t.shape[1], t.ctypes.data))
+
+
+def read_transform(path):
+    """XML matrix file (a key's transform, an `initial-transform`) -> f32 [rows, columns]"""
+    L = _lib.lib()
+    r, c, p = C.c_int(), C.c_int(), C.c_void_p()
+    _lib.check(L.amx_cmllr_transform_read(os.fsencode(path), C.byref(r), C.byref(c), C.byref(p)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(r.value, c.value)).copy()
+    finally:
+        L.amx_free(p)
+
+
+class AffineFeatureTransform:
+    """the application of CMLLR transforms: y = A_key [1, x] with the key chosen per segment inside one launch; a key without a
+    transform passes its segments through (the first model_dim components)"""
+
+    def __init__(self, ctx, model_dim, feature_dim, n_keys):
+        self.ctx, self.L = ctx, ctx.L
+        self.model_dim, self.feature_dim, self.n_keys = int(model_dim), int(feature_dim), int(n_keys)
+
+    def apply_dev(self, transforms_dev, has_transform, frame_offsets, seg_key, in_dev, in_ld, out_dev, out_ld):
+        """transforms_dev f32 [n_keys, model_dim, feature_dim + 1] on the device, has_transform [n_keys] on the host; returns the number of
+        segments that got the identity"""
+        off = _offsets(frame_offsets, "AffineFeatureTransform.apply_dev")
+        keys = np.ascontiguousarray(seg_key, dtype=np.int32)
+        has = np.ascontiguousarray(has_transform, dtype=np.int32)
+        if len(keys) != len(off) - 1 or len(has) != self.n_keys:
+            raise ValueError("seg_key holds %d keys for %d segments, has_transform %d flags for %d keys" % (len(keys), len(off) - 1, len(has), self.n_keys))
+        n = C.c_int(0)
+        _lib.check(self.L.amx_cmllr_apply_dev(self.ctx.h, _ptr(transforms_dev), has.ctypes.data, self.n_keys, self.model_dim, self.feature_dim, _ptr(in_dev),
+                                              int(in_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(out_dev), int(out_ld), C.byref(n)))
+        return n.value

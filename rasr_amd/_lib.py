@@ -163,6 +163,10 @@ class CartInfo(C.Structure):
 
 
 AMX_CART_SPLIT, AMX_CART_PARTITION, AMX_CART_CLUSTER = range(3)
+
+
+class CmllrShape(C.Structure):
+    _fields_ = [("feature_dim", C.c_int), ("model_dim", C.c_int), ("n_keys", C.c_int), ("pooled", C.c_int)]
 (AMX_LINSEG_OK, AMX_LINSEG_TOO_SHORT, AMX_LINSEG_TOO_LONG, AMX_LINSEG_NO_STATES, AMX_LINSEG_JUMP, AMX_LINSEG_MISMATCH, AMX_LINSEG_NONFINITE,
  AMX_LINSEG_N_REASONS) = range(8)
 AMX_BW_MAX_LABELS = 4096
@@ -503,7 +507,24 @@ SIGNATURES = {
     "amx_nntrain_get_step_statistics": (C.c_int, [_P, C.c_int, _P, _P]),
     "amx_nntrain_get_activation_statistics": (C.c_int, [_P, C.c_int, _P, _P]),
     "amx_nntrain_get_layer_input": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "amx_cmllr_create": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
+    "amx_cmllr_destroy": (None, [_P]),
+    "amx_cmllr_describe": (C.c_int, [_P, C.POINTER(CmllrShape), _P]),
+    "amx_cmllr_accumulator_size": (C.c_long, [_P]),
+    "amx_cmllr_key_size": (C.c_long, [C.POINTER(CmllrShape)]),
+    "amx_cmllr_kernel_shape": (None, [_P, _P, _P]),
+    "amx_cmllr_set_tile": (C.c_int, [_P, C.c_int]),
+    "amx_cmllr_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "amx_cmllr_apply_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "amx_cmllr_accumulator_write": (C.c_int, [C.POINTER(CmllrShape), _P, _P, C.c_char_p]),
+    "amx_cmllr_accumulator_read": (C.c_int, [C.POINTER(CmllrShape), _P, C.c_char_p, _P]),
+    "amx_cmllr_combine": (C.c_int, [C.POINTER(CmllrShape), _P, _P, C.POINTER(CmllrShape), _P, _P, C.c_double]),
+    "amx_cmllr_estimate": (C.c_int, [C.POINTER(CmllrShape), _P, _P, C.c_int, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "amx_cmllr_score": (C.c_int, [C.POINTER(CmllrShape), _P, _P, _P, C.c_int, _P]),
+    "amx_cmllr_transform_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P]),
+    "amx_cmllr_transform_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
 }
+AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
 AMX_COMM_ID_BYTES = 128
 
 _lib = None

@@ -2312,6 +2312,15 @@ int amx_gmm_topology(const amx_gmm* h, int* n_entries, uint32_t* mix_offsets, ui
     return AMX_OK;
 }
 
+int amx_internal_gmm_view_get(const amx_gmm* h, amx_internal_gmm_view* v) {
+    AMX_REQUIRE(h && v, AMX_ERR_INVALID, "amx_internal_gmm_view_get: NULL argument");
+    v->ctx = h->ctx, v->dim = h->dim, v->n_mix = h->n_mix, v->n_dens = h->n_dens, v->n_mean = h->n_mean, v->n_cov = h->n_cov;
+    v->d_mix_off = h->d_mix_off.get(), v->d_k_dens = h->d_k_dens.get(), v->d_d_mean = h->d_d_mean.get(), v->d_d_cov = h->d_d_cov.get();
+    v->d_means = h->d_means.get();
+    v->h_vars  = h->h_vars.empty() ? nullptr : h->h_vars.data();
+    return AMX_OK;
+}
+
 int amx_gmm_tables(const amx_gmm* h, float* m2lw, float* isr, float* lognorm) {
     AMX_REQUIRE(h, AMX_ERR_INVALID, "amx_gmm_tables: NULL handle");
     if (m2lw)

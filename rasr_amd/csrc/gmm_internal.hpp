@@ -49,6 +49,17 @@ int amx_internal_gmm_fused_score(amx_ctx* ctx, int dim, const void* rec_dev, con
                                  int contract_fma, float na_all);
 int amx_internal_gmm_fused_waves(int Tpad, int forced_waves);
 
+// gmm.hip: what an estimator built on a scorer handle reads of it (cmllr.hip).  The pointers live as long as the handle; the device ones
+// and h_vars ([n_cov x dim], host) are NULL for a host-only handle
+struct amx_internal_gmm_view {
+    amx_ctx*        ctx;
+    int             dim, n_mix, n_dens, n_mean, n_cov;
+    const uint32_t *d_mix_off, *d_k_dens, *d_d_mean, *d_d_cov;
+    const float*    d_means;   // [n_mean x dim]
+    const float*    h_vars;
+};
+int amx_internal_gmm_view_get(const amx_gmm* h, amx_internal_gmm_view* out);
+
 // ffnn.hip: combine per-tile arg-min partials [n_tiles x part_ld] (shared with the NN scorer's fused statistics)
 int amx_internal_best_state_reduce(amx_ctx* ctx, const float* part_min, const unsigned* part_idx, int n_tiles, int part_ld, int T,
                                    uint32_t* best_state_dev, unsigned long long* counts_dev, double* score_sum_dev);
