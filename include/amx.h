@@ -1917,6 +1917,113 @@ int  amx_cmllr_score(const amx_cmllr_shape* shape, const float* pooled_variance,
 int  amx_cmllr_transform_write(const char* path, int rows, int cols, const float* transform);
 int  amx_cmllr_transform_read(const char* path, int* rows, int* cols, float** data);
 
+/* ------------------------------------------------------------------ MLLR, mean transforms per key and regression class */
+
+/* Speech::ModelTransformEstimator over Mm::FullAdaptorViterbiEstimator / Mm::ShiftAdaptorViterbiEstimator (Mm/MllrAdaptation.cc): the
+ * corpus pass on the device (mllr.hip), files and the estimate on the host (mllr_host.cpp, no device needed), and the adapted mean
+ * table of one key on the device.  Modes full and shift; band and semi-tied (MODULE_ADAPT_ADVANCED) are refused.
+ *
+ * A handle is created on an amx_gmm handle (which must outlive it).  leaf_of_mixture [n_mixtures] is the reference's leafIndex_ AS
+ * MllrAdaptation.cc INDEXES IT, with the mixture index (Am/AdaptationTree.cc:95-99 appends the silence class), every value in
+ * [0, n_leafs).  Limits: dimension D <= 255, n_keys <= 65535, n_leafs <= 4096 (the compaction kernel keeps a counter per leaf in
+ * LDS; the reference's default is 70 + 1); AMX_ERR_UNSUPPORTED beyond, and for a model in which two (mixture, density) visits reach
+ * the same mean (adaptMixtureSet would transform it twice, :147-148).  At most 2^30 frames per call.
+ *
+ * The accumulator is ONE flat f64 buffer the caller owns and zeroes, amx_mllr_accumulator_size(h) doubles, [key][leaf][cells]:
+ *     full:   [count_Z | Z: D x (D + 1) | count_G | G: (D + 1) x (D + 1)]      (all of G, both triangles, both counts)
+ *     shift:  [count | beta: D | shift: D]
+ * Ranks may all-reduce the buffer (amx_comm_all_reduce_f64_dev); the reference has no combine for these classes
+ * (AbstractAdaptationAccumulator::combine is defect()), so such sums are outside the bit-parity claim.
+ *
+ * Arithmetic of one frame x (f32) aligned to a density with mean m and variance v (f32), mt = [1, m] widened to f64:
+ *     full (:599-653):   count_Z++, count_G++ (frames, also in the weighted overload);
+ *                        Z[i][j] += x_i * mt_j           | (w * x_i) * mt_j
+ *                        G[i][j] += mt_i * mt_j          | (w * mt_i) * mt_j
+ *     shift (:381-416):  count += 1 | w;   beta[d] += 1.0 / v_d | w / v_d   (f64 divisions)
+ *                        shift[d] += f64((x_d - m_d) / v_d)   (f32 subtraction and division)   |   w * f64(x_d - m_d) / v_d
+ * The unweighted products are exact in f64, so both contract modes give the same bits; in the weighted full form
+ * AMX_CONTRACT_FMA fuses Z's last product with the addition, as the reference's -march=native build does; that build leaves G's
+ * product and addition apart, and so does the library in both modes (tests/golden/ref_mllr.npz holds both builds).  Per (key, leaf, cell) the sum is ONE chain over that key's frames of that leaf in
+ * ascending frame order that continues from the value in the buffer: no floating-point atomics, no partial sums, nothing depends on
+ * the launch shape, and a corpus fed in order and cut into calls anywhere gives the same bits. */
+typedef struct amx_mllr amx_mllr;
+enum { AMX_MLLR_FULL = 0, AMX_MLLR_SHIFT = 1, AMX_MLLR_BAND = 2, AMX_MLLR_SEMI_TIED = 3 };
+typedef struct {
+    int mode, dim, n_leafs, n_keys;
+} amx_mllr_shape;
+/* The pruned Core::BinaryTree (Core/BinaryTree.hh) over node ids 0 .. n_ids - 1, n_ids = numberOfNodes + numberOfLeafs: left / right
+ * / previous per id (-1 = invalidId), leaf_number per id (-1 for an inner node), the leaf list as node ids in leafList() order, the
+ * silence mixtures ascending (std::set order). */
+typedef struct {
+    int        n_ids, root;
+    const int *left, *right, *previous, *leaf_number;
+    int        n_leaf_list;
+    const int* leaf_list;
+    int        n_silence;
+    const int* silence_mixtures;
+} amx_mllr_tree;
+int  amx_mllr_create(amx_gmm* gmm, int mode, int n_keys, int n_leafs, const int* leaf_of_mixture, amx_mllr** out);
+void amx_mllr_destroy(amx_mllr* h);
+int  amx_mllr_describe(const amx_mllr* h, amx_mllr_shape* shape);
+long amx_mllr_accumulator_size(const amx_mllr* h);                  /* doubles, all keys; 0 for NULL */
+long amx_mllr_leaf_size(const amx_mllr_shape* shape);               /* doubles of ONE (key, leaf); 0 for a bad shape */
+long amx_mllr_key_size(const amx_mllr_shape* shape);                /* doubles of ONE key = n_leafs * leaf size */
+/* frames per LDS stage and cells per workgroup of the accumulation kernel (any pointer nullable) */
+void amx_mllr_kernel_shape(int* stage_frames, int* tile_cells);
+/* Arguments and device checks as amx_cmllr_accumulate_dev: feats_dev [frame x feats_ld]; segment s covers frames [frame_offsets[s],
+ * frame_offsets[s + 1]) of key seg_key[s]; emission_dev -1 skips the frame (the adapter sets it for alignment items below weight
+ * 0.5, which accumulate(alignment, ...) of the shift estimator skips, :424); best densities in either layout; weight_dev nullable.
+ * An emission outside the model, a density outside its mixture, a non-finite feature or weight: AMX_ERR_INVALID naming the first
+ * such frame, acc_dev untouched.  Waits for the stream. */
+int  amx_mllr_accumulate_dev(amx_mllr* h, const float* feats_dev, int feats_ld, int n_seg, const long* frame_offsets, const int* seg_key,
+                             const int32_t* emission_dev, const uint32_t* best_density_dev, int best_density_ld, const double* weight_dev,
+                             double* acc_dev);
+/* FullAdaptor::adaptMixtureSet / ShiftAdaptor::adaptMixtureSet(mixtureSet) (:59-79, :146-170) for one key: out_dev [n_means x D] f32.
+ * matrices (host, f64) [n_matrices x D x (D + 1)] (shift: [n_matrices x D]) with their ids, matrix_of_mixture [n_mixtures] as
+ * amx_mllr_estimate gives them.  full: per (mean, row) the f64 dot product over [1, m] in ascending column order, fused under
+ * AMX_CONTRACT_FMA, narrowed once; shift: f32(shift_d + f64(m_d)).  A mean no mixture reaches is copied.  A matrix id that is not
+ * among matrix_ids (the reference's ensure, :64 / :154): AMX_ERR_INVALID.  The caller builds the adapted scorer with amx_gmm_create. */
+int  amx_mllr_adapt_means_dev(amx_mllr* h, int n_matrices, const int* matrix_ids, const double* matrices, const int* matrix_of_mixture,
+                              float* out_dev);
+
+/* ---- host side (mllr_host.cpp): `acc` is ONE key's part of the flat buffer, amx_mllr_key_size(shape) doubles, host memory. */
+/* The reference's binary accumulator behind Core::IoRef's type-name tag, little endian (AdaptorEstimator::write :247-250, then
+ * :829-841 / :533-545; AccumulatorBase::write :279-287):
+ *   string tag | string clusterId | u32 dimension | Vector<f64> count_ | f64 min-observation | f64 min-silence-observation |
+ *   full:  Vector<ZAccumulator> | Vector<GAccumulator> (each Matrix<f64>, f64 count) | map<u16, Matrix<f64>> w_
+ *   shift: Vector<f64> count | Vector<Vector<f64>> beta | Vector<Vector<f64>> shift | map<u16, Matrix<f64>> shift_
+ * with tag "full-adaptor-viterbi-estimator" / "shift-adaptor-viterbi-estimator".  write gives the file of the accumulating pass:
+ * count_ empty (node_count NULL) or the n_ids counts of an estimate, the map as init() leaves it -- every id of map_ids (the tree's
+ * ids, ascending) with a 0 x 0 matrix (full) or a 1 x D zero row (shift).  read checks tag, dimension and leaf count against the
+ * shape, skips count_ and the map, and returns the two thresholds (nullable); a wrong tag, dimension or leaf count or a truncated
+ * file: AMX_ERR_INVALID. */
+int  amx_mllr_accumulator_write(const amx_mllr_shape* shape, const double* acc, const char* cluster_id, double min_observation,
+                                double min_silence_observation, int n_count, const double* node_count, int n_map_ids, const int* map_ids,
+                                const char* path);
+int  amx_mllr_accumulator_read(const amx_mllr_shape* shape, const char* path, double* acc, double* min_observation,
+                               double* min_silence_observation);
+enum { AMX_MLLR_ROOT_FALLBACK = 1, AMX_MLLR_SILENCE_FALLBACK = 2 };
+/* adaptor() (:741-827 / :444-531) for one key: propagate in the reference's recursion order (node = left, then += right; :228-248),
+ * count > min_observation (strict), per kept node W = Z * pinv(G) (Matrix * Matrix's loop; shift: shift / beta per component), every
+ * leaf of the leaf list walked up `previous` to the first node with enough observations, the root-only fallback to
+ * adaptationUnitMatrix / the zero shift, the silence mixtures from the LEAF accumulators against min_silence_observation, numbered
+ * from n_ids upward, and matrix_of_mixture [n_mixtures] = matrixId[leaf_of_mixture[mixture]].  pinv is Lapack::pseudoInvert's
+ * (Math/Lapack/Svd.cc:21-99, dgelsd with rcond 1e-12) by a cyclic Jacobi eigen-decomposition of the symmetrised G with the same
+ * truncation (|lambda| <= rcond * max |lambda| dropped); DESIGN.md section 4.19 has the measured distance.  rcond <= 0 takes 1e-12.
+ * Out: *n_matrices, matrix_ids ascending (as the std::map iterates) and matrices, room for n_leaf_list + n_silence + 1 of them;
+ * node_count [n_ids] (nullable); *flags (nullable).  A tree whose arrays do not describe a tree, a leaf number outside [0, n_leafs),
+ * a silence mixture outside the model: AMX_ERR_INVALID. */
+int  amx_mllr_estimate(const amx_mllr_shape* shape, const double* acc, const amx_mllr_tree* tree, int n_mixtures, const int* leaf_of_mixture,
+                       double min_observation, double min_silence_observation, double rcond, int* n_matrices, int* matrix_ids,
+                       double* matrices, int* matrix_of_mixture, double* node_count, int* flags);
+/* The adaptor file (FullAdaptor::write / ShiftAdaptor::write :172-177 / :121-126 behind the tag "full-adaptor" / "shift-adaptor"):
+ *   string tag | string clusterId | map<u16, Matrix<f64>> | Vector<u16> adaptationMatrixIndex
+ * read: capacity max_matrices; *n_matrices, ids, matrices, matrix_of_mixture [n_mixtures] out. */
+int  amx_mllr_adaptor_write(const amx_mllr_shape* shape, const char* cluster_id, int n_matrices, const int* matrix_ids, const double* matrices,
+                            int n_mixtures, const int* matrix_of_mixture, const char* path);
+int  amx_mllr_adaptor_read(const amx_mllr_shape* shape, const char* path, int max_matrices, int* n_matrices, int* matrix_ids, double* matrices,
+                           int n_mixtures, int* matrix_of_mixture);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -2425,3 +2425,161 @@ class AffineFeatureTransform:
         _lib.check(self.L.amx_cmllr_apply_dev(self.ctx.h, _ptr(transforms_dev), has.ctypes.data, self.n_keys, self.model_dim, self.feature_dim, _ptr(in_dev),
                                               int(in_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(out_dev), int(out_ld), C.byref(n)))
         return n.value
+
+
+_MLLR_MODES = {"full": _lib.AMX_MLLR_FULL, "shift": _lib.AMX_MLLR_SHIFT, "band": _lib.AMX_MLLR_BAND, "semi-tied": _lib.AMX_MLLR_SEMI_TIED}
+
+
+class ModelTransformEstimator:
+    """Speech::ModelTransformEstimator over Mm::FullAdaptorViterbiEstimator / Mm::ShiftAdaptorViterbiEstimator (MLLR): per (key, leaf) the
+    flat f64 accumulator ([count_Z | Z: D x (D + 1) | count_G | G: (D + 1) x (D + 1)], shift: [count | beta: D | shift: D]), its corpus
+    pass on the device, its files and adaptor().
+
+    leaf_of_mixture is the reference's leafIndex_ as MllrAdaptation.cc indexes it, with the mixture index.  With a GmmFeatureScorer
+    created on a context the estimator accumulates; for host-only use (files, estimate) pass gmm=None and dim."""
+
+    def __init__(self, gmm, mode, n_leafs, leaf_of_mixture, n_keys=1, dim=None):
+        self.L = _lib.lib()
+        self.gmm, self.h = gmm, None
+        if mode not in _MLLR_MODES:
+            raise ValueError("ModelTransformEstimator: unknown mode %r" % (mode,))
+        self.leaf_of_mixture = np.ascontiguousarray(leaf_of_mixture, dtype=np.int32)
+        self.shape = _lib.MllrShape()
+        if gmm is not None:
+            h = C.c_void_p()
+            _lib.check(self.L.amx_mllr_create(gmm.h, _MLLR_MODES[mode], int(n_keys), int(n_leafs), self.leaf_of_mixture.ctypes.data, C.byref(h)))
+            self.h = h
+            _lib.check(self.L.amx_mllr_describe(h, C.byref(self.shape)))
+        else:
+            if dim is None:
+                raise ValueError("ModelTransformEstimator: without a scorer, dim says what the model's dimension is")
+            self.shape = _lib.MllrShape(_MLLR_MODES[mode], int(dim), int(n_leafs), int(n_keys))
+            if self.key_size() == 0:   # the shape is refused: let the library say why
+                _lib.check(self.L.amx_mllr_accumulator_read(C.byref(self.shape), None, None, None, None))
+        self.mode, self.dim, self.n_leafs, self.n_keys = mode, self.shape.dim, self.shape.n_leafs, self.shape.n_keys
+        self.n_mixtures = len(self.leaf_of_mixture)
+
+    def close(self):
+        if self.h:
+            self.L.amx_mllr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def leaf_size(self):
+        return int(self.L.amx_mllr_leaf_size(C.byref(self.shape)))
+
+    def key_size(self):
+        """doubles of ONE key's part of the accumulator (0: the shape is refused)"""
+        return int(self.L.amx_mllr_key_size(C.byref(self.shape)))
+
+    def accumulator_size(self):
+        return self.key_size() * self.n_keys
+
+    @staticmethod
+    def kernel_shape():
+        """(frames per LDS stage, cells per workgroup) of the accumulation kernel"""
+        s, c = C.c_int(), C.c_int()
+        _lib.lib().amx_mllr_kernel_shape(C.byref(s), C.byref(c))
+        return s.value, c.value
+
+    def accumulate_dev(self, feats_dev, feats_ld, frame_offsets, seg_key, emission_dev, best_density_dev, acc_dev, best_density_ld=0, weight_dev=None):
+        """add the segments' frames to (their key, their emission's leaf): arguments as AffineFeatureTransformEstimator.accumulate_dev"""
+        if self.h is None:
+            raise RuntimeError("ModelTransformEstimator.accumulate_dev: created without a scorer")
+        off = _offsets(frame_offsets, "ModelTransformEstimator.accumulate_dev")
+        keys = np.ascontiguousarray(seg_key, dtype=np.int32)
+        if len(keys) != len(off) - 1:
+            raise ValueError("seg_key holds %d keys for %d segments" % (len(keys), len(off) - 1))
+        _lib.check(self.L.amx_mllr_accumulate_dev(self.h, _ptr(feats_dev), int(feats_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(emission_dev),
+                                                  _ptr(best_density_dev), int(best_density_ld), _ptr(weight_dev), _ptr(acc_dev)))
+
+    def _key(self, acc_host, key):
+        a = np.ascontiguousarray(acc_host, dtype=np.float64).reshape(-1)
+        n = self.key_size()
+        if a.size == n and key in (0, None):
+            return a
+        if a.size != n * self.n_keys or key is None or not 0 <= key < self.n_keys:
+            raise ValueError("accumulator has %d entries (%d per key, %d keys), key %r" % (a.size, n, self.n_keys, key))
+        return a[key * n:(key + 1) * n]
+
+    def write(self, acc_host, path, key=0, cluster_id="", min_observation=1000.0, min_silence_observation=500.0, node_count=None, map_ids=()):
+        """one key's accumulator as the reference's binary accumulator file (type tag first); map_ids: the tree's node ids"""
+        a = self._key(acc_host, key)
+        cnt = None if node_count is None else np.ascontiguousarray(node_count, dtype=np.float64)
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32)
+        _lib.check(self.L.amx_mllr_accumulator_write(C.byref(self.shape), a.ctypes.data, os.fsencode(cluster_id), float(min_observation),
+                                                     float(min_silence_observation), 0 if cnt is None else len(cnt), _ptr(cnt), len(ids),
+                                                     ids.ctypes.data if len(ids) else None, os.fsencode(path)))
+
+    def read(self, path, thresholds=False):
+        """accumulator file -> one key's flat accumulator (thresholds=True: and the file's two thresholds)"""
+        n = self.key_size()
+        a = np.zeros(max(n, 1), np.float64)
+        mo, ms = C.c_double(), C.c_double()
+        _lib.check(self.L.amx_mllr_accumulator_read(C.byref(self.shape), os.fsencode(path), a.ctypes.data, C.byref(mo), C.byref(ms)))
+        return (a[:n], mo.value, ms.value) if thresholds else a[:n]
+
+    def estimate(self, acc_host, tree, key=0, min_observation=1000.0, min_silence_observation=500.0, rcond=0.0):
+        """adaptor() of one key.  tree: dict(root, left, right, previous, leaf_number [n_ids] with -1 for none, leaf_list (node ids in
+        leafList() order), silence_mixtures (ascending)).  Returns dict(matrix_ids, matrices [n, D, D + 1] (shift: [n, D]),
+        matrix_of_mixture, node_count, root_fallback, silence_fallback)"""
+        a, D = self._key(acc_host, key), self.dim
+        arr = {k: np.ascontiguousarray(tree[k], dtype=np.int32) for k in ("left", "right", "previous", "leaf_number", "leaf_list", "silence_mixtures")}
+        n_ids = len(arr["left"])
+        if not (len(arr["right"]) == len(arr["previous"]) == len(arr["leaf_number"]) == n_ids):
+            raise ValueError("ModelTransformEstimator.estimate: left, right, previous and leaf_number must have one entry per node id")
+        t = _lib.MllrTree(n_ids, int(tree["root"]), arr["left"].ctypes.data, arr["right"].ctypes.data, arr["previous"].ctypes.data,
+                          arr["leaf_number"].ctypes.data, len(arr["leaf_list"]), arr["leaf_list"].ctypes.data, len(arr["silence_mixtures"]),
+                          arr["silence_mixtures"].ctypes.data)
+        cap = len(arr["leaf_list"]) + len(arr["silence_mixtures"]) + 1
+        per = (D,) if self.mode == "shift" else (D, D + 1)
+        ids, mats = np.zeros(cap, np.int32), np.zeros((cap,) + per, np.float64)
+        index, cnt = np.zeros(self.n_mixtures, np.int32), np.zeros(max(n_ids, 1), np.float64)
+        n, fl = C.c_int(0), C.c_int(0)
+        _lib.check(self.L.amx_mllr_estimate(C.byref(self.shape), a.ctypes.data, C.byref(t), self.n_mixtures, self.leaf_of_mixture.ctypes.data,
+                                            float(min_observation), float(min_silence_observation), float(rcond), C.byref(n), ids.ctypes.data,
+                                            mats.ctypes.data, index.ctypes.data, cnt.ctypes.data, C.byref(fl)))
+        return dict(matrix_ids=ids[:n.value].copy(), matrices=mats[:n.value].copy(), matrix_of_mixture=index, node_count=cnt[:n_ids],
+                    root_fallback=bool(fl.value & _lib.AMX_MLLR_ROOT_FALLBACK), silence_fallback=bool(fl.value & _lib.AMX_MLLR_SILENCE_FALLBACK))
+
+    def write_adaptor(self, path, matrix_ids, matrices, matrix_of_mixture, cluster_id=""):
+        """FullAdaptor::write / ShiftAdaptor::write behind the type tag"""
+        ids = np.ascontiguousarray(matrix_ids, dtype=np.int32)
+        mats = np.ascontiguousarray(matrices, dtype=np.float64)
+        index = np.ascontiguousarray(matrix_of_mixture, dtype=np.int32)
+        if mats.shape != (len(ids),) + ((self.dim,) if self.mode == "shift" else (self.dim, self.dim + 1)):
+            raise ValueError("write_adaptor: matrices of shape %r for %d ids" % (mats.shape, len(ids)))
+        _lib.check(self.L.amx_mllr_adaptor_write(C.byref(self.shape), os.fsencode(cluster_id), len(ids), ids.ctypes.data, mats.ctypes.data, len(index),
+                                                 index.ctypes.data, os.fsencode(path)))
+
+    def read_adaptor(self, path, max_matrices=65535):
+        per = (self.dim,) if self.mode == "shift" else (self.dim, self.dim + 1)
+        ids, mats = np.zeros(max_matrices, np.int32), np.zeros((max_matrices,) + per, np.float64)
+        index, n = np.zeros(self.n_mixtures, np.int32), C.c_int(0)
+        _lib.check(self.L.amx_mllr_adaptor_read(C.byref(self.shape), os.fsencode(path), int(max_matrices), C.byref(n), ids.ctypes.data, mats.ctypes.data,
+                                                self.n_mixtures, index.ctypes.data))
+        return dict(matrix_ids=ids[:n.value].copy(), matrices=mats[:n.value].copy(), matrix_of_mixture=index)
+
+
+class MixtureSetAdaptor:
+    """Am::MixtureSetAdaptor's mean adaptation for one key: FullAdaptor / ShiftAdaptor::adaptMixtureSet on the device.  The adapted mean
+    table [n_means, D] f32 goes to a device buffer; the caller copies it out and creates the adapted scorer from it."""
+
+    def __init__(self, estimator):
+        if estimator.h is None:
+            raise RuntimeError("MixtureSetAdaptor: the estimator was created without a scorer")
+        self.est, self.L = estimator, estimator.L
+
+    def adapt_means_dev(self, matrix_ids, matrices, matrix_of_mixture, out_dev):
+        ids = np.ascontiguousarray(matrix_ids, dtype=np.int32)
+        mats = np.ascontiguousarray(matrices, dtype=np.float64)
+        index = np.ascontiguousarray(matrix_of_mixture, dtype=np.int32)
+        e = self.est
+        if mats.shape != (len(ids),) + ((e.dim,) if e.mode == "shift" else (e.dim, e.dim + 1)) or len(index) != e.n_mixtures:
+            raise ValueError("adapt_means_dev: matrices of shape %r for %d ids, %d indices for %d mixtures" % (mats.shape, len(ids), len(index), e.n_mixtures))
+        _lib.check(self.L.amx_mllr_adapt_means_dev(e.h, len(ids), ids.ctypes.data, mats.ctypes.data, index.ctypes.data, _ptr(out_dev)))

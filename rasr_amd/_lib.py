@@ -167,6 +167,16 @@ AMX_CART_SPLIT, AMX_CART_PARTITION, AMX_CART_CLUSTER = range(3)
 
 class CmllrShape(C.Structure):
     _fields_ = [("feature_dim", C.c_int), ("model_dim", C.c_int), ("n_keys", C.c_int), ("pooled", C.c_int)]
+
+
+class MllrShape(C.Structure):
+    _fields_ = [("mode", C.c_int), ("dim", C.c_int), ("n_leafs", C.c_int), ("n_keys", C.c_int)]
+
+
+class MllrTree(C.Structure):
+    _fields_ = [("n_ids", C.c_int), ("root", C.c_int), ("left", C.c_void_p), ("right", C.c_void_p), ("previous", C.c_void_p),
+                ("leaf_number", C.c_void_p), ("n_leaf_list", C.c_int), ("leaf_list", C.c_void_p), ("n_silence", C.c_int),
+                ("silence_mixtures", C.c_void_p)]
 (AMX_LINSEG_OK, AMX_LINSEG_TOO_SHORT, AMX_LINSEG_TOO_LONG, AMX_LINSEG_NO_STATES, AMX_LINSEG_JUMP, AMX_LINSEG_MISMATCH, AMX_LINSEG_NONFINITE,
  AMX_LINSEG_N_REASONS) = range(8)
 AMX_BW_MAX_LABELS = 4096
@@ -523,8 +533,25 @@ SIGNATURES = {
     "amx_cmllr_score": (C.c_int, [C.POINTER(CmllrShape), _P, _P, _P, C.c_int, _P]),
     "amx_cmllr_transform_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _P]),
     "amx_cmllr_transform_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
+    "amx_mllr_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    "amx_mllr_destroy": (None, [_P]),
+    "amx_mllr_describe": (C.c_int, [_P, C.POINTER(MllrShape)]),
+    "amx_mllr_accumulator_size": (C.c_long, [_P]),
+    "amx_mllr_leaf_size": (C.c_long, [C.POINTER(MllrShape)]),
+    "amx_mllr_key_size": (C.c_long, [C.POINTER(MllrShape)]),
+    "amx_mllr_kernel_shape": (None, [_P, _P]),
+    "amx_mllr_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "amx_mllr_adapt_means_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "amx_mllr_accumulator_write": (C.c_int, [C.POINTER(MllrShape), _P, C.c_char_p, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, C.c_char_p]),
+    "amx_mllr_accumulator_read": (C.c_int, [C.POINTER(MllrShape), C.c_char_p, _P, _P, _P]),
+    "amx_mllr_estimate": (C.c_int, [C.POINTER(MllrShape), _P, C.POINTER(MllrTree), C.c_int, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                                    _P, _P]),
+    "amx_mllr_adaptor_write": (C.c_int, [C.POINTER(MllrShape), C.c_char_p, C.c_int, _P, _P, C.c_int, _P, C.c_char_p]),
+    "amx_mllr_adaptor_read": (C.c_int, [C.POINTER(MllrShape), C.c_char_p, C.c_int, _P, _P, _P, C.c_int, _P]),
 }
 AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
+AMX_MLLR_FULL, AMX_MLLR_SHIFT, AMX_MLLR_BAND, AMX_MLLR_SEMI_TIED = 0, 1, 2, 3
+AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2
 AMX_COMM_ID_BYTES = 128
 
 _lib = None
