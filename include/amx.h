@@ -2024,6 +2024,149 @@ int  amx_mllr_adaptor_write(const amx_mllr_shape* shape, const char* cluster_id,
 int  amx_mllr_adaptor_read(const amx_mllr_shape* shape, const char* path, int max_matrices, int* n_matrices, int* matrix_ids, double* matrices,
                            int n_mixtures, int* matrix_of_mixture);
 
+/* ------------------------------------------------------------------ EBW: discriminative training statistics from lattices */
+
+/* The corpus pass of Speech::SegmentwiseGmmTrainer feeding Mm::EbwDiscriminativeMixtureSetEstimator: the arc weights that Fsa::posteriorE
+ * left on a lattice become numerator and denominator statistics.  The lattice computation, the arc walk and the per-arc alignments stay
+ * with the adapter, which hands over, per segment, its arcs in the order of the reference's depth-first walk, each with one signed f32
+ * weight and its alignment as items (frame relative to the segment, emission index).
+ *   sides       an arc is numerator if w > weight_threshold, denominator with weight -w if -w > weight_threshold (f32, strict;
+ *               Lattice/Accumulator.tcc:66-87 under Speech/SegmentwiseGmmTrainer.cc:160-168), otherwise neither;
+ *   collection  per (side, frame, mixture) the f64 sum of the widened arc weights in arc order, then item order
+ *               (CachedAcousticAccumulator::process, Collector::collect, Accumulator.tcc:101-107): the order is the input's, so the
+ *               collected weights are the reference's in every bit;
+ *   density     the best density of the key's mixture for that frame, amx_gmm_best_density_dev's bits (viterbi = 0,
+ *               getDensityPosteriorProbabilities, is AMX_ERR_UNSUPPORTED naming `viterbi`); a key without a density is left out;
+ *   sums        finish() (:109-115) -> Mm::DiscriminativeMixtureSetEstimator::accumulate / accumulateDenominator
+ *               (Mm/DiscriminativeMixtureSetEstimator.cc:187-203): a numerator key adds w to its slot's mixture weight and to its mean's and
+ *               covariance's weights, w * x and (w * x) * x to their sums (Mm/MixtureEstimator.cc:92-97); a denominator key adds the
+ *               same to the denominator accumulators and w to denWeights_, and NOTHING to the slot's mixture weight:
+ *               EbwDiscriminativeMixtureEstimator::accumulateDenominator (Mm/EbwDiscriminativeMixtureEstimator.cc:109-116) overrides the
+ *               base class's (Mm/DiscriminativeMixtureEstimator.cc:59-66, `weights_ -= weight`) without calling it, so weights_ of the
+ *               EBW estimator is the numerator's weight (its XML writer calls it numerator-weight); tests/golden/make_ebw_golden.py
+ *               compiles both functions and the fixture pins this.  x + w * y and x + w * y * y (Mm/Utilities.hh:108-153) are one fused
+ *               multiply-add each under amx_set_contract(AMX_CONTRACT_FMA), two roundings otherwise.  The contract of the sums is the
+ *               context's at the time of the call; the densities follow the contract the gmm handle took at ITS creation.
+ * Order: the reference's finish() walks an unordered_map, which its text does not define.  Here every cell's chain takes its keys in
+ * ascending (frame, mixture), per side.  A chain starts from what the buffer holds, so the order continues across calls: a segment gives the same bits
+ * alone and in any batch, and a corpus cut into calls between segments gives the bits of one call.  No floating-point atomics.
+ * The accumulator is ONE flat f64 buffer the caller owns and zeroes, amx_ebw_accumulator_size() doubles, for one all-reduce:
+ *   [ numerator: amx_gmm_accumulate_dev's layout (mixture weights_ | mean weights | mean sums | covariance weights | covariance sums) ]
+ *   [ denominator: slot weights (denWeights_) | mean weights | mean sums | covariance weights | covariance sums ] [ objective ]
+ * Checked on the device before anything is written, AMX_ERR_INVALID naming the first offender, acc_dev untouched: an item's frame outside
+ * its segment, an emission outside the model, an arc weight that is not finite (arcs without items and arcs of neither side included), a
+ * feature row that is not finite and that an item of an arc with a side touches.  At most 2^27 frames, arcs and items per call. */
+typedef struct amx_ebw amx_ebw;
+typedef struct {
+    float weight_threshold; /* weight-threshold, default Core::Type<f32>::epsilon */
+    int   viterbi;          /* viterbi, default 1; 0 is AMX_ERR_UNSUPPORTED */
+} amx_ebw_cfg;
+typedef struct {
+    long num_mixture_weights, num_mean_weights, num_mean_sums, num_cov_weights, num_cov_sums; /* offsets in doubles */
+    long den_density_weights, den_mean_weights, den_mean_sums, den_cov_weights, den_cov_sums;
+    long objective, size;
+    long n_slots /* sum of the mixtures' densities */, n_means, n_covariances, dim;
+} amx_ebw_offsets;
+void amx_ebw_cfg_default(amx_ebw_cfg* cfg);
+/* the gmm handle must outlive this one; created without a context it gives a host-only handle (sizes and layout).  A scorer that keeps
+ * no diagonal-maximum tables on the device (amx_gmm_best_density_dev's condition) is refused here with AMX_ERR_UNSUPPORTED */
+int  amx_ebw_create(amx_gmm* gmm, const amx_ebw_cfg* cfg /* NULL: defaults */, amx_ebw** out);
+void amx_ebw_destroy(amx_ebw* h);
+long amx_ebw_accumulator_size(const amx_ebw* h); /* doubles; 0 for NULL */
+int  amx_ebw_layout(const amx_ebw* h, amx_ebw_offsets* out);
+/* feats_dev [rows x feats_ld] as the front end left it; segment s owns the rows [frame_offsets[s], frame_offsets[s + 1]) and the arcs
+ * [arc_offsets[s], arc_offsets[s + 1]), arc a the items [item_offsets[a], item_offsets[a + 1]); arc_offsets[0] = item_offsets[0] = 0.
+ * The tables are host memory.  Synchronises the stream. */
+int  amx_ebw_accumulate_dev(amx_ebw* h, const float* feats_dev, int feats_ld, int n_seg, const long* frame_offsets /*[n_seg+1]*/,
+                            const long* arc_offsets /*[n_seg+1]*/, const float* arc_weight, const long* item_offsets /*[n_arcs+1]*/,
+                            const int32_t* item_frame, const int32_t* item_emission, double* acc_dev);
+/* accumulateObjectiveFunction(f32) (Speech/SegmentwiseGmmTrainer.cc:113-116): the widened objective of one segment into the last cell */
+int  amx_ebw_accumulate_objective(amx_ebw* h, float objective, double* acc_dev);
+/* DIAGNOSTIC, for tests, probes and the statistics channel (not part of the reference's interface; it copies from the handle's workspace):
+ * the keys of the last amx_ebw_accumulate_dev in ascending (frame, mixture, side): frame relative to frame_offsets[0], side 0 numerator /
+ * 1 denominator, the collected weight and the slot (offset of the best density in the mixture-weight block, -1: no density).  Every array
+ * nullable; all NULL: *n_keys only. */
+int  amx_ebw_last_keys(const amx_ebw* h, int capacity, int* n_keys, long* frame, int32_t* mixture, int32_t* side, double* weight, int32_t* slot);
+
+/* ---- host side (ebw_host.cpp): `acc` is the flat buffer in host memory, `topology` the model the statistics were accumulated with
+ * (its means, variances and weights are not read).  amx_ebw_topology_accumulator_size: amx_ebw_accumulator_size from the topology alone
+ * (0 for a topology that is refused).
+ * The file is the reference's binary estimator file of Mm::EbwDiscriminativeMixtureSetEstimator: the "MIXSET" layout under the magic "DTACC"
+ * (Mm/DiscriminativeMixtureSetEstimator.hh:42-44; eight bytes, the three behind the letters zero), version 2
+ * (Mm/AbstractMixtureSetEstimator.cc:404-508), every mean and covariance record followed by its denominator accumulator
+ * (Mm/EbwDiscriminativeGaussDensityEstimator.cc:55-58, :150-153), every mixture record by its denWeights_
+ * (Mm/EbwDiscriminativeMixtureEstimator.cc:148-154), and the objective function as the last f64
+ * (Mm/DiscriminativeMixtureSetEstimator.cc:115-119): the file RASR's accumulate, combine-mixture-set-estimators and estimate actions exchange.
+ * Its bytes are those the reference's write chain makes, compiled by tests/golden/make_ebw_golden.py (ref_ebw.npz); the reference's
+ * reader has not been run on a file from here.  read requires the file's topology to equal the
+ * model's, its version to be 2 and the file to end behind the objective; a file that is refused leaves `acc` untouched.
+ * combine is the file-level sum of AbstractMixtureSetEstimator::accumulate(is, os) (:170-300) for two estimators: acc += add in every
+ * cell, the objective included (DiscriminativeMixtureSetEstimator.cc:162-177); an entry that is not finite is AMX_ERR_INVALID and
+ * nothing is added. */
+long amx_ebw_topology_accumulator_size(const amx_gmm_model* topology);
+
+/* The EBW update: Mm::DiscriminativeMixtureSetEstimator::estimate (Mm/DiscriminativeMixtureSetEstimator.cc:136-160) for
+ * Mm::EbwDiscriminativeMixtureSetEstimator and, with an i-smoothing set, ...WithISmoothing, operation by operation in f64:
+ *   previous set   distributed by index (:51-86); here its topology must EQUAL `topology` (the reference compares the counts only);
+ *   removal        removeDensitiesWithLowWeight's discriminative rule (Mm/DiscriminativeMixtureEstimator.cc:34-49): weights_ -- the
+ *                  numerator's weight, see above -- against min_observation_weight, the previous mixture weight against
+ *                  min_relative_weight, the heaviest density kept, `--densityMax` after EVERY removal as the reference has it; the
+ *                  survivors renumbered in order of first appearance, as amx_gmm_estimate renumbers;
+ *   constants      Mm/IterationConstants.cc: Xi and beta, sigma-minimum (or sigma_minimum_factor times the smallest previous variance),
+ *                  minimumDk, global-rwth / local-rwth, step-size, minimum-icd, the scaling by the previous mixture weight;
+ *   means, covariances   Mm/EbwDiscriminativeGaussDensityEstimator.cc:73-99, :165-207: the narrowing to f32, applyMinimumVariance, the
+ *                  previous mean where dtWeight + D <= 0;
+ *   weights        the Cambridge scheme of estimateMixtureWeights (Mm/EbwDiscriminativeMixtureEstimator.cc:39-91): number_of_iterations,
+ *                  the clamp to 0, the normalisation and its vanishing-sum fallback; then Mixture::normalizeWeights;
+ *   i-smoothing    with `ismoothing` given: i_smoothing_means / i_smoothing_weights enter dtSum, dtWeight, iSum and weight(dns)
+ *                  (:114-121, :222-229, Mm/ISmoothingGaussDensityEstimator.cc:56-71, Mm/EbwDiscriminativeMixtureEstimator.hh:83-85), and
+ *                  info->i_smoothing_objective is ISmoothing*::getObjectiveFunction on the NEW set (Mm/ISmoothingMixtureSetEstimator.cc:96-115);
+ *   finalize       with min_relative_weight != 0, Mixture::removeDensitiesWithLowWeight on the new set (Mm/Mixture.cc:109-129; its
+ *                  densityIndexWithMaxWeight compares two iterators, so no density is protected there).
+ * cfg->contract says which build of the reference is followed (AMX_CONTRACT_OFF | AMX_CONTRACT_FMA: the sums the -march=native build
+ * fuses, read off tests/golden/ref_ebw.npz).  Sums that the reference takes in the order of a hash table -- the densities of a shared
+ * covariance in minimumDk, the means of a covariance in the covariance estimate and iSum -- are taken in ascending (new) index here;
+ * DESIGN.md section 6 has the measured distance.  The result is a mixture set like amx_gmm_estimate's.
+ * Refused, amx_last_error naming the cause: AMX_ERR_UNSUPPORTED for iteration constants of type cambridge (maximumRoot starts with
+ * require(false)), local-rwth on a model where a mixture's densities use more than one covariance (the result would depend on the hash
+ * walk), a density shared by two mixtures (the reference requires this) or a mean shared by two densities (the iteration constant of the
+ * mean would be the hash walk's last), the Rprop estimator, viterbi = 0; AMX_ERR_INVALID for a non-finite accumulator, a topology that
+ * differs, a summed weight <= 0 or an estimated variance <= 0 (the reference's verify), an iteration constant that is not finite. */
+enum { AMX_EBW_IC_GLOBAL_RWTH = 0, AMX_EBW_IC_LOCAL_RWTH = 1, AMX_EBW_IC_CAMBRIDGE = 2 };
+enum { AMX_EBW_ESTIMATOR_EBW = 0, AMX_EBW_ESTIMATOR_RPROP = 1 };
+typedef struct {
+    double min_observation_weight;    /* minimum-observation-weight, 5 */
+    double min_relative_weight;       /* minimum-relative-weight, 0 */
+    double min_variance;              /* minimum-variance, 0 (compared and stored as f32) */
+    int    normalize_mixture_weights; /* normalize-mixture-weights, 1 */
+    int    iteration_constants;       /* iteration-constants.type, global-rwth */
+    double step_size;                 /* step-size, 1.1 */
+    double minimum_icd;               /* minimum-icd, 1 */
+    double beta;                      /* icb.xi.beta, 1 */
+    double sigma_minimum;             /* icb.sigma-minimum; negative (the default here): sigma_minimum_factor * smallest previous variance */
+    double sigma_minimum_factor;      /* icb.sigma-minimum-factor, 1e-5 */
+    int    number_of_iterations;      /* mixture-estimator.number-of-iterations, 100 */
+    double i_smoothing_means;         /* i-smoothing-means, 0 */
+    double i_smoothing_weights;       /* i-smoothing-weights, 0 */
+    int    viterbi;                   /* 1 */
+    int    estimator;                 /* AMX_EBW_ESTIMATOR_EBW */
+    int    contract;                  /* AMX_CONTRACT_OFF */
+} amx_ebw_estimate_cfg;
+typedef struct {
+    double i_smoothing_objective; /* 0 without an i-smoothing set */
+    double sigma_minimum;
+    int    n_removed, n_clamped /* (mixture, density) pairs whose weight an iteration set to 0 */, n_mean_fallback, n_floored;
+} amx_ebw_estimate_info;
+void amx_ebw_estimate_cfg_default(amx_ebw_estimate_cfg* cfg);
+/* previous / ismoothing: views of mixture sets on the topology (amx_mixture_set_view gives one); ismoothing, info and
+ * iteration_constants ([topology->n_mean] doubles, filled by NEW mean index) are nullable */
+int  amx_ebw_estimate(const amx_gmm_model* topology, const double* acc, const amx_gmm_model* previous, const amx_gmm_model* ismoothing,
+                      const amx_ebw_estimate_cfg* cfg /* NULL: defaults */, amx_mixture_set** out, amx_ebw_estimate_info* info,
+                      double* iteration_constants);
+int  amx_ebw_accumulator_write(const amx_gmm_model* topology, const double* acc, const char* path);
+int  amx_ebw_accumulator_read(const amx_gmm_model* topology, const char* path, double* acc);
+int  amx_ebw_accumulator_combine(const amx_gmm_model* topology, double* acc, const double* add);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -2583,3 +2583,178 @@ class MixtureSetAdaptor:
         if mats.shape != (len(ids),) + ((e.dim,) if e.mode == "shift" else (e.dim, e.dim + 1)) or len(index) != e.n_mixtures:
             raise ValueError("adapt_means_dev: matrices of shape %r for %d ids, %d indices for %d mixtures" % (mats.shape, len(ids), len(index), e.n_mixtures))
         _lib.check(self.L.amx_mllr_adapt_means_dev(e.h, len(ids), ids.ctypes.data, mats.ctypes.data, index.ctypes.data, _ptr(out_dev)))
+
+
+class EbwAccumulator:
+    """The corpus pass of Speech::SegmentwiseGmmTrainer into Mm::EbwDiscriminativeMixtureSetEstimator's accumulators: lattice arc weights
+    (what Fsa::posteriorE left on the arcs) become numerator and denominator statistics in ONE flat f64 buffer,
+    [numerator: amx_gmm_accumulate_dev's layout][denominator slot weights | mean weights | mean sums |
+    covariance weights | covariance sums][objective].
+
+    weight_threshold and viterbi are the reference's parameters with its defaults; viterbi=False is refused."""
+
+    VIEWS = ("num_mixture_weights", "num_mean_weights", "num_mean_sums", "num_cov_weights", "num_cov_sums", "den_density_weights",
+             "den_mean_weights", "den_mean_sums", "den_cov_weights", "den_cov_sums", "objective")
+
+    def __init__(self, gmm, weight_threshold=None, viterbi=True):
+        self.L = _lib.lib()
+        self.gmm, self.h = gmm, None
+        cfg = _lib.EbwCfg()
+        self.L.amx_ebw_cfg_default(C.byref(cfg))
+        if weight_threshold is not None:
+            cfg.weight_threshold = float(weight_threshold)
+        cfg.viterbi = 1 if viterbi else 0
+        h = C.c_void_p()
+        _lib.check(self.L.amx_ebw_create(gmm.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.weight_threshold = cfg.weight_threshold
+        self.layout = _lib.EbwOffsets()
+        _lib.check(self.L.amx_ebw_layout(h, C.byref(self.layout)))
+
+    def close(self):
+        if self.h:
+            self.L.amx_ebw_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulator_size(self):
+        return int(self.L.amx_ebw_accumulator_size(self.h))
+
+    def view(self, acc, name):
+        """the named part of a flat accumulator (numpy array or tensor): a view, shaped [n] or [n, dim]"""
+        o = self.layout
+        n = {"num_mixture_weights": o.n_slots, "den_density_weights": o.n_slots, "num_mean_weights": o.n_means, "den_mean_weights": o.n_means,
+             "num_cov_weights": o.n_covariances, "den_cov_weights": o.n_covariances, "objective": 1}
+        if name not in self.VIEWS:
+            raise KeyError("EbwAccumulator.view: no part called %r" % (name,))
+        b = getattr(o, name)
+        if name in n:
+            return acc[b:b + n[name]]
+        rows = o.n_means if "mean" in name else o.n_covariances
+        return acc[b:b + rows * o.dim].reshape(rows, o.dim)
+
+    def accumulate_dev(self, feats_dev, feats_ld, frame_offsets, arc_offsets, arc_weight, item_offsets, item_frame, item_emission, acc_dev):
+        """add a batch of segments: segment s owns the feature rows [frame_offsets[s], frame_offsets[s + 1]) and the arcs
+        [arc_offsets[s], arc_offsets[s + 1]); arc a carries arc_weight[a] (f32, signed) and the items [item_offsets[a], item_offsets[a + 1]),
+        each a frame relative to the segment and an emission index.  The tables are host arrays."""
+        off = _offsets(frame_offsets, "EbwAccumulator.accumulate_dev")
+        arcs = np.ascontiguousarray(arc_offsets, dtype=np.int64)
+        items = np.ascontiguousarray(item_offsets, dtype=np.int64)
+        w = np.ascontiguousarray(arc_weight, dtype=np.float32)
+        fr = np.ascontiguousarray(item_frame, dtype=np.int32)
+        em = np.ascontiguousarray(item_emission, dtype=np.int32)
+        if len(arcs) != len(off) or len(items) != len(w) + 1 or (len(arcs) and arcs[-1] != len(w)) or len(fr) != len(em) or items[-1] != len(fr):
+            raise ValueError("EbwAccumulator.accumulate_dev: %d segments, %d arc offsets, %d arcs, %d item offsets, %d / %d items"
+                             % (len(off) - 1, len(arcs), len(w), len(items), len(fr), len(em)))
+        _lib.check(self.L.amx_ebw_accumulate_dev(self.h, _ptr(feats_dev), int(feats_ld), len(off) - 1, off.ctypes.data, arcs.ctypes.data,
+                                                 w.ctypes.data, items.ctypes.data, fr.ctypes.data, em.ctypes.data, _ptr(acc_dev)))
+
+    def accumulate_objective(self, objective, acc_dev):
+        """accumulateObjectiveFunction: one segment's objective (f32, widened) into the buffer's last cell"""
+        _lib.check(self.L.amx_ebw_accumulate_objective(self.h, float(np.float32(objective)), _ptr(acc_dev)))
+
+    def last_keys(self):
+        """the keys of the last accumulate_dev in ascending (frame, mixture, side): dict(frame, mixture, side, weight, slot)"""
+        n = C.c_int(0)
+        _lib.check(self.L.amx_ebw_last_keys(self.h, 0, C.byref(n), None, None, None, None, None))
+        k = max(n.value, 1)
+        frame, mix, side = np.zeros(k, np.int64), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        weight, slot = np.zeros(k, np.float64), np.zeros(k, np.int32)
+        _lib.check(self.L.amx_ebw_last_keys(self.h, k, C.byref(n), frame.ctypes.data, mix.ctypes.data, side.ctypes.data, weight.ctypes.data,
+                                            slot.ctypes.data))
+        return dict(frame=frame[:n.value], mixture=mix[:n.value], side=side[:n.value], weight=weight[:n.value], slot=slot[:n.value])
+
+    # ---- host side: the reference's binary estimator file and the file-level sum; `model` is the model dict of the statistics
+
+    @staticmethod
+    def topology_size(model):
+        """doubles of the flat accumulator, from the model's topology alone"""
+        keep = []
+        return int(_lib.lib().amx_ebw_topology_accumulator_size(C.byref(_gmm_struct(model, 1.0, 1.0, keep))))
+
+    @staticmethod
+    def _host(model, acc, who):
+        a = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1)
+        n = EbwAccumulator.topology_size(model)   # 0: the topology is refused, and the library says why
+        if n and a.size != n:
+            raise ValueError("%s: accumulator has %d entries, the model's has %d" % (who, a.size, n))
+        return a
+
+    @staticmethod
+    def write(model, acc_host, path):
+        """Mm::EbwDiscriminativeMixtureSetEstimator's binary estimator file (magic "DTACC", version 2, denominator accumulators, objective)"""
+        keep = []
+        a = EbwAccumulator._host(model, acc_host, "EbwAccumulator.write")
+        _lib.check(_lib.lib().amx_ebw_accumulator_write(C.byref(_gmm_struct(model, 1.0, 1.0, keep)), a.ctypes.data, os.fsencode(path)))
+
+    @staticmethod
+    def read(model, path):
+        """estimator file -> flat accumulator; the file's topology must be the model's"""
+        keep = []
+        a = np.zeros(EbwAccumulator.topology_size(model), np.float64)
+        _lib.check(_lib.lib().amx_ebw_accumulator_read(C.byref(_gmm_struct(model, 1.0, 1.0, keep)), os.fsencode(path), a.ctypes.data if a.size else None))
+        return a
+
+    @staticmethod
+    def combine(model, acc_host, add_host):
+        """combine-mixture-set-estimators for two accumulators: acc_host += add_host (in place when acc_host is a contiguous f64 array)"""
+        keep = []
+        a = EbwAccumulator._host(model, acc_host, "EbwAccumulator.combine")
+        b = EbwAccumulator._host(model, add_host, "EbwAccumulator.combine")
+        _lib.check(_lib.lib().amx_ebw_accumulator_combine(C.byref(_gmm_struct(model, 1.0, 1.0, keep)), a.ctypes.data, b.ctypes.data))
+        return a
+
+
+class EbwEstimator:
+    """Mm::EbwDiscriminativeMixtureSetEstimator::estimate (with an i-smoothing set: ...WithISmoothing): the EBW update from the flat
+    accumulator of EbwAccumulator.  Keyword arguments are the reference's parameters with its defaults: minimum_observation_weight (5),
+    minimum_relative_weight (0), minimum_variance (0), normalize_mixture_weights (True), type ("global-rwth" | "local-rwth";
+    "cambridge" is refused), step_size (1.1), minimum_icd (1), beta (1), sigma_minimum (None: sigma_minimum_factor times the smallest
+    previous variance), sigma_minimum_factor (1e-5), number_of_iterations (100), i_smoothing_means (0), i_smoothing_weights (0),
+    viterbi (True), estimator ("ebw"; "rprop" is refused), contract ("off" | "fma")."""
+
+    TYPES = {"global-rwth": _lib.AMX_EBW_IC_GLOBAL_RWTH, "local-rwth": _lib.AMX_EBW_IC_LOCAL_RWTH, "cambridge": _lib.AMX_EBW_IC_CAMBRIDGE}
+    NAMES = {"minimum_observation_weight": "min_observation_weight", "minimum_relative_weight": "min_relative_weight", "minimum_variance": "min_variance"}
+
+    def __init__(self, **kw):
+        self.L = _lib.lib()
+        self.cfg = _lib.EbwEstimateCfg()
+        self.L.amx_ebw_estimate_cfg_default(C.byref(self.cfg))
+        for k, v in kw.items():
+            k = self.NAMES.get(k, k)
+            if k == "type":
+                if v not in self.TYPES:
+                    raise ValueError("EbwEstimator: unknown type of iteration constants %r" % (v,))
+                self.cfg.iteration_constants = self.TYPES[v]
+            elif k == "estimator":
+                self.cfg.estimator = {"ebw": _lib.AMX_EBW_ESTIMATOR_EBW, "rprop": _lib.AMX_EBW_ESTIMATOR_RPROP}[v]
+            elif k == "contract":
+                self.cfg.contract = Context.CONTRACTS[v] if isinstance(v, str) else int(v)
+            elif k == "sigma_minimum":
+                self.cfg.sigma_minimum = -1.0 if v is None else float(v)
+            elif hasattr(self.cfg, k):
+                setattr(self.cfg, k, int(v) if k in ("normalize_mixture_weights", "number_of_iterations", "viterbi") else float(v))
+            else:
+                raise TypeError("EbwEstimator: unknown option %r" % (k,))
+
+    def estimate(self, model, acc_host, previous, ismoothing=None):
+        """model: the model dict the statistics were accumulated with; previous / ismoothing: model dicts on the same topology.
+        Returns (new model dict, dict(i_smoothing_objective, sigma_minimum, n_removed, n_clamped, n_mean_fallback, n_floored,
+        iteration_constants [new means]))"""
+        keep = []
+        a = EbwAccumulator._host(model, acc_host, "EbwEstimator.estimate")
+        st = _gmm_struct(model, 1.0, 1.0, keep)
+        ps = _gmm_struct(previous, 1.0, 1.0, keep)
+        ist = _gmm_struct(ismoothing, 1.0, 1.0, keep) if ismoothing is not None else None
+        info, icd, h = _lib.EbwEstimateInfo(), np.zeros(max(st.n_mean, 1), np.float64), C.c_void_p()
+        _lib.check(self.L.amx_ebw_estimate(C.byref(st), a.ctypes.data, C.byref(ps), C.byref(ist) if ist is not None else None, C.byref(self.cfg),
+                                           C.byref(h), C.byref(info), icd.ctypes.data))
+        new = _mixture_set_to_dict(h)
+        return new, dict(i_smoothing_objective=info.i_smoothing_objective, sigma_minimum=info.sigma_minimum, n_removed=info.n_removed,
+                         n_clamped=info.n_clamped, n_mean_fallback=info.n_mean_fallback, n_floored=info.n_floored,
+                         iteration_constants=icd[:new["means"].shape[0]].copy())

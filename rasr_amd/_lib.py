@@ -173,6 +173,29 @@ class MllrShape(C.Structure):
     _fields_ = [("mode", C.c_int), ("dim", C.c_int), ("n_leafs", C.c_int), ("n_keys", C.c_int)]
 
 
+class EbwCfg(C.Structure):
+    _fields_ = [("weight_threshold", C.c_float), ("viterbi", C.c_int)]
+
+
+class EbwOffsets(C.Structure):
+    _fields_ = [(n, C.c_long) for n in ("num_mixture_weights", "num_mean_weights", "num_mean_sums", "num_cov_weights", "num_cov_sums",
+                                        "den_density_weights", "den_mean_weights", "den_mean_sums", "den_cov_weights", "den_cov_sums",
+                                        "objective", "size", "n_slots", "n_means", "n_covariances", "dim")]
+
+
+class EbwEstimateCfg(C.Structure):
+    _fields_ = [("min_observation_weight", C.c_double), ("min_relative_weight", C.c_double), ("min_variance", C.c_double),
+                ("normalize_mixture_weights", C.c_int), ("iteration_constants", C.c_int), ("step_size", C.c_double), ("minimum_icd", C.c_double),
+                ("beta", C.c_double), ("sigma_minimum", C.c_double), ("sigma_minimum_factor", C.c_double), ("number_of_iterations", C.c_int),
+                ("i_smoothing_means", C.c_double), ("i_smoothing_weights", C.c_double), ("viterbi", C.c_int), ("estimator", C.c_int),
+                ("contract", C.c_int)]
+
+
+class EbwEstimateInfo(C.Structure):
+    _fields_ = [("i_smoothing_objective", C.c_double), ("sigma_minimum", C.c_double), ("n_removed", C.c_int), ("n_clamped", C.c_int),
+                ("n_mean_fallback", C.c_int), ("n_floored", C.c_int)]
+
+
 class MllrTree(C.Structure):
     _fields_ = [("n_ids", C.c_int), ("root", C.c_int), ("left", C.c_void_p), ("right", C.c_void_p), ("previous", C.c_void_p),
                 ("leaf_number", C.c_void_p), ("n_leaf_list", C.c_int), ("leaf_list", C.c_void_p), ("n_silence", C.c_int),
@@ -548,9 +571,25 @@ SIGNATURES = {
                                     _P, _P]),
     "amx_mllr_adaptor_write": (C.c_int, [C.POINTER(MllrShape), C.c_char_p, C.c_int, _P, _P, C.c_int, _P, C.c_char_p]),
     "amx_mllr_adaptor_read": (C.c_int, [C.POINTER(MllrShape), C.c_char_p, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "amx_ebw_cfg_default": (None, [C.POINTER(EbwCfg)]),
+    "amx_ebw_create": (C.c_int, [_P, C.POINTER(EbwCfg), C.POINTER(_P)]),
+    "amx_ebw_destroy": (None, [_P]),
+    "amx_ebw_accumulator_size": (C.c_long, [_P]),
+    "amx_ebw_layout": (C.c_int, [_P, C.POINTER(EbwOffsets)]),
+    "amx_ebw_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "amx_ebw_accumulate_objective": (C.c_int, [_P, C.c_float, _P]),
+    "amx_ebw_last_keys": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P, _P]),
+    "amx_ebw_topology_accumulator_size": (C.c_long, [_P]),
+    "amx_ebw_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),
+    "amx_ebw_accumulator_read": (C.c_int, [_P, C.c_char_p, _P]),
+    "amx_ebw_accumulator_combine": (C.c_int, [_P, _P, _P]),
+    "amx_ebw_estimate_cfg_default": (None, [C.POINTER(EbwEstimateCfg)]),
+    "amx_ebw_estimate": (C.c_int, [_P, _P, _P, _P, C.POINTER(EbwEstimateCfg), C.POINTER(_P), C.POINTER(EbwEstimateInfo), _P]),
 }
 AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
 AMX_MLLR_FULL, AMX_MLLR_SHIFT, AMX_MLLR_BAND, AMX_MLLR_SEMI_TIED = 0, 1, 2, 3
+AMX_EBW_IC_GLOBAL_RWTH, AMX_EBW_IC_LOCAL_RWTH, AMX_EBW_IC_CAMBRIDGE = 0, 1, 2
+AMX_EBW_ESTIMATOR_EBW, AMX_EBW_ESTIMATOR_RPROP = 0, 1
 AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2
 AMX_COMM_ID_BYTES = 128
 

@@ -27,13 +27,7 @@
 #include <vector>
 
 #include "common.hpp"
-
-struct amx_mixture_set {
-    int                   dim = 0;
-    std::vector<uint32_t> mix_off, dens_index, dens_mean, dens_cov;
-    std::vector<double>   log_weight;
-    std::vector<float>    means, variances;
-};
+#include "mixture_set.hpp"
 
 extern "C" {
 
