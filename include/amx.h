@@ -2167,6 +2167,106 @@ int  amx_ebw_accumulator_write(const amx_gmm_model* topology, const double* acc,
 int  amx_ebw_accumulator_read(const amx_gmm_model* topology, const char* path, double* acc);
 int  amx_ebw_accumulator_combine(const amx_gmm_model* topology, double* acc, const double* add);
 
+/* ------------------------------------------------------------------ Lattice arc posteriors */
+
+/* The forward-backward pass over word lattices that the discriminative trainers start from, for a batch of lattices per call, the
+ * results left on the device: Fsa::posterior64 (Fsa/Sssp.cc:95-225; the MMI GMM trainer, Nn::MmiSegmentwiseNnTrainer,
+ * Nn/MmiSegmentwiseNnTrainer.cc:36-60, Lattice::posterior) and Fsa::posteriorE (Sssp.cc:231-375; the MPE GMM trainer,
+ * Speech/SegmentwiseGmmTrainer.cc:138-169, Nn::MeSegmentwiseNnTrainer), in f64 in the log semiring.
+ *   potentials   StatePotentials64DfsState::finishState (Sssp.cc:95-138): a state's potential is a function of its outgoing arcs IN ARC
+ *                ORDER, of the targets' potentials and of its final weight.  Start value: the final weight widened from f32, or
+ *                Zero = Core::Type<f64>::max (:67).  score = potential[target] + f32(weight), an infinite score becomes f64 max; the
+ *                search uses `<=`, so the LAST minimal arc is left out of the sum; the sum starts with exp(min - final) only for a final
+ *                state whose minimum an arc took; the other arcs add exp(min - score) in arc order; min - log1p(sum), clamped to Zero.
+ *   forward      the same function on transpose(fsa) (Fsa/tRational.cc:594-689): a state's transposed arcs stand in the order in which
+ *                TransposeDfsState::discoverState appended them, that is the DISCOVER order of their source states in the stack walk of
+ *                Fsa/tDfs.cc:21-68 (every white target is pushed, a state is discovered when it is popped) and, within a source, the
+ *                source's arc order; a new initial state has one arc per final state in discover order, weighted with the final weight;
+ *                the old initial state is final with weight one.
+ *   arcs         f32(min(fw[s] + f32(w) + bw[target] + totalInv, f32 max)) (:156-159); a final state f32(min(fw[s] + final + totalInv,
+ *                f32 max)), or 0 without arcs (:160-165); totalInv = -bw[initial], or 0 with normalize = 0 (:185).
+ *   AMX_LATPOST_PROB         then Fsa::expm (Fsa/Arithmetic.cc:47-61): isinf(w) ? 0 : f32(exp(-(f64)w)) -- the f64 overload, as the
+ *                reference's translation unit resolves it (tests/golden/make_latpost_golden.py compiles the text and records it).
+ *   AMX_LATPOST_EXPECTATION  StatePotentialsEDfsState::finishState (:254-288): strict minimum, denSum takes EVERY arc (log1p(denSum - 1)),
+ *                numSum += p * (risk + generalized[target]) -- a contraction site of the reference's default build: one fused multiply-add
+ *                under amx_set_contract(AMX_CONTRACT_FMA), two roundings otherwise (the context's setting at the time of the call) --,
+ *                written only if denSum > 0, generalized clamped to +-Zero.  An arc: f32(exp(-(f64)logPosterior) * risk) with
+ *                risk = f32(min(gfw[s] + f32(r) + gbw[target] - normalization, f32 max)) (:305-314, :352-362), normalization =
+ *                gbw[initial] with v_normalized, else 0; a final state f32(exp(-finalLogPosterior) * f32(min(final_risk - normalization,
+ *                f32 max))), the risk factor 0 without arcs.  totalInv is -bw[initial] whatever `normalize` says (:340).
+ * Input: CSR tables in host memory.  Segment g owns the states [state_offsets[g], state_offsets[g + 1]), state ids are dense per segment
+ * (arc_target and initial are ids within the segment), state i (counted over the call) owns the arcs [arc_offsets[i], arc_offsets[i + 1])
+ * in the automaton's own order.  Outputs: f32 on the device, arc_out_dev[n_arcs] in the input's arc order, final_out_dev[n_states].
+ * Where the reference defines nothing, the library chooses:
+ *   - a state the walk from the initial state does not reach has backward potential Zero, and a state the transposed walk does not reach
+ *     (the reference's forwardPotentials_ vector may not even have grown that far) has forward potential Zero; the arcs that leave such
+ *     a state are counted in info.undefined_arcs, the states in info.undefined_states; their outputs follow from Zero by the formulas;
+ *   - a state that is not final has final_out f32 max (LOG) or 0 (PROB, EXPECTATION);
+ *   - a segment in which no final state is reached (the reference's transpose returns an empty automaton) has reason
+ *     AMX_LATPOST_NO_FINAL and every output dead: f32 max (LOG) or 0; it is not an error.
+ * Order: every sum is one chain in the order above and depends on the segment alone: a segment gives the same bits alone and in any
+ * batch.  No floating-point atomics, no tree sums.  exp and log1p are the device library's (1 ulp class), so values are close to, not
+ * equal to, the host's; the bars are measured from the reference's arithmetic (tests/golden/ref_latpost.npz).
+ * Refused with AMX_ERR_INVALID naming the first offender, outputs untouched: a cycle anywhere in a segment (the reference requires
+ * PropertyAcyclic), a target outside its segment, an initial state out of range, a NaN weight or risk, EXPECTATION without risks,
+ * offsets that do not ascend.  +-inf weights follow the reference (isinf(score) -> f64 max). */
+enum { AMX_LATPOST_LOG = 0, AMX_LATPOST_PROB = 1, AMX_LATPOST_EXPECTATION = 2 };
+enum { AMX_LATPOST_OK = 0, AMX_LATPOST_NO_FINAL = 1 };
+enum { AMX_LATPOST_POTENTIALS_AUTO = 0, AMX_LATPOST_POTENTIALS_GLOBAL = 1 };
+typedef struct amx_latpost amx_latpost;
+typedef struct {
+    int mode;         /* AMX_LATPOST_LOG */
+    int normalize;    /* 1; read by LOG and PROB */
+    int v_normalized; /* 1; read by EXPECTATION */
+    int tolerance;    /* 100: posterior-tolerance of the flow comparison */
+    int potentials;   /* AMX_LATPOST_POTENTIALS_AUTO: in LDS while a segment's states fit (amx_latpost_kernel_shape); _GLOBAL: always in
+                         global memory (tests: both paths give the same bits) */
+} amx_latpost_cfg;
+typedef struct {
+    double total_inv;     /* -bw[initial] (Posterior64Automaton::totalInv) */
+    float  total_inv_f32; /* LOG, PROB: clamped from below at f32 min (:206); EXPECTATION: narrowed (:328-330) */
+    float  expectation;   /* EXPECTATION: f32(gbw[initial]); 0 otherwise */
+    float  forward_flow, backward_flow;
+    int    flows_agree;    /* Core::isAlmostEqual(fwd, bwd, tolerance) (:188), EXPECTATION: isAlmostEqualUlp (:343) */
+    int    vanishing_flow; /* isAlmostEqualUlp(total_inv_f32, f32 min, tolerance) (Nn/MmiSegmentwiseNnTrainer.cc:41) */
+    int    reason;         /* AMX_LATPOST_OK | AMX_LATPOST_NO_FINAL */
+    int    states_reached, arcs_reached;      /* by the walk from the initial state */
+    int    states_coreached;                  /* by the transposed walk (the new initial state not counted) */
+    int    undefined_states, undefined_arcs;  /* states the transposed walk does not reach, and the arcs that leave them */
+    int    levels_forward, levels_backward;   /* barriers of the two workgroups */
+} amx_latpost_info;
+void amx_latpost_cfg_default(amx_latpost_cfg* cfg);
+/* ctx NULL: a host-only handle (amx_latpost_plan_host) */
+int  amx_latpost_create(amx_ctx* ctx, const amx_latpost_cfg* cfg /* NULL: defaults */, amx_latpost** out);
+void amx_latpost_destroy(amx_latpost* h);
+/* the potentials kernel's launch shape (tests pick their sizes around it): threads of a workgroup, the largest number of states of a
+ * segment (the forward walk's new initial state included: n + 1 <= lds_states) whose potentials live in LDS, and the number of arcs from
+ * which a state is shared by a wave instead of taken by one lane */
+void amx_latpost_kernel_shape(int* threads, int* lds_states, int* wave_arcs);
+/* arc_risk / final_risk: EXPECTATION only, else ignored (NULL allowed); final_weight / final_risk are read where final_flag is set.
+ * info [n_seg] in host memory, nullable.  Synchronises the stream. */
+int  amx_latpost_run_dev(amx_latpost* h, int n_seg, const long* state_offsets /*[n_seg+1]*/, const long* arc_offsets /*[n_states+1]*/,
+                         const int32_t* arc_target, const float* arc_weight, const float* arc_risk, const int32_t* initial /*[n_seg]*/,
+                         const uint8_t* final_flag, const float* final_weight, const float* final_risk, float* arc_out_dev,
+                         float* final_out_dev, amx_latpost_info* info);
+/* The host plan alone (no device): the checks above and, per state counted over the call, discover_index (position in the reference's
+ * discover order, -1: not reached), level_backward / level_forward (the level at which the state's potential is computed, -1: not walked),
+ * in_offsets [n_states + 1] / in_arc: the transposed state's arcs as indices of input arcs, in the reference's order; final_order: per
+ * segment, from state_offsets[g] on, the reached final states in discover order (the new initial state's arcs), then -1.  level_super
+ * [n_seg]: the new initial state's level (-1 with AMX_LATPOST_NO_FINAL).  Every output nullable; info's discrete fields are filled. */
+int  amx_latpost_plan_host(const amx_latpost* h, int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target,
+                           const float* arc_weight, const float* arc_risk, const int32_t* initial, const uint8_t* final_flag,
+                           const float* final_weight, const float* final_risk, int32_t* discover_index, int32_t* level_backward,
+                           int32_t* level_forward, int32_t* level_super, long* in_offsets, int32_t* in_arc, int32_t* final_order,
+                           amx_latpost_info* info);
+/* DIAGNOSTIC (tests, probes): the potentials of the last amx_latpost_run_dev, per state counted over the call; generalized_*: EXPECTATION
+ * (else zeros).  Every array nullable. */
+int  amx_latpost_last_potentials(const amx_latpost* h, long n_states, double* forward, double* backward, double* generalized_forward,
+                                 double* generalized_backward);
+/* DIAGNOSTIC (tools/latpost_probe.py): host wall time of the last amx_latpost_run_dev's plan and of packing and uploading its tables, in ms;
+ * the kernels' times are the event timers' (amx_profile_get "latpost_potentials", "latpost_arcs") */
+int  amx_latpost_last_timing(const amx_latpost* h, double* plan_ms, double* upload_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -2758,3 +2758,129 @@ class EbwEstimator:
         return new, dict(i_smoothing_objective=info.i_smoothing_objective, sigma_minimum=info.sigma_minimum, n_removed=info.n_removed,
                          n_clamped=info.n_clamped, n_mean_fallback=info.n_mean_fallback, n_floored=info.n_floored,
                          iteration_constants=icd[:new["means"].shape[0]].copy())
+
+
+class LatticePosterior:
+    """Arc posteriors of word lattices, a batch per call, left on the device: Fsa::posterior64 (mode "log"), posterior64 followed by
+    Fsa::expm ("prob") and Fsa::posteriorE over an accuracy lattice ("expectation"), in f64 in the log semiring, every sum in the
+    reference's order.  A lattice is a dict of host arrays: arc_offsets [n + 1] (state s owns the arcs [arc_offsets[s], arc_offsets[s + 1])
+    in the automaton's own order), arc_target (state ids of this lattice), arc_weight, initial, final_flag [n], final_weight [n] and, for
+    "expectation", arc_risk and final_risk.  The contract (the one fused multiply-add of the expectation pass) is the context's."""
+
+    MODES = {"log": _lib.AMX_LATPOST_LOG, "prob": _lib.AMX_LATPOST_PROB, "expectation": _lib.AMX_LATPOST_EXPECTATION}
+    INFO = tuple(n for n, _ in _lib.LatpostInfo._fields_)
+
+    def __init__(self, ctx, mode="log", normalize=True, v_normalized=True, tolerance=100, potentials="auto"):
+        self.L = _lib.lib()
+        self.ctx, self.h = ctx, None
+        if mode not in self.MODES:
+            raise ValueError("LatticePosterior: unknown mode %r" % (mode,))
+        if potentials not in ("auto", "global"):
+            raise ValueError("LatticePosterior: potentials must be 'auto' or 'global', not %r" % (potentials,))
+        cfg = _lib.LatpostCfg()
+        self.L.amx_latpost_cfg_default(C.byref(cfg))
+        cfg.mode, cfg.normalize, cfg.v_normalized, cfg.tolerance = self.MODES[mode], int(bool(normalize)), int(bool(v_normalized)), int(tolerance)
+        cfg.potentials = _lib.AMX_LATPOST_POTENTIALS_GLOBAL if potentials == "global" else _lib.AMX_LATPOST_POTENTIALS_AUTO
+        h = C.c_void_p()
+        _lib.check(self.L.amx_latpost_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h, self.mode = h, mode
+
+    def close(self):
+        if self.h:
+            self.L.amx_latpost_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def kernel_shape():
+        """dict(threads, lds_states, wave_arcs): the potentials kernel's workgroup, the largest segment (states + 1) kept in LDS, the
+        number of arcs from which a wave shares a state"""
+        t, s, w = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_latpost_kernel_shape(C.byref(t), C.byref(s), C.byref(w))
+        return dict(threads=t.value, lds_states=s.value, wave_arcs=w.value)
+
+    def tables(self, lattices):
+        """the call's CSR tables from a list of lattice dicts"""
+        who, e = "LatticePosterior", self.mode == "expectation"
+        so, ao, tgt, w, r, ini, ff, fw, fr = [0], [np.zeros(1, np.int64)], [], [], [], [], [], [], []
+        n_arcs = 0
+        for k, lat in enumerate(lattices):
+            off = np.ascontiguousarray(lat["arc_offsets"], dtype=np.int64)
+            n = len(off) - 1
+            t = np.ascontiguousarray(lat["arc_target"], dtype=np.int32)
+            if n < 0 or (n >= 0 and (off[0] != 0 or off[-1] != len(t))) or len(lat["arc_weight"]) != len(t) or len(lat["final_flag"]) != n or \
+                    len(lat["final_weight"]) != n:
+                raise ValueError("%s: lattice %d: %d states, %d arc offsets ending at %s, %d targets, %d weights" %
+                                 (who, k, n, len(off), off[-1] if len(off) else None, len(t), len(lat["arc_weight"])))
+            if e and ("arc_risk" not in lat or "final_risk" not in lat or len(lat["arc_risk"]) != len(t) or len(lat["final_risk"]) != n):
+                raise ValueError("%s: lattice %d: mode 'expectation' needs arc_risk and final_risk" % (who, k))
+            so.append(so[-1] + n)
+            ao.append(off[1:] + n_arcs)
+            n_arcs += len(t)
+            tgt.append(t), w.append(np.asarray(lat["arc_weight"], np.float32)), ini.append(int(lat["initial"]))
+            ff.append(np.asarray(lat["final_flag"]).astype(np.uint8)), fw.append(np.asarray(lat["final_weight"], np.float32))
+            if e:
+                r.append(np.asarray(lat["arc_risk"], np.float32)), fr.append(np.asarray(lat["final_risk"], np.float32))
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dt), dtype=dt)   # noqa: E731
+        return dict(n_seg=len(lattices), state_offsets=np.array(so, np.int64), arc_offsets=cat(ao, np.int64), arc_target=cat(tgt, np.int32),
+                    arc_weight=cat(w, np.float32), arc_risk=cat(r, np.float32) if e else None, initial=np.array(ini, np.int32),
+                    final_flag=cat(ff, np.uint8), final_weight=cat(fw, np.float32), final_risk=cat(fr, np.float32) if e else None)
+
+    @classmethod
+    def _info(cls, infos):
+        return [{n: getattr(i, n) for n in cls.INFO} for i in infos]
+
+    def run(self, lattices):
+        """-> (arc weights, final weights, info): two f32 device tensors, one value per arc in the order of the input (lattice after
+        lattice) and one per state, and a list of dicts per lattice (total_inv, total_inv_f32, expectation, forward_flow, backward_flow,
+        flows_agree, vanishing_flow, reason, the counts).  A refused input raises AmxError and leaves nothing behind."""
+        import torch
+        t = self.tables(lattices)
+        n_states, n_arcs = int(t["state_offsets"][-1]), len(t["arc_target"])
+        dev = torch.device("cuda", self.ctx.device)
+        arc_out, final_out = torch.empty(max(n_arcs, 1), dtype=torch.float32, device=dev), torch.empty(max(n_states, 1), dtype=torch.float32, device=dev)
+        info = self.run_dev(t, arc_out, final_out)
+        return arc_out[:n_arcs], final_out[:n_states], info
+
+    def run_dev(self, t, arc_out_dev, final_out_dev):
+        """the same into buffers of the caller's (t: what tables() returns)"""
+        infos = (_lib.LatpostInfo * max(t["n_seg"], 1))()
+        _lib.check(self.L.amx_latpost_run_dev(self.h, t["n_seg"], _ptr(t["state_offsets"]), _ptr(t["arc_offsets"]), _ptr(t["arc_target"]), _ptr(t["arc_weight"]),
+                                              _ptr(t["arc_risk"]), _ptr(t["initial"]), _ptr(t["final_flag"]), _ptr(t["final_weight"]), _ptr(t["final_risk"]),
+                                              _ptr(arc_out_dev), _ptr(final_out_dev), C.cast(infos, C.c_void_p)))
+        return self._info(infos[:t["n_seg"]])
+
+    def plan(self, lattices):
+        """the host plan alone (no device): dict(discover_index, level_backward, level_forward, level_super, in_offsets, in_arc, final_order,
+        info) over the call's states and arcs"""
+        t = self.tables(lattices)
+        n_states, n_arcs, n_seg = int(t["state_offsets"][-1]), len(t["arc_target"]), t["n_seg"]
+        out = dict(discover_index=np.zeros(n_states, np.int32), level_backward=np.zeros(n_states, np.int32), level_forward=np.zeros(n_states, np.int32),
+                   level_super=np.zeros(n_seg, np.int32), in_offsets=np.zeros(n_states + 1, np.int64), in_arc=np.full(n_arcs, -1, np.int32),
+                   final_order=np.zeros(n_states, np.int32))
+        infos = (_lib.LatpostInfo * max(n_seg, 1))()
+        _lib.check(self.L.amx_latpost_plan_host(self.h, n_seg, _ptr(t["state_offsets"]), _ptr(t["arc_offsets"]), _ptr(t["arc_target"]), _ptr(t["arc_weight"]),
+                                                _ptr(t["arc_risk"]), _ptr(t["initial"]), _ptr(t["final_flag"]), _ptr(t["final_weight"]), _ptr(t["final_risk"]),
+                                                *(_ptr(out[k]) for k in ("discover_index", "level_backward", "level_forward", "level_super", "in_offsets",
+                                                                         "in_arc", "final_order")), C.cast(infos, C.c_void_p)))
+        out["info"] = self._info(infos[:n_seg])
+        out["tables"] = t
+        return out
+
+    def last_timing(self):
+        """DIAGNOSTIC: (plan ms, upload ms) of the last run: host wall time of the plan and of packing and uploading the tables"""
+        a, b = C.c_double(), C.c_double()
+        _lib.check(self.L.amx_latpost_last_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_potentials(self, n_states):
+        """DIAGNOSTIC: dict(forward, backward, generalized_forward, generalized_backward) of the last run, per state over the call"""
+        out = {k: np.zeros(n_states, np.float64) for k in ("forward", "backward", "generalized_forward", "generalized_backward")}
+        _lib.check(self.L.amx_latpost_last_potentials(self.h, n_states, *(_ptr(out[k]) for k in ("forward", "backward", "generalized_forward",
+                                                                                                 "generalized_backward"))))
+        return out

@@ -183,6 +183,17 @@ class EbwOffsets(C.Structure):
                                         "objective", "size", "n_slots", "n_means", "n_covariances", "dim")]
 
 
+class LatpostCfg(C.Structure):
+    _fields_ = [("mode", C.c_int), ("normalize", C.c_int), ("v_normalized", C.c_int), ("tolerance", C.c_int), ("potentials", C.c_int)]
+
+
+class LatpostInfo(C.Structure):
+    _fields_ = [("total_inv", C.c_double), ("total_inv_f32", C.c_float), ("expectation", C.c_float), ("forward_flow", C.c_float),
+                ("backward_flow", C.c_float)] + \
+        [(n, C.c_int) for n in ("flows_agree", "vanishing_flow", "reason", "states_reached", "arcs_reached", "states_coreached",
+                                "undefined_states", "undefined_arcs", "levels_forward", "levels_backward")]
+
+
 class EbwEstimateCfg(C.Structure):
     _fields_ = [("min_observation_weight", C.c_double), ("min_relative_weight", C.c_double), ("min_variance", C.c_double),
                 ("normalize_mixture_weights", C.c_int), ("iteration_constants", C.c_int), ("step_size", C.c_double), ("minimum_icd", C.c_double),
@@ -585,11 +596,22 @@ SIGNATURES = {
     "amx_ebw_accumulator_combine": (C.c_int, [_P, _P, _P]),
     "amx_ebw_estimate_cfg_default": (None, [C.POINTER(EbwEstimateCfg)]),
     "amx_ebw_estimate": (C.c_int, [_P, _P, _P, _P, C.POINTER(EbwEstimateCfg), C.POINTER(_P), C.POINTER(EbwEstimateInfo), _P]),
+    "amx_latpost_cfg_default": (None, [C.POINTER(LatpostCfg)]),
+    "amx_latpost_create": (C.c_int, [_P, C.POINTER(LatpostCfg), C.POINTER(_P)]),
+    "amx_latpost_destroy": (None, [_P]),
+    "amx_latpost_kernel_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_latpost_run_dev": (C.c_int, [_P, C.c_int] + [_P] * 12),
+    "amx_latpost_plan_host": (C.c_int, [_P, C.c_int] + [_P] * 17),
+    "amx_latpost_last_potentials": (C.c_int, [_P, C.c_long, _P, _P, _P, _P]),
+    "amx_latpost_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
 AMX_MLLR_FULL, AMX_MLLR_SHIFT, AMX_MLLR_BAND, AMX_MLLR_SEMI_TIED = 0, 1, 2, 3
 AMX_EBW_IC_GLOBAL_RWTH, AMX_EBW_IC_LOCAL_RWTH, AMX_EBW_IC_CAMBRIDGE = 0, 1, 2
 AMX_EBW_ESTIMATOR_EBW, AMX_EBW_ESTIMATOR_RPROP = 0, 1
+AMX_LATPOST_LOG, AMX_LATPOST_PROB, AMX_LATPOST_EXPECTATION = 0, 1, 2
+AMX_LATPOST_OK, AMX_LATPOST_NO_FINAL = 0, 1
+AMX_LATPOST_POTENTIALS_AUTO, AMX_LATPOST_POTENTIALS_GLOBAL = 0, 1
 AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2
 AMX_COMM_ID_BYTES = 128
 
