@@ -2087,6 +2087,17 @@ int  amx_ebw_accumulate_objective(amx_ebw* h, float objective, double* acc_dev);
  * 1 denominator, the collected weight and the slot (offset of the best density in the mixture-weight block, -1: no density).  Every array
  * nullable; all NULL: *n_keys only. */
 int  amx_ebw_last_keys(const amx_ebw* h, int capacity, int* n_keys, long* frame, int32_t* mixture, int32_t* side, double* weight, int32_t* slot);
+/* DIAGNOSTIC, for tests and probes.  amx_ebw_kernel_shape: elements per workgroup of the sort and the scan, keys a chain stages at a time,
+ * threads per workgroup (any pointer nullable).  amx_ebw_last_shape: what the last amx_ebw_accumulate_dev ran -- passes and workgroups of
+ * the item sort and of the list sort, and whether the scan of a sort's digit table (256 x workgroups) took more than one level; all 0
+ * for a call that was refused or ended before the sort */
+typedef struct {
+    int item_sort_passes, list_sort_passes;
+    int item_blocks, list_blocks;
+    int item_table_recursed, list_table_recursed;
+} amx_ebw_call_shape;
+void amx_ebw_kernel_shape(int* block_items, int* stage_keys, int* threads);
+int  amx_ebw_last_shape(const amx_ebw* h, amx_ebw_call_shape* out);
 
 /* ---- host side (ebw_host.cpp): `acc` is the flat buffer in host memory, `topology` the model the statistics were accumulated with
  * (its means, variances and weights are not read).  amx_ebw_topology_accumulator_size: amx_ebw_accumulator_size from the topology alone

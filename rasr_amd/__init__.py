@@ -2658,6 +2658,20 @@ class EbwAccumulator:
         """accumulateObjectiveFunction: one segment's objective (f32, widened) into the buffer's last cell"""
         _lib.check(self.L.amx_ebw_accumulate_objective(self.h, float(np.float32(objective)), _ptr(acc_dev)))
 
+    @staticmethod
+    def kernel_shape():
+        """(elements per workgroup of the sort and the scan, keys a chain stages at a time, threads per workgroup)"""
+        b, s, t = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_ebw_kernel_shape(C.byref(b), C.byref(s), C.byref(t))
+        return b.value, s.value, t.value
+
+    def last_shape(self):
+        """what the last accumulate_dev ran: dict(item_sort_passes, list_sort_passes, item_blocks, list_blocks, item_table_recursed,
+        list_table_recursed), all 0 for a call that ended before the sort"""
+        s = _lib.EbwCallShape()
+        _lib.check(self.L.amx_ebw_last_shape(self.h, C.byref(s)))
+        return {n: (bool(getattr(s, n)) if n.endswith("recursed") else int(getattr(s, n))) for n, _ in s._fields_}
+
     def last_keys(self):
         """the keys of the last accumulate_dev in ascending (frame, mixture, side): dict(frame, mixture, side, weight, slot)"""
         n = C.c_int(0)

@@ -183,6 +183,11 @@ class EbwOffsets(C.Structure):
                                         "objective", "size", "n_slots", "n_means", "n_covariances", "dim")]
 
 
+class EbwCallShape(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("item_sort_passes", "list_sort_passes", "item_blocks", "list_blocks", "item_table_recursed",
+                                       "list_table_recursed")]
+
+
 class LatpostCfg(C.Structure):
     _fields_ = [("mode", C.c_int), ("normalize", C.c_int), ("v_normalized", C.c_int), ("tolerance", C.c_int), ("potentials", C.c_int)]
 
@@ -590,6 +595,8 @@ SIGNATURES = {
     "amx_ebw_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "amx_ebw_accumulate_objective": (C.c_int, [_P, C.c_float, _P]),
     "amx_ebw_last_keys": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P, _P]),
+    "amx_ebw_kernel_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_ebw_last_shape": (C.c_int, [_P, C.POINTER(EbwCallShape)]),
     "amx_ebw_topology_accumulator_size": (C.c_long, [_P]),
     "amx_ebw_accumulator_write": (C.c_int, [_P, _P, C.c_char_p]),
     "amx_ebw_accumulator_read": (C.c_int, [_P, C.c_char_p, _P]),

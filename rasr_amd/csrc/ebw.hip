@@ -382,6 +382,7 @@ struct amx_ebw {
     long long             nk = 0;
     amx_ebw_offsets       off{};
     int                   n_keys = 0, mix_bits = 1;   // the last call's keys
+    amx_ebw_call_shape    last{};                     // ... and the launches it ran
     // per-call workspace
     amx::DevBuf<long long>          d_off;       // frame, arc and item offsets
     amx::DevBuf<float>              d_arc_w;
@@ -408,13 +409,15 @@ int bit_length(long long v) {   // bits that hold every value of [0, v]
     return b;
 }
 
-// exclusive scan in place; ws holds the block totals of every level
-int ebw_scan(hipStream_t st, int* data, long long n, int* ws) {
+// exclusive scan in place; ws holds the block totals of every level.  *levels (nullable) counts the levels that ran
+int ebw_scan(hipStream_t st, int* data, long long n, int* ws, int* levels = nullptr) {
     const long long nb = (n + amx::kEbwBlock - 1) / amx::kEbwBlock;
+    if (levels)
+        ++*levels;
     hipLaunchKernelGGL(amx::ebw_scan_block_kernel, dim3((unsigned)nb), dim3(amx::kEbwThreads), 0, st, data, n, ws);
     AMX_HIP(hipGetLastError());
     if (nb > 1) {
-        AMX_TRY(ebw_scan(st, ws, nb, ws + nb));
+        AMX_TRY(ebw_scan(st, ws, nb, ws + nb, levels));
         hipLaunchKernelGGL(amx::ebw_scan_add_kernel, dim3((unsigned)amx::ceil_div(n, amx::kEbwThreads)), dim3(amx::kEbwThreads), 0, st, data, n,
                            (const int*)ws);
         AMX_HIP(hipGetLastError());
@@ -431,19 +434,26 @@ size_t ebw_scan_ws(long long n) {
     return total + 1;
 }
 
-// stable sort of (code, val) by the low `bits` bits of code; *side: which of the two buffers holds the result
-int ebw_sort(amx_ebw* h, hipStream_t st, amx::DevBuf<unsigned long long>* code, amx::DevBuf<uint32_t>* val, long long n, int bits, int* side) {
+// stable sort of (code, val) by the low `bits` bits of code; *side: which of the two buffers holds the result; what ran goes to
+// *passes, *blocks and *recursed (the scan of the digit table took more than one level)
+int ebw_sort(amx_ebw* h, hipStream_t st, amx::DevBuf<unsigned long long>* code, amx::DevBuf<uint32_t>* val, long long n, int bits, int* side,
+             int* passes, int* blocks, int* recursed) {
     const int nb = (int)((n + amx::kEbwBlock - 1) / amx::kEbwBlock);
     if (h->d_table.capacity() < (size_t)256 * nb || h->d_scan_ws.capacity() < ebw_scan_ws(256ll * nb))
         AMX_HIP(hipStreamSynchronize(st));   // a workspace that grows is freed first: nothing in flight may still read it
     AMX_TRY(h->d_table.reserve((size_t)256 * nb));
     AMX_TRY(h->d_scan_ws.reserve(ebw_scan_ws(256ll * nb)));
     int cur = 0;
+    *passes = 0, *blocks = nb, *recursed = 0;
     for (int shift = 0; shift < bits; shift += 8, cur ^= 1) {
+        int levels = 0;
         hipLaunchKernelGGL(amx::ebw_sort_count_kernel, dim3((unsigned)nb), dim3(amx::kEbwThreads), 0, st, (const unsigned long long*)code[cur].get(), n, shift,
                            nb, h->d_table.get());
         AMX_HIP(hipGetLastError());
-        AMX_TRY(ebw_scan(st, h->d_table.get(), 256ll * nb, h->d_scan_ws.get()));
+        AMX_TRY(ebw_scan(st, h->d_table.get(), 256ll * nb, h->d_scan_ws.get(), &levels));
+        ++*passes;
+        if (levels > 1)
+            *recursed = 1;
         hipLaunchKernelGGL(amx::ebw_sort_place_kernel, dim3((unsigned)nb), dim3(amx::kEbwThreads), 0, st, (const unsigned long long*)code[cur].get(),
                            (const uint32_t*)val[cur].get(), n, shift, nb, (const int*)h->d_table.get(), code[cur ^ 1].get(), val[cur ^ 1].get());
         AMX_HIP(hipGetLastError());
@@ -536,6 +546,7 @@ int amx_ebw_accumulate_dev(amx_ebw* h, const float* feats_dev, int feats_ld, int
                            double* acc_dev) {
     const char* who = "amx_ebw_accumulate_dev";
     AMX_REQUIRE(h, AMX_ERR_INVALID, "%s: NULL handle", who);
+    h->last = amx_ebw_call_shape{};   // before any refusal: the shape is this call's, never the one before's
     AMX_REQUIRE(n_seg >= 0 && feats_ld >= h->D, AMX_ERR_INVALID, "%s: n_seg %d, feats_ld %d (dimension %d)", who, n_seg, feats_ld, h->D);
     AMX_REQUIRE(h->gmm.ctx, AMX_ERR_STATE, "%s: host-only gmm handle (created without a context)", who);
     h->n_keys = 0;
@@ -637,7 +648,8 @@ int amx_ebw_accumulate_dev(amx_ebw* h, const float* feats_dev, int feats_ld, int
     int side = 0;
     {
         amx::ScopedKernelTimer timer(ctx, "ebw_sort_items");
-        AMX_TRY(ebw_sort(h, st, h->d_code, h->d_val, n_items, code_bits + 1, &side));
+        AMX_TRY(ebw_sort(h, st, h->d_code, h->d_val, n_items, code_bits + 1, &side, &h->last.item_sort_passes, &h->last.item_blocks,
+                         &h->last.item_table_recursed));
     }
     const unsigned long long* s_code = h->d_code[side].get();
     const uint32_t*           s_val  = h->d_val[side].get();
@@ -692,7 +704,8 @@ int amx_ebw_accumulate_dev(amx_ebw* h, const float* feats_dev, int feats_ld, int
                            h->gmm.d_mix_off, h->gmm.d_k_dens, h->gmm.d_d_mean, h->gmm.d_d_cov, h->nk, (long long)h->gmm.n_mean, list_end,
                            h->d_key_slot.get(), h->d_ecode[0].get(), h->d_eval[0].get());
         AMX_HIP(hipGetLastError());
-        AMX_TRY(ebw_sort(h, st, h->d_ecode, h->d_eval, n_entries, list_bits + 1, &side));
+        AMX_TRY(ebw_sort(h, st, h->d_ecode, h->d_eval, n_entries, list_bits + 1, &side, &h->last.list_sort_passes, &h->last.list_blocks,
+                         &h->last.list_table_recursed));
         AMX_HIP(hipMemsetAsync(h->d_lists.get(), 0, (size_t)2 * n_lists * sizeof(int), st));
         hipLaunchKernelGGL(amx::ebw_bounds_kernel, dim3((unsigned)amx::ceil_div(n_entries, amx::kEbwThreads)), dim3(amx::kEbwThreads), 0, st,
                            (const unsigned long long*)h->d_ecode[side].get(), n_entries, list_end, h->d_lists.get(), h->d_lists.get() + n_lists);
@@ -715,6 +728,21 @@ int amx_ebw_accumulate_dev(amx_ebw* h, const float* feats_dev, int feats_ld, int
         AMX_HIP(hipGetLastError());
     }
     AMX_HIP(hipStreamSynchronize(st));   // the workspace is the handle's, the tables are this call's
+    return AMX_OK;
+}
+
+void amx_ebw_kernel_shape(int* block_items, int* stage_keys, int* threads) {
+    if (block_items)
+        *block_items = amx::kEbwBlock;
+    if (stage_keys)
+        *stage_keys = amx::kEbwStage;
+    if (threads)
+        *threads = amx::kEbwThreads;
+}
+
+int amx_ebw_last_shape(const amx_ebw* h, amx_ebw_call_shape* out) {
+    AMX_REQUIRE(h && out, AMX_ERR_INVALID, "amx_ebw_last_shape: NULL argument");
+    *out = h->last;
     return AMX_OK;
 }
 

@@ -76,16 +76,19 @@ __device__ __forceinline__ float gmm_distance(const float (&x)[DIM], const float
     return result;
 }
 
-// runtime-dimension variant: features live in LDS as [dim][64] (one column per lane)
-template<bool FMA = false>
+// runtime-dimension variant: features live in LDS as [dim][64] (one column per lane, STRIDE 64).  A workgroup's 256 frames take 1 KB of
+// LDS per dimension and gfx950 has 160 KB: a row of more than kGmmRtLdsDim components stays in memory and is read from there (STRIDE 1)
+// with the same arithmetic, by kernel instances of their own (DIM == -1), so that the instances for rows that fit are what they were
+constexpr int kGmmRtLdsDim = 160;
+template<bool FMA = false, int STRIDE = 64>
 __device__ __forceinline__ float gmm_distance_rt(const float* xs, int dim, const float* __restrict__ mu, const float* __restrict__ is) {
     float     l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f;
     const int eff = dim & ~3;
     for (int i = 0; i < eff; i += 4) {
-        float d0 = (mu[i] - xs[i * 64]) * is[i];
-        float d1 = (mu[i + 1] - xs[(i + 1) * 64]) * is[i + 1];
-        float d2 = (mu[i + 2] - xs[(i + 2) * 64]) * is[i + 2];
-        float d3 = (mu[i + 3] - xs[(i + 3) * 64]) * is[i + 3];
+        float d0 = (mu[i] - xs[i * STRIDE]) * is[i];
+        float d1 = (mu[i + 1] - xs[(i + 1) * STRIDE]) * is[i + 1];
+        float d2 = (mu[i + 2] - xs[(i + 2) * STRIDE]) * is[i + 2];
+        float d3 = (mu[i + 3] - xs[(i + 3) * STRIDE]) * is[i + 3];
         l0       = sq_acc<FMA>(d0, l0);
         l1       = sq_acc<FMA>(d1, l1);
         l2       = sq_acc<FMA>(d2, l2);
@@ -94,7 +97,7 @@ __device__ __forceinline__ float gmm_distance_rt(const float* xs, int dim, const
     float result = 0.f;
     result       = result + ((l0 + l1) + (l2 + l3));
     for (int i = eff; i < dim; ++i) {
-        float df = (mu[i] - xs[i * 64]) * is[i];
+        float df = (mu[i] - xs[i * STRIDE]) * is[i];
         result   = sq_acc<FMA>(df, result);
     }
     return result;
@@ -154,7 +157,8 @@ struct SumState {
     static constexpr bool kTwoPass = true;
 };
 
-// DIM > 0: features in registers; DIM == 0: runtime dimension, features in LDS
+// DIM > 0: features in registers; DIM == 0: runtime dimension, features in LDS; DIM == -1: runtime dimension above kGmmRtLdsDim,
+// features read from memory
 struct GmmDims {
     int T, dim, n_mix, mix_tile;
 };
@@ -190,7 +194,7 @@ __global__ __launch_bounds__(256) void gmm_direct_kernel(const float* __restrict
         for (int i = 0; i < DIM; ++i)
             x[i] = p.feats[(size_t)tt * DIM + i];
     }
-    else {
+    else if (DIM == 0) {
         xs = xs_all + wave * 64 * p.dim + lane;
         for (int i = 0; i < p.dim; ++i)
             xs[i * 64] = p.feats[(size_t)tt * p.dim + i];
@@ -203,6 +207,8 @@ __global__ __launch_bounds__(256) void gmm_direct_kernel(const float* __restrict
         const float* is = p.isr + (size_t)p.k_cov[k] * (DIM > 0 ? DIM : p.dim);
         if (DIM > 0)
             return gmm_distance<(DIM > 0 ? DIM : 1), FMA>(x, mu, is);
+        if (DIM < 0)
+            return gmm_distance_rt<FMA, 1>(p.feats + (size_t)tt * p.dim, p.dim, mu, is);
         return gmm_distance_rt<FMA>(xs, p.dim, mu, is);
     };
     for (int m = m0; m < m1; ++m) {
@@ -581,7 +587,7 @@ __global__ __launch_bounds__(256) void gmm_dist_kernel(const float* __restrict__
         for (int i = 0; i < DIM; ++i)
             x[i] = p.feats[(size_t)tt * DIM + i];
     }
-    else {
+    else if (DIM == 0) {
         xs = xs_all + wave * 64 * p.dim + lane;
         for (int i = 0; i < p.dim; ++i)
             xs[i * 64] = p.feats[(size_t)tt * p.dim + i];
@@ -600,6 +606,8 @@ __global__ __launch_bounds__(256) void gmm_dist_kernel(const float* __restrict__
             float        dist;
             if (DIM > 0)
                 dist = gmm_distance<(DIM > 0 ? DIM : 1), FMA>(x, mu, is);
+            else if (DIM < 0)
+                dist = gmm_distance_rt<FMA, 1>(p.feats + (size_t)tt * p.dim, p.dim, mu, is);
             else
                 dist = gmm_distance_rt<FMA>(xs, p.dim, mu, is);
             q[j] = dist;
@@ -1880,6 +1888,13 @@ int launch_direct(amx_gmm* h, const amx::GmmParams& p, dim3 grid) {
         constexpr int D   = decltype(dc)::value;
         const size_t  lds = D ? 0 : (size_t)4 * 64 * h->dim * sizeof(float);
         with_flag(h->contract_fma, [&](auto fc) {
+            if constexpr (D == 0) {
+                if (h->dim > amx::kGmmRtLdsDim) {  // a row that LDS cannot hold: the instance that reads it from memory
+                    hipLaunchKernelGGL((amx::gmm_direct_kernel<-1, State, decltype(fc)::value>), grid, dim3(256), 0, h->ctx->stream, p.feats, p.scores,
+                                       p.best, p.mix_off, p.k_mean, p.k_cov, p.k_c64, p.k_c32, p.means, p.isr, dims);
+                    return;
+                }
+            }
             hipLaunchKernelGGL((amx::gmm_direct_kernel<D, State, decltype(fc)::value>), grid, dim3(256), lds, h->ctx->stream, p.feats, p.scores, p.best,
                                p.mix_off, p.k_mean, p.k_cov, p.k_c64, p.k_c32, p.means, p.isr, dims);
         });
@@ -1899,6 +1914,10 @@ int launch_dist(amx_gmm* h, const amx::GmmDistParams& p, dim3 grid, double* dist
         if constexpr (D != 0) {  // (the fallback has no staging form)
             if (stage)
                 return with_flag(h->contract_fma, [&](auto fc) { launch(amx::gmm_dist_kernel<D, true, decltype(fc)::value>, (size_t)256 * (D + 1) * sizeof(float)); });
+        }
+        if constexpr (D == 0) {
+            if (h->dim > amx::kGmmRtLdsDim)  // a row that LDS cannot hold: the instance that reads it from memory
+                return with_flag(h->contract_fma, [&](auto fc) { launch(amx::gmm_dist_kernel<-1, false, decltype(fc)::value>, 0); });
         }
         with_flag(h->contract_fma, [&](auto fc) { launch(amx::gmm_dist_kernel<D, false, decltype(fc)::value>, D ? 0 : (size_t)4 * 64 * h->dim * sizeof(float)); });
     });

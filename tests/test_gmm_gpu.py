@@ -52,6 +52,16 @@ def test_dimensions_including_sse_tail(ctx, dim):
     assert_exact(ctx, model, feats(130, dim, 21))
 
 
+@pytest.mark.parametrize("tuning", [None, "contract=fma"])
+@pytest.mark.parametrize("kind", ["cart", "tied"])
+@pytest.mark.parametrize("dim", [160, 161, 256, 300])
+def test_dimensions_past_the_lds_of_the_runtime_path(ctx, dim, kind, tuning):
+    """the runtime-dimension kernels keep a workgroup's frames in LDS, 1 KB per dimension: 160 is the widest row that fits, a wider one
+    is read from memory.  Both models' kernels (gmm_direct_kernel, gmm_dist_kernel), both contracts, more than one workgroup of frames"""
+    model = synth.gmm_cart(9, 1, 4, dim, seed=dim, pooled=False) if kind == "cart" else synth.gmm_tied(11, 8, dim, seed=dim, pooled=True)
+    assert_exact(ctx, model, feats(300, dim, dim + 1), tuning=tuning)
+
+
 def test_scales(ctx):
     model = synth.gmm_cart(50, 2, 6, 40, seed=9, pooled=False)
     assert_exact(ctx, model, feats(100, 40, 10), mixture_weight_scale=0.7, gaussian_scale=1.3)
