@@ -2278,6 +2278,120 @@ int  amx_latpost_last_potentials(const amx_latpost* h, long n_states, double* fo
  * the kernels' times are the event timers' (amx_profile_get "latpost_potentials", "latpost_arcs") */
 int  amx_latpost_last_timing(const amx_latpost* h, double* plan_ms, double* upload_ms);
 
+/* ------------------------------------------------------------------ NN sequence-discriminative training (MMI, ME)
+ * Nn::SegmentwiseNnTrainer in full-batch mode (Nn/SegmentwiseNnTrainer.cc:121-250 processWordLattice) for a batch of segments per
+ * call, on an amx_nntrain handle whose mask has BASE (and GRADIENT for anything but the base statistics): the handle's weights, its
+ * workspace and its accumulator layout are shared, so amx_nnstat_write / _combine and amx_nntrain_estimate take the result as it is.
+ * The model comes with the log prior already removed from the top bias (Nn/SharedNeuralNetwork.cc:40-90).  What stays with the
+ * adapter: numerator extraction and Lattice::best (emission_dev is their result), the language-model part of the arc scores and the
+ * scales, the lattice forward-backward (amx_latpost_run_dev on the combined scores), `skip`, and objective[s].
+ *
+ * 1. amx_nnseq_forward_dev: the forward pass of amx_nntrain_accumulate_dev for every segment; feats_dev rows are absolute
+ *    ([frame_offsets[s], frame_offsets[s + 1]) belongs to segment s).  In the workspace segment s starts at a row that is a multiple
+ *    of AMX_NNTRAIN_CHUNK; the rows between two segments are zero in every layer input.  The sum of the padded lengths is at most
+ *    AMX_NNTRAIN_MAX_FRAMES.  Every layer's input and the linear top output are kept until the next forward.
+ * 2. amx_nnseq_arc_scores_dev: EmissionLatticeRescorerAutomaton::_score (Nn/EmissionLatticeRescorer.cc:208-231): per arc one f32 chain
+ *    from 0, score -= out[class_to_output[e], t] in item order; an arc without items keeps 0.  Tables as amx_ebw_accumulate_dev's, in
+ *    host memory (item_frame relative to the segment); the scores stay on the device.  Needs the linear top output (before an
+ *    accumulate with smoothing has replaced it by the softmax).
+ * 3. amx_nnseq_accumulate_dev: the rest of processWordLattice.  A pass is one accumulateStatisticsOnLattice (:619-627) over its own
+ *    arc and item tables with arc_weight_dev as amx_latpost_run_dev left it:
+ *      collection  an arc counts if (f64)w > weight_threshold, w = the f32 arc weight, times (f32)-1 first with `negate`
+ *                  (Fsa::multiply; Lattice/Accumulator.tcc:66-87); per (frame, emission) the widened weights are summed in f64 in arc
+ *                  order, then item order (Nn/LatticeAccumulators.hh:82-93); E[o, t] = (f32)((f64)E[o, t] + factor * collected),
+ *                  o = class_to_output[e] (LatticeAccumulators.cc:45-49), one write per cell and pass, passes in the order given: the
+ *                  reference's bits whatever its unordered_map walk was.  A stable key sort, no floating-point atomics.
+ *      roles       AMX_NNSEQ_ADD; AMX_NNSEQ_ADD_REJECT: then w[t] = 0 where E[alignment[t], t] < frame_rejection_threshold (f32;
+ *                  Nn/MmiSegmentwiseNnTrainer.cc:78-86), counted per segment; a cell that is not >= 0 (verify_ge) refuses the call;
+ *                  AMX_NNSEQ_ADD_REJECT_CLEAR: then E = 0 (Nn/MeSegmentwiseNnTrainer.cc:69-100).
+ *                  MMI: den PROB +1 [reject], num PROB -1.  ME: EXPECTATION -1, the same tables negated +1.  ME with rejection: the
+ *                  MMI denominator +1 [reject, clear] in front.
+ *      alignment   alignment[t] = class_to_output[emission_dev[t]] (AlignmentAccumulator); emission_dev is indexed by frame -
+ *                  frame_offsets[0]; a frame with 0xffffffff: "alignment vector failed", the segment is skipped and counted.
+ *                  w[t] = class_weights[alignment[t]] (:740-745; weights of 1 give the unweighted trainer's bits).
+ *      smoothing   if ce_smoothing_weight > 0 (:630-692): top += prior_scale * log_prior where prior_scale > 0 (one fused multiply-add
+ *                  per element, the convention stated for the regulariser's axpy), softmax as amx_ffnn_forward_dev(..,
+ *                  AMX_NN_TOP_SOFTMAX); E *= (f32)(1.0 - lambda); E = fmaf(lambda, p, E); E[alignment[t], t] += -lambda; the CE objective
+ *                  of a segment is one f32 chain obj -= logf(p[alignment[t], t]) * w[t] in frame order.  lambda == 1: the passes are
+ *                  not run, E starts from zero (:159-162).
+ *      gradient    E's columns times w (multiplyColumnsByScalars), backpropagation without a clip, gradients through the kernels of
+ *                  amx_nntrain_accumulate_dev.
+ *      base        classification errors of the top output as it then stands (softmax or linear) against the alignment, observations,
+ *                  total weight = sum |w|, objective[s] (f32, widened) -- the adapter forms it from amx_latpost_info.total_inv_f32 as
+ *                  the two trainers do (MMI: f32(den) - f32(num); ME: -f32(totalInv)).
+ * Order: a segment's gradient is formed in f32 from zero over its own chunks, as one amx_nntrain_accumulate_dev call forms it, then
+ * widened and added into acc_dev in segment order: a segment gives the same bits alone and in any batch, a batch the bits of one call
+ * per segment.  The f64 buffer is the library's choice, as for amx_nntrain_*: the reference's only instantiation
+ * (SegmentwiseNnTrainer<f32>) sums across segments in f32 inside BLAS, in no defined order.
+ * Checked on the device before acc_dev is written, AMX_ERR_INVALID naming the first offender: an item's frame outside its segment, an
+ * emission >= n_classes or of a disregarded class, an arc weight that is not finite, a label out of range or of a disregarded class, a
+ * negative cell under the rejection test.  Segments flagged in skip add nothing and are not checked.
+ * A segment whose alignment holds 0xffffffff is marked before the labels are checked, so nothing of it is checked either.
+ * Keys: the reference's Collector keys on (frame, emission), the library on (frame, class_to_output[emission]).  The two are the same
+ * keys because amx_nntrain_create refuses a class_to_output in which two classes share an output ("no one-to-one correspondence").
+ * Limits: at most 8 passes per call; at most 2^27 - 1 arcs and 2^27 - 1 items per table.
+ * The workspace is the nntrain handle's: forward, scores and accumulate of one batch belong together.  Any amx_nntrain_accumulate_dev /
+ * amx_nntrain_step_* call or another amx_nnseq handle's forward on the same nntrain handle in between takes the workspace, and the
+ * scores / accumulate call that follows returns AMX_ERR_STATE asking for the forward pass again.
+ * AMX_ERR_UNSUPPORTED naming the option: the stochastic per-segment update (full_batch = 0), accumulate_prior (the adapter has it from
+ * emission_dev and AMX_NNSTAT_CLASS_COUNTS), allophone-state labels (label_type != 0), and what amx_nntrain_create refuses. */
+typedef struct amx_nnseq amx_nnseq;
+enum { AMX_NNSEQ_ADD = 0, AMX_NNSEQ_ADD_REJECT = 1, AMX_NNSEQ_ADD_REJECT_CLEAR = 2 };
+enum { AMX_NNSEQ_SEG_OK = 0, AMX_NNSEQ_SEG_SKIPPED = 1, AMX_NNSEQ_SEG_NO_ALIGNMENT = 2 };
+typedef struct {
+    double       weight_threshold;          /* weight-threshold (an Mm::Weight), default Core::Type<f32>::epsilon */
+    float        ce_smoothing_weight;       /* 0..1, default 0 */
+    float        frame_rejection_threshold; /* 0..1, default 0 = off */
+    const float* log_prior;                 /* nullable [n_outputs]; read by the smoothing alone */
+    float        prior_scale;               /* default 0 */
+    int          full_batch;                /* default 1; 0 is AMX_ERR_UNSUPPORTED */
+    int          accumulate_prior;          /* default 0; 1 is AMX_ERR_UNSUPPORTED */
+    int          label_type;                /* default 0 = emission indices; anything else is AMX_ERR_UNSUPPORTED */
+    int          keep_lattice_error;        /* DIAGNOSTIC: keep a copy of E as the passes left it (amx_nnseq_get_error_signal, layer -1) */
+} amx_nnseq_cfg;
+typedef struct {
+    const long*    arc_offsets;    /* host [n_seg + 1] */
+    const long*    item_offsets;   /* host [n_arcs + 1] */
+    const int32_t* item_frame;     /* host, relative to the segment */
+    const int32_t* item_emission;  /* host */
+    const float*   arc_weight_dev; /* device [n_arcs] */
+    int            negate;
+    double         factor;
+    int            role;           /* AMX_NNSEQ_ADD* */
+} amx_nnseq_pass;
+typedef struct {
+    int      segments_processed, segments_skipped, segments_without_alignment;
+    long     observations, rejected_observations;
+    float    ce_objective;   /* ceObjectiveFunction_: the segments' values added in f32 in segment order */
+    int*      seg_reason;       /* nullable [n_seg]: AMX_NNSEQ_SEG_* */
+    uint32_t* seg_errors;       /* nullable [n_seg] */
+    uint32_t* seg_rejected;     /* nullable [n_seg] */
+    float*    seg_ce_objective; /* nullable [n_seg] */
+} amx_nnseq_info;
+void amx_nnseq_default_cfg(amx_nnseq_cfg* cfg);
+/* the nntrain handle must outlive this one; on a host-only nntrain handle this is a host-only handle (the checks alone) */
+int  amx_nnseq_create(amx_nntrain* train, const amx_nnseq_cfg* cfg, amx_nnseq** out);
+void amx_nnseq_destroy(amx_nnseq* h);
+int  amx_nnseq_forward_dev(amx_nnseq* h, const float* feats_dev, int feats_stride, int n_seg, const long* frame_offsets /*[n_seg+1]*/);
+int  amx_nnseq_arc_scores_dev(amx_nnseq* h, const long* arc_offsets /*[n_seg+1]*/, const long* item_offsets /*[n_arcs+1]*/,
+                              const int32_t* item_frame, const int32_t* item_emission, float* arc_score_dev);
+/* skip [n_seg] nullable; objective [n_seg] host f32; info nullable, its arrays nullable.  Synchronises the stream. */
+int  amx_nnseq_accumulate_dev(amx_nnseq* h, int n_pass, const amx_nnseq_pass* passes, const uint32_t* emission_dev, const uint8_t* skip,
+                              const float* objective, double* acc_dev, amx_nnseq_info* info);
+/* DIAGNOSTICS for tests and probes.  workspace_row: the workspace row of a segment's first frame after the last forward.  The getters
+ * copy rows [row, row + n) of the workspace: get_top which = 0 the linear top output, 1 the softmax p (AMX_ERR_STATE if the workspace
+ * holds the other) [n x n_outputs]; get_error_signal E of a layer [n x out_dim] as the last accumulate left it (the top layer's after
+ * smoothing and weighting), layer -1: the copy cfg.keep_lattice_error keeps [n x n_outputs]; get_weights w [n]. */
+int  amx_nnseq_workspace_row(const amx_nnseq* h, int segment, int* row);
+int  amx_nnseq_get_top(amx_nnseq* h, int which, int row, int n, float* out);
+int  amx_nnseq_get_error_signal(amx_nnseq* h, int layer, int row, int n, float* out);
+int  amx_nnseq_get_weights(amx_nnseq* h, int row, int n, float* out);
+/* elements per workgroup of the collection's sort, arcs a workgroup of the score kernel takes, items a wave of it stages at a time,
+ * threads per workgroup (any pointer nullable) */
+void amx_nnseq_kernel_shape(int* sort_block_items, int* score_block_arcs, int* score_stage_items, int* threads);
+/* passes and workgroups of the sort of the last accumulate's LAST pass; 0 where none ran */
+int  amx_nnseq_last_shape(const amx_nnseq* h, int* sort_passes, int* sort_blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -2898,3 +2898,148 @@ class LatticePosterior:
         _lib.check(self.L.amx_latpost_last_potentials(self.h, n_states, *(_ptr(out[k]) for k in ("forward", "backward", "generalized_forward",
                                                                                                  "generalized_backward"))))
         return out
+
+
+class SegmentwiseNnTrainer:
+    """Nn::SegmentwiseNnTrainer in full-batch mode (criteria MMI and ME) on a FeedForwardTrainer whose statistics are "base" and,
+    for anything but the base statistics, "gradient": forward pass of a batch of segments, arc scores from the network's output, and the
+    error signal collected from the arcs' posteriors, with frame rejection and cross-entropy smoothing, into the trainer's flat f64
+    accumulator (include/amx.h, "NN sequence-discriminative training").  The model carries the log prior removed from the top bias
+    already.  Numerator extraction, the best path (emission), the language-model part of the arc scores, the lattice forward-backward
+    (LatticePosterior), `skip` and `objective` stay with the caller.  Arc tables: dict(arc_offsets [n_seg + 1], item_offsets
+    [n_arcs + 1], item_frame, item_emission) of host arrays, the layout EbwAccumulator takes; item_frame counts from its segment's start."""
+
+    ROLES = {"add": _lib.AMX_NNSEQ_ADD, "reject": _lib.AMX_NNSEQ_ADD_REJECT, "reject-clear": _lib.AMX_NNSEQ_ADD_REJECT_CLEAR}
+    REASONS = {_lib.AMX_NNSEQ_SEG_OK: "ok", _lib.AMX_NNSEQ_SEG_SKIPPED: "skipped", _lib.AMX_NNSEQ_SEG_NO_ALIGNMENT: "no-alignment"}
+
+    def __init__(self, trainer, weight_threshold=None, ce_smoothing_weight=0.0, frame_rejection_threshold=0.0, log_prior=None, prior_scale=0.0,
+                 full_batch=True, accumulate_prior=False, label_type="emission-ids", keep_lattice_error=False):
+        self.L, self.trainer, self.ctx, self.h = _lib.lib(), trainer, trainer.ctx, None
+        cfg = _lib.NnSeqCfg()
+        self.L.amx_nnseq_default_cfg(C.byref(cfg))
+        if weight_threshold is not None:
+            cfg.weight_threshold = float(weight_threshold)
+        cfg.ce_smoothing_weight, cfg.frame_rejection_threshold, cfg.prior_scale = float(ce_smoothing_weight), float(frame_rejection_threshold), float(prior_scale)
+        self._prior = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float32)
+        if self._prior is not None and len(self._prior) != trainer.n_outputs:
+            raise ValueError("SegmentwiseNnTrainer: log_prior has %d entries, the network %d outputs" % (len(self._prior), trainer.n_outputs))
+        cfg.log_prior = _ptr(self._prior)
+        cfg.full_batch, cfg.accumulate_prior = int(bool(full_batch)), int(bool(accumulate_prior))
+        cfg.label_type = 0 if label_type == "emission-ids" else 1
+        cfg.keep_lattice_error = int(bool(keep_lattice_error))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_nnseq_create(trainer.h, C.byref(cfg), C.byref(h)))
+        self.h, self.n_seg = h, 0
+
+    def close(self):
+        if self.h:
+            self.L.amx_nnseq_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def kernel_shape():
+        """dict(sort_block_items, score_block_arcs, score_stage_items, threads)"""
+        v = [C.c_int() for _ in range(4)]
+        _lib.lib().amx_nnseq_kernel_shape(*(C.byref(x) for x in v))
+        return dict(zip(("sort_block_items", "score_block_arcs", "score_stage_items", "threads"), (x.value for x in v)))
+
+    @staticmethod
+    def _tables(t, who):
+        try:
+            return (np.ascontiguousarray(t["arc_offsets"], dtype=np.int64), np.ascontiguousarray(t["item_offsets"], dtype=np.int64),
+                    np.ascontiguousarray(t["item_frame"], dtype=np.int32), np.ascontiguousarray(t["item_emission"], dtype=np.int32))
+        except KeyError as e:
+            raise ValueError("%s: the arc tables lack %s" % (who, e))
+
+    def forward_dev(self, feats_dev, feats_stride, frame_offsets):
+        """feats_dev f32 [rows x feats_stride] on the device; segment s owns the rows [frame_offsets[s], frame_offsets[s + 1])"""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        _lib.check(self.L.amx_nnseq_forward_dev(self.h, _ptr(feats_dev), int(feats_stride), len(off) - 1, _ptr(off)))
+        self.n_seg, self.frame_offsets = len(off) - 1, off
+
+    def arc_scores_dev(self, tables, arc_score_dev):
+        """EmissionLatticeRescorer's acoustic arc scores into arc_score_dev f32 [n_arcs] (device)"""
+        ao, io, fr, em = self._tables(tables, "SegmentwiseNnTrainer.arc_scores_dev")
+        if len(ao) != self.n_seg + 1 or len(io) != int(ao[-1]) + 1 or len(fr) != int(io[-1]) or len(em) != len(fr):
+            raise ValueError("SegmentwiseNnTrainer.arc_scores_dev: the arc tables do not fit the %d segments of the forward pass" % self.n_seg)
+        _lib.check(self.L.amx_nnseq_arc_scores_dev(self.h, _ptr(ao), _ptr(io), _ptr(fr), _ptr(em), _ptr(arc_score_dev)))
+
+    def arc_scores(self, tables):
+        import torch
+        n = int(np.asarray(tables["arc_offsets"])[-1])
+        out = torch.zeros(max(n, 1), dtype=torch.float32, device=torch.device("cuda", self.ctx.device))
+        torch.cuda.synchronize()
+        self.arc_scores_dev(tables, out)
+        return out[:n]
+
+    def accumulate_dev(self, passes, emission_dev, objective, acc_dev, skip=None):
+        """passes: list of dict(tables=..., arc_weight_dev=f32 device tensor [n_arcs], factor=+-1.0, negate=False, role="add" |
+        "reject" | "reject-clear"); emission_dev u32 [frames] from frame_offsets[0] on (0xffffffff: no alignment); objective f32 [n_seg]
+        (host); skip [n_seg] or None.  -> dict(segments_processed, segments_skipped, segments_without_alignment, observations,
+        rejected_observations, ce_objective, seg_reason, seg_errors, seg_rejected, seg_ce_objective)"""
+        who, n = "SegmentwiseNnTrainer.accumulate_dev", self.n_seg
+        arr, keep = (_lib.NnSeqPass * max(len(passes), 1))(), []
+        for k, p in enumerate(passes):
+            ao, io, fr, em = self._tables(p["tables"], who)
+            if len(ao) != n + 1 or len(io) != int(ao[-1]) + 1 or len(fr) != int(io[-1]) or len(em) != len(fr):
+                raise ValueError("%s: pass %d: the arc tables do not fit the %d segments of the forward pass" % (who, k, n))
+            w = p["arc_weight_dev"]
+            if int(ao[-1]) and (w is None or w.numel() < int(ao[-1])):
+                raise ValueError("%s: pass %d: arc_weight_dev holds fewer than %d weights" % (who, k, int(ao[-1])))
+            keep.append((ao, io, fr, em, w))
+            arr[k] = _lib.NnSeqPass(_ptr(ao), _ptr(io), _ptr(fr), _ptr(em), _ptr(w), int(bool(p.get("negate", False))), float(p.get("factor", 1.0)),
+                                    self.ROLES[p.get("role", "add")])
+        obj = np.ascontiguousarray(objective, dtype=np.float32)
+        sk = None if skip is None else np.ascontiguousarray(skip).astype(np.uint8)
+        if len(obj) != n or (sk is not None and len(sk) != n):
+            raise ValueError("%s: objective and skip need one entry per segment (%d)" % (who, n))
+        info = _lib.NnSeqInfo()
+        out = dict(seg_reason=np.zeros(n, np.int32), seg_errors=np.zeros(n, np.uint32), seg_rejected=np.zeros(n, np.uint32), seg_ce_objective=np.zeros(n, np.float32))
+        for k, v in out.items():
+            setattr(info, k, _ptr(v))
+        _lib.check(self.L.amx_nnseq_accumulate_dev(self.h, len(passes), C.cast(arr, C.c_void_p), _ptr(emission_dev), _ptr(sk), _ptr(obj), _ptr(acc_dev), C.byref(info)))
+        for k in ("segments_processed", "segments_skipped", "segments_without_alignment", "observations", "rejected_observations", "ce_objective"):
+            out[k] = getattr(info, k)
+        return out
+
+    # ---- diagnostics
+    def workspace_row(self, segment):
+        r = C.c_int()
+        _lib.check(self.L.amx_nnseq_workspace_row(self.h, int(segment), C.byref(r)))
+        return r.value
+
+    def _segment_rows(self, segment):
+        return self.workspace_row(segment), int(self.frame_offsets[segment + 1] - self.frame_offsets[segment])
+
+    def top(self, segment, softmax=False):
+        """[frames x n_outputs] of a segment: the linear top output, or the softmax p the smoothing left"""
+        r, n = self._segment_rows(segment)
+        out = np.zeros((n, self.trainer.n_outputs), np.float32)
+        _lib.check(self.L.amx_nnseq_get_top(self.h, int(bool(softmax)), r, n, _ptr(out)))
+        return out
+
+    def error_signal(self, segment, layer=None):
+        """[frames x out_dim] of a segment; layer None: the top layer's; "lattice": the copy keep_lattice_error keeps"""
+        r, n = self._segment_rows(segment)
+        lay = self.trainer.layout
+        l = -1 if layer == "lattice" else (lay.n_layers - 1 if layer is None else int(layer))
+        out = np.zeros((n, lay.n_outputs if l < 0 else lay.out_dim[l]), np.float32)
+        _lib.check(self.L.amx_nnseq_get_error_signal(self.h, l, r, n, _ptr(out)))
+        return out
+
+    def weights(self, segment):
+        r, n = self._segment_rows(segment)
+        out = np.zeros(n, np.float32)
+        _lib.check(self.L.amx_nnseq_get_weights(self.h, r, n, _ptr(out)))
+        return out
+
+    def last_shape(self):
+        a, b = C.c_int(), C.c_int()
+        _lib.check(self.L.amx_nnseq_last_shape(self.h, C.byref(a), C.byref(b)))
+        return dict(sort_passes=a.value, sort_blocks=b.value)

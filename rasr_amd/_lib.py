@@ -199,6 +199,23 @@ class LatpostInfo(C.Structure):
                                 "undefined_states", "undefined_arcs", "levels_forward", "levels_backward")]
 
 
+class NnSeqCfg(C.Structure):
+    _fields_ = [("weight_threshold", C.c_double), ("ce_smoothing_weight", C.c_float), ("frame_rejection_threshold", C.c_float),
+                ("log_prior", C.c_void_p), ("prior_scale", C.c_float), ("full_batch", C.c_int), ("accumulate_prior", C.c_int),
+                ("label_type", C.c_int), ("keep_lattice_error", C.c_int)]
+
+
+class NnSeqPass(C.Structure):
+    _fields_ = [("arc_offsets", C.c_void_p), ("item_offsets", C.c_void_p), ("item_frame", C.c_void_p), ("item_emission", C.c_void_p),
+                ("arc_weight_dev", C.c_void_p), ("negate", C.c_int), ("factor", C.c_double), ("role", C.c_int)]
+
+
+class NnSeqInfo(C.Structure):
+    _fields_ = [("segments_processed", C.c_int), ("segments_skipped", C.c_int), ("segments_without_alignment", C.c_int),
+                ("observations", C.c_long), ("rejected_observations", C.c_long), ("ce_objective", C.c_float),
+                ("seg_reason", C.c_void_p), ("seg_errors", C.c_void_p), ("seg_rejected", C.c_void_p), ("seg_ce_objective", C.c_void_p)]
+
+
 class EbwEstimateCfg(C.Structure):
     _fields_ = [("min_observation_weight", C.c_double), ("min_relative_weight", C.c_double), ("min_variance", C.c_double),
                 ("normalize_mixture_weights", C.c_int), ("iteration_constants", C.c_int), ("step_size", C.c_double), ("minimum_icd", C.c_double),
@@ -611,7 +628,21 @@ SIGNATURES = {
     "amx_latpost_plan_host": (C.c_int, [_P, C.c_int] + [_P] * 17),
     "amx_latpost_last_potentials": (C.c_int, [_P, C.c_long, _P, _P, _P, _P]),
     "amx_latpost_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "amx_nnseq_default_cfg": (None, [C.POINTER(NnSeqCfg)]),
+    "amx_nnseq_create": (C.c_int, [_P, C.POINTER(NnSeqCfg), C.POINTER(_P)]),
+    "amx_nnseq_destroy": (None, [_P]),
+    "amx_nnseq_forward_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "amx_nnseq_arc_scores_dev": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "amx_nnseq_accumulate_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(NnSeqInfo)]),
+    "amx_nnseq_workspace_row": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "amx_nnseq_get_top": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "amx_nnseq_get_error_signal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "amx_nnseq_get_weights": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "amx_nnseq_kernel_shape": (None, [C.POINTER(C.c_int)] * 4),
+    "amx_nnseq_last_shape": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
+AMX_NNSEQ_ADD, AMX_NNSEQ_ADD_REJECT, AMX_NNSEQ_ADD_REJECT_CLEAR = 0, 1, 2
+AMX_NNSEQ_SEG_OK, AMX_NNSEQ_SEG_SKIPPED, AMX_NNSEQ_SEG_NO_ALIGNMENT = 0, 1, 2
 AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
 AMX_MLLR_FULL, AMX_MLLR_SHIFT, AMX_MLLR_BAND, AMX_MLLR_SEMI_TIED = 0, 1, 2, 3
 AMX_EBW_IC_GLOBAL_RWTH, AMX_EBW_IC_LOCAL_RWTH, AMX_EBW_IC_CAMBRIDGE = 0, 1, 2

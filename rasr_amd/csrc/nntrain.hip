@@ -663,6 +663,79 @@ int amx_nntrain_layout(const amx_nntrain* h, amx_nntrain_layout_info* info) {
 
 namespace amx {
 
+// ---- the launches of a pass that the segment-wise trainer (nnseq.hip) runs on its own rows: nntrain_pass goes through these too
+void nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st) {
+    const int L = h->L, n_out = h->n_outputs;
+    for (int l = 0; l < L; ++l) {
+        const int    ntn = h->Pout[l] / amx::BN, ntt = Tpad / amx::BT;
+        const float *W = h->d_W[l].get(), *x = h->d_x[l].get(), *b = h->d_bias[l].get();
+        const dim3   grid(ntn * ntt), block(256);
+        if (l == L - 1)
+            hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_NONE, true>), grid, block, 0, st, W, x, b, h->d_top.get(), h->Pin[l], h->Pin[l], n_out, n_out, T, ntn);
+        else {
+            float* o = h->d_x[l + 1].get();
+            switch (h->act[l]) {
+                case AMX_ACT_RELU:
+                    hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_RELU, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
+                    break;
+                case AMX_ACT_SIGMOID:
+                    hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_SIGMOID, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
+                    break;
+                case AMX_ACT_TANH:
+                    hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_TANH, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
+                    break;
+                default:
+                    hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_NONE, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
+            }
+        }
+    }
+}
+
+void nntrain_launch_softmax(amx_nntrain* h, int T, hipStream_t st) {
+    const int n_out = h->n_outputs;
+    float* const    row_max = h->d_rowstat.get();
+    float* const    row_sum = row_max + T;
+    const long long total   = (long long)T * n_out;
+    hipLaunchKernelGGL(amx::top_negexp_kernel, dim3(T), dim3(256), 0, st, h->d_top.get(), n_out, row_max);
+    hipLaunchKernelGGL(amx::top_rowsum_kernel, dim3((T + 63) / 64), dim3(64), 0, st, (const float*)h->d_top.get(), T, n_out, row_sum);
+    hipLaunchKernelGGL(amx::top_finish_kernel, dim3((int)std::min<long long>(16384, (total + 255) / 256)), dim3(256), 0, st, h->d_top.get(), total, n_out,
+                       (const float*)row_sum);
+}
+
+void nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st) {
+    const int L = h->L;
+    for (int l = L - 1; l >= 1; --l) {
+        const int    ntn = h->Pin[l] / amx::BN, ntt = Tpad / amx::BT, do_clip = (l - 1 > 0 && clip < FLT_MAX) ? 1 : 0;
+        const float *WT = h->d_WT[l].get(), *E = h->d_E[l].get(), *Y = h->d_x[l].get();
+        float*       o = h->d_E[l - 1].get();
+        const dim3   grid(ntn * ntt), block(256);
+        switch (h->act[l - 1]) {
+            case AMX_ACT_RELU:
+                hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_RELU>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, clip, do_clip);
+                break;
+            case AMX_ACT_SIGMOID:
+                hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_SIGMOID>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, clip, do_clip);
+                break;
+            case AMX_ACT_TANH:
+                hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_TANH>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, clip, do_clip);
+                break;
+            default:
+                hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_NONE>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, clip, do_clip);
+        }
+    }
+}
+
+void nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st) {
+    const int Kp = h->Pin[l], Np = h->Pout[l], ntn = Np / 128, ntk = Kp / 128;
+    hipLaunchKernelGGL(amx::nntrain_gemm_tn_kernel, dim3(ntk * ntn, tn_chunks), dim3(256), 0, st, (const float*)h->d_x[l].get(),
+                       (const float*)h->d_E[l].get(), h->d_part.get(), Kp, Np, Tpad, ntn);
+}
+
+void nntrain_launch_bias_sums(amx_nntrain* h, int l, int T, int n_chunks, hipStream_t st) {
+    hipLaunchKernelGGL(amx::nntrain_colsum_kernel<0>, dim3((h->out[l] + 255) / 256, n_chunks), dim3(256), 0, st, (const float*)h->d_E[l].get(), h->Pout[l], T,
+                       h->out[l], (const int*)h->d_label.get(), (const float*)h->d_w.get(), h->d_part.get());
+}
+
 int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint32_t* emission, const double* weight, double* acc, const StepSink* sink,
                  const char* who) {
     AMX_REQUIRE(h && (acc || sink), AMX_ERR_INVALID, "%s: NULL argument", who);
@@ -676,6 +749,7 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
         AMX_REQUIRE(feats && ldf >= h->feature_dim, AMX_ERR_INVALID, "%s: feats_dev is NULL or feats_stride %d < %d", who, ldf, h->feature_dim);
     if (T == 0)
         return AMX_OK;
+    ++h->workspace_epoch;
     hipStream_t st   = h->ctx->stream;
     const int   Tpad = amx::pad128(T), n_chunks = (T + amx::NT_CHUNK - 1) / amx::NT_CHUNK, L = h->L, n_out = h->n_outputs;
     const amx_nntrain_layout_info& y = h->lay;
@@ -740,40 +814,12 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
         }
         {
             amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_forward");
-            for (int l = 0; l < L; ++l) {
-                const int    ntn = h->Pout[l] / amx::BN, ntt = Tpad / amx::BT;
-                const float *W = h->d_W[l].get(), *x = h->d_x[l].get(), *b = h->d_bias[l].get();
-                const dim3   grid(ntn * ntt), block(256);
-                if (l == L - 1)
-                    hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_NONE, true>), grid, block, 0, st, W, x, b, h->d_top.get(), h->Pin[l], h->Pin[l], n_out, n_out, T, ntn);
-                else {
-                    float* o = h->d_x[l + 1].get();
-                    switch (h->act[l]) {
-                        case AMX_ACT_RELU:
-                            hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_RELU, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
-                            break;
-                        case AMX_ACT_SIGMOID:
-                            hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_SIGMOID, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
-                            break;
-                        case AMX_ACT_TANH:
-                            hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_TANH, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
-                            break;
-                        default:
-                            hipLaunchKernelGGL((amx::gemm_f32_kernel<AMX_ACT_NONE, false>), grid, block, 0, st, W, x, b, o, h->Pin[l], h->Pin[l], h->Pout[l], h->out[l], T, ntn);
-                    }
-                }
-            }
+            amx::nntrain_launch_forward(h, Tpad, T, st);
             AMX_HIP(hipGetLastError());
         }
         {   // the softmax of the forward node on the dense [T x n_out] scores (= -activation)
             amx::ScopedKernelTimer timer(h->ctx, "nntrain_softmax");
-            float* const    row_max = h->d_rowstat.get();
-            float* const    row_sum = row_max + T;
-            const long long total   = (long long)T * n_out;
-            hipLaunchKernelGGL(amx::top_negexp_kernel, dim3(T), dim3(256), 0, st, h->d_top.get(), n_out, row_max);
-            hipLaunchKernelGGL(amx::top_rowsum_kernel, dim3((T + 63) / 64), dim3(64), 0, st, (const float*)h->d_top.get(), T, n_out, row_sum);
-            hipLaunchKernelGGL(amx::top_finish_kernel, dim3((int)std::min<long long>(16384, (total + 255) / 256)), dim3(256), 0, st, h->d_top.get(), total, n_out,
-                               (const float*)row_sum);
+            amx::nntrain_launch_softmax(h, T, st);
             AMX_HIP(hipGetLastError());
         }
         // 4. criterion and the top error signal
@@ -795,36 +841,17 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
         // 6. error backpropagation: E_{l-1} = (W_l^T E_l) (.) f'(Y_{l-1}); E_{l-1} is clipped unless it is the lowest layer's
         {
             amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_backward");
-            for (int l = L - 1; l >= 1; --l) {
-                const int    ntn = h->Pin[l] / amx::BN, ntt = Tpad / amx::BT, do_clip = (l - 1 > 0 && h->clip < FLT_MAX) ? 1 : 0;
-                const float *WT = h->d_WT[l].get(), *E = h->d_E[l].get(), *Y = h->d_x[l].get();
-                float*       o = h->d_E[l - 1].get();
-                const dim3   grid(ntn * ntt), block(256);
-                switch (h->act[l - 1]) {
-                    case AMX_ACT_RELU:
-                        hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_RELU>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, h->clip, do_clip);
-                        break;
-                    case AMX_ACT_SIGMOID:
-                        hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_SIGMOID>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, h->clip, do_clip);
-                        break;
-                    case AMX_ACT_TANH:
-                        hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_TANH>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, h->clip, do_clip);
-                        break;
-                    default:
-                        hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_NONE>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, h->clip, do_clip);
-                }
-            }
+            amx::nntrain_launch_backward(h, Tpad, h->clip, st);
             AMX_HIP(hipGetLastError());
         }
         // 7. gradients: G_l += X_l E_l^T, g_l += the column sums of E_l
         {
             const int tn_chunks = (Tpad + amx::NT_CHUNK - 1) / amx::NT_CHUNK;  // == n_chunks: NT_CHUNK is a multiple of the padding
             for (int l = L - 1; l >= 0; --l) {
-                const int Kp = h->Pin[l], Np = h->Pout[l], ntn = Np / 128, ntk = Kp / 128;
+                const int Kp = h->Pin[l], Np = h->Pout[l];
                 {
                     amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_tn");
-                    hipLaunchKernelGGL(amx::nntrain_gemm_tn_kernel, dim3(ntk * ntn, tn_chunks), dim3(256), 0, st, (const float*)h->d_x[l].get(),
-                                       (const float*)h->d_E[l].get(), h->d_part.get(), Kp, Np, Tpad, ntn);
+                    amx::nntrain_launch_gemm_tn(h, l, Tpad, tn_chunks, st);
                 }
                 amx::ScopedKernelTimer timer(h->ctx, "nntrain_gradient_sums");
                 const long long total = (long long)h->in[l] * h->out[l];
@@ -836,8 +863,7 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
                 else
                     hipLaunchKernelGGL(amx::nntrain_reduce_kernel, rgrid, dim3(256), 0, st, (const float*)h->d_part.get(), tn_chunks, (size_t)Kp * Np, h->in[l], h->out[l],
                                        Np, acc + y.gradient_weights[l]);
-                hipLaunchKernelGGL(amx::nntrain_colsum_kernel<0>, dim3((h->out[l] + 255) / 256, n_chunks), dim3(256), 0, st, (const float*)h->d_E[l].get(), Np, T, h->out[l],
-                                   label, w, h->d_part.get());
+                amx::nntrain_launch_bias_sums(h, l, T, n_chunks, st);
                 const dim3 bgrid(std::min(1024, (h->out[l] + 255) / 256));
                 if (sink)
                     hipLaunchKernelGGL(amx::nntrain_reduce_step_kernel, bgrid, dim3(256), 0, st, (const float*)h->d_part.get(), n_chunks, (size_t)h->out[l], 1, h->out[l],

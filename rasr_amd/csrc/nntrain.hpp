@@ -72,6 +72,7 @@ struct amx_nntrain {
     amx::DevBuf<unsigned> d_err, d_bad;
     amx::DevBuf<unsigned, true> h_bad;
     amx::NnStep           step;
+    unsigned long         workspace_epoch = 0;  // counts the calls that fill the workspace: nnseq.hip sees whether its batch is still there
 };
 
 namespace amx {
@@ -80,6 +81,16 @@ namespace amx {
 // acc is not read and the results go where the sink says.  who: the entry point's name for the messages.
 int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint32_t* emission, const double* weight, double* acc,
                  const StepSink* sink, const char* who);
+
+// The launches of a pass on the handle's workspace, for the segment-wise trainer (nnseq.hip), which fills d_x[0], d_E[top], d_label
+// and d_w itself; nntrain_pass goes through the same functions.  forward: every layer from d_x[0] [Tpad x Pin], the negated top
+// output into d_top [T x n_outputs]; softmax: d_top in place (d_rowstat holds 2 T floats); backward: d_E[l - 1] from d_E[l], clip ==
+// FLT_MAX: none; gemm_tn: the chunk partials of X_l E_l^T into d_part; bias_sums: the chunk partials of E_l's column sums into d_part.
+void nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st);
+void nntrain_launch_softmax(amx_nntrain* h, int T, hipStream_t st);
+void nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st);
+void nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st);
+void nntrain_launch_bias_sums(amx_nntrain* h, int l, int T, int n_chunks, hipStream_t st);
 
 // the regulariser's axpy alone on the sink's statistic as it stands (amx_nntrain_estimate): factor = group_tail[0] + call_tail[0]
 int nntrain_add_regularizer(amx_nntrain* h, const StepSink* sink);
