@@ -2028,7 +2028,7 @@ int  amx_mllr_adaptor_read(const amx_mllr_shape* shape, const char* path, int ma
 
 /* The corpus pass of Speech::SegmentwiseGmmTrainer feeding Mm::EbwDiscriminativeMixtureSetEstimator: the arc weights that Fsa::posteriorE
  * left on a lattice become numerator and denominator statistics.  The lattice computation, the arc walk and the per-arc alignments stay
- * with the adapter, which hands over, per segment, its arcs in the order of the reference's depth-first walk, each with one signed f32
+ * with the adapter (the alignments: or with amx_arcalign_* below), which hands over, per segment, its arcs in the order of the reference's depth-first walk, each with one signed f32
  * weight and its alignment as items (frame relative to the segment, emission index).
  *   sides       an arc is numerator if w > weight_threshold, denominator with weight -w if -w > weight_threshold (f32, strict;
  *               Lattice/Accumulator.tcc:66-87 under Speech/SegmentwiseGmmTrainer.cc:160-168), otherwise neither;
@@ -2391,6 +2391,70 @@ int  amx_nnseq_get_weights(amx_nnseq* h, int row, int n, float* out);
 void amx_nnseq_kernel_shape(int* sort_block_items, int* score_block_arcs, int* score_stage_items, int* threads);
 /* passes and workgroups of the sort of the last accumulate's LAST pass; 0 where none ran */
 int  amx_nnseq_last_shape(const amx_nnseq* h, int* sort_passes, int* sort_blocks);
+
+/* ------------------------------------------------------------------ Lattice word-arc alignment: one Viterbi alignment per arc key
+ * Speech::PhonemeSequenceAlignmentGenerator::getAlignment (Speech/PhonemeSequenceAlignmentGenerator.cc:280-323): for every distinct
+ * (coarticulated pronunciation, begin time, end time) of a word lattice one Search::Aligner in Viterbi mode over the frames
+ * [tbeg, tend) on the pronunciation's allophone-state acceptor; AlignmentLatticeRescorerAutomaton and EmissionLatticeRescorerAutomaton
+ * (Speech/LatticeRescorerAutomaton.cc:71-102, 229-255) turn the result into the arcs' acoustic scores.  Here: all keys of a batch in
+ * one call on the score matrix in device memory, one wave per key.  A key is exactly amx_align_viterbi_dev's search on the window's
+ * rows -- expansion order, recombination, pruning, the loop of thresholds, the first-best final hypothesis, the NaN rule as stated in
+ * the section "Viterbi alignment" above -- and only f32 additions and comparisons happen: every result equals the reference in every
+ * bit and does not depend on amx_set_contract.
+ * Not built: the TDP half of CombinedAcousticLatticeRescorer (Fsa::bestscore over a graph rebuilt from the alignment), Baum-Welch arc
+ * alignments, alignment cache files, add-emission-scores.
+ * Limits per key: AMX_ARCALIGN_MAX_STATES states and as many distinct emission indices, AMX_ARCALIGN_MAX_IN_ARCS arcs into a state,
+ * AMX_ALIGN_MAX_OUT_ARCS out of one, AMX_ARCALIGN_MAX_FRAMES frames.  A pronunciation above them goes through amx_align_viterbi_dev. */
+#define AMX_ARCALIGN_MAX_STATES 256
+#define AMX_ARCALIGN_MAX_IN_ARCS 255
+#define AMX_ARCALIGN_MAX_FRAMES 65535
+#define AMX_ARCALIGN_ALIGNMENT_SCORE 0 /* AlignmentLatticeRescorerAutomaton::_score: alignmentScore() */
+#define AMX_ARCALIGN_EMISSION_SCORE 1  /* EmissionLatticeRescorerAutomaton::_score */
+typedef struct amx_arcalign amx_arcalign;
+/* the configuration and the refusals of amx_align_create (mode baum-welch and n_best_pruning < INT_MAX: AMX_ERR_UNSUPPORTED) */
+int  amx_arcalign_create(amx_ctx* ctx /* nullable: validation only */, const amx_align_cfg* cfg, amx_arcalign** out);
+void amx_arcalign_destroy(amx_arcalign* h);
+/* graphs: the model-acceptor cache, n_graphs graphs in amx_align_graphs' layout (state_offsets [n_graphs + 1], ...); many keys share one.
+ * Key k (one entry of the reference's alignment cache): graph key_graph[k] on the frames [key_tbeg[k], key_tend[k]) of segment
+ * key_segment[k], matrix row frame_offsets[segment] + t.  Keys may overlap and repeat freely.  All key tables and frame_offsets are host.
+ *   slot_offsets            host out [n_keys + 1]: the prefix sum of tend - tbeg; key k owns the slots [slot_offsets[k], slot_offsets[k + 1])
+ *                           of the three item arrays, slot i is frame tbeg + i
+ *   item_label_dev          int32, the aligned arc's label; item_emission_dev int32, its emission index; both -1 in a key that reached no
+ *                           final state
+ *   item_arc_score_dev      nullable f32: score[hyp] - score[trace] (Aligner.cc:438), 0 in such a key
+ *   key_score_dev           f32 [n_keys]: alignmentScore(), FLT_MAX where no final state was reached
+ *   key_emission_score_dev  f32 [n_keys]: one chain from 0 in frame order, score += score_scale * scores[t][e], each term rounded once as
+ *                           the search rounds it (LatticeRescorerAutomaton.cc:86-102); a key without an alignment keeps 0
+ *   result[k]               host, as amx_align_viterbi_dev's per segment
+ *   counters                nullable, host: [0] keys that met a NaN, [1] passes run on the device, [2] passes counted without running
+ * Checked on the host before anything is launched, the outputs untouched.  AMX_ERR_INVALID naming key or graph and index: tbeg >= tend or
+ * a window outside its segment (the reference never aligns such an arc: the adapter gives it key -1), a graph or segment index out of
+ * range, whatever amx_align_viterbi_dev refuses in a graph (those messages call graph g "segment g").  AMX_ERR_UNSUPPORTED naming the
+ * graph or key: the limits above.  n_keys = 0: nothing is launched or written but slot_offsets[0]. */
+int  amx_arcalign_run_dev(amx_arcalign* h, int n_graphs, const amx_align_graphs* graphs, int n_keys, const int* key_graph, const int* key_segment,
+                          const int* key_tbeg, const int* key_tend, int n_seg, const long* frame_offsets /*[n_seg+1]*/, const float* scores_dev,
+                          int scores_ld, int n_columns, long* slot_offsets /*[n_keys+1]*/, int32_t* item_label_dev, int32_t* item_emission_dev,
+                          float* item_arc_score_dev, float* key_score_dev, float* key_emission_score_dev, amx_align_result* result /*[n_keys]*/,
+                          unsigned long long counters[3]);
+/* The last run's key scores in arc order: arc_score_dev[a] = score of key arc_key[a] (host table), 0 for key -1 (an arc the rescorers
+ * give one()).  which: AMX_ARCALIGN_ALIGNMENT_SCORE | AMX_ARCALIGN_EMISSION_SCORE.  What goes into amx_latpost_run_dev's weights after
+ * the adapter has added its language-model part. */
+int  amx_arcalign_arc_scores_dev(amx_arcalign* h, int n_arcs, const int32_t* arc_key, int which, float* arc_score_dev);
+/* Pure host function, no device and no handle: the item tables amx_ebw_accumulate_dev, amx_nnseq_arc_scores_dev and amx_nnseq_pass take,
+ * from the keys, a host copy of item_emission_dev (slot_emission) and the lattice's arcs in arc-walk order (segment s owns the arcs
+ * [arc_offsets[s], arc_offsets[s + 1]), arc a has key arc_key[a] or -1).  An arc with key -1 or with a key that reached no final state
+ * gets no items; item_frame is relative to the segment.  Returns the number of items, or a negative amx_status (an arc key out of
+ * range or of another segment).  The three output tables all NULL: the count alone. */
+long amx_arcalign_expand(int n_keys, const int* key_segment, const int* key_tbeg, const int* key_tend, const long* slot_offsets,
+                         const int32_t* slot_emission, int n_seg, const long* arc_offsets /*[n_seg+1]*/, const int32_t* arc_key /*[n_arcs]*/,
+                         long* item_offsets /*[n_arcs+1]*/, int32_t* item_frame, int32_t* item_emission);
+/* DIAGNOSTICS for tests and probes.  kernel_shape: of the variant for graphs of <= 64 states and emission indices (wide = 0) or <= 256
+ * (wide = 1): states per lane, keys (waves) per workgroup, LDS bytes per wave, arcs a wave keeps in LDS (any pointer nullable).
+ * set_workspace_cap: bytes of back-pointers per launch, above which a call is cut into several launches (0: the default);
+ * last_launches: how many the last run took. */
+void amx_arcalign_kernel_shape(int wide, int* states_per_lane, int* keys_per_workgroup, int* lds_bytes_per_wave, int* lds_arcs);
+int  amx_arcalign_set_workspace_cap(amx_arcalign* h, long long bytes);
+int  amx_arcalign_last_launches(const amx_arcalign* h);
 
 #ifdef __cplusplus
 }

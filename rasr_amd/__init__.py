@@ -13,6 +13,7 @@ same reference interfaces for tests and benchmarks:
   BayesClassifier      Signal::BayesClassification (signal-bayes-classification[-score]: fast VTLN, segment classifiers)
   ViterbiAligner       Search::Aligner in Viterbi mode (Speech::AlignmentNode): search, traceback and labels on the score matrix
   BaumWelchAligner     Search::Aligner in mode baum-welch: forward-backward on the score matrix, per-frame item lists with posterior weights
+  LatticeArcAligner    Speech::PhonemeSequenceAlignmentGenerator: one Viterbi alignment per (pronunciation, begin, end) of a word lattice's arcs
   StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
   CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
@@ -30,7 +31,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
@@ -1530,6 +1531,113 @@ class ViterbiAligner:
                         last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum))
                    for r in res[:n_seg]]
         return label_dev, emission_dev, arc_score_dev, results, tuple(int(c) for c in counters)
+
+
+class LatticeArcAligner:
+    """Speech::PhonemeSequenceAlignmentGenerator::getAlignment for all arcs of a batch of word lattices: one Viterbi alignment per key
+    (graph, segment, begin time, end time) on the device's score matrix, a wave per key.  Keyword names are the fields of amx_align_cfg;
+    ctx None gives a handle that only checks configurations, graphs and keys."""
+
+    graphs = staticmethod(ViterbiAligner.graphs)
+    WHICH = {"alignment": _lib.AMX_ARCALIGN_ALIGNMENT_SCORE, "emission": _lib.AMX_ARCALIGN_EMISSION_SCORE}
+
+    def __init__(self, ctx, **kw):
+        self.L, self.h = _lib.lib(), None
+        self.ctx = ctx
+        cfg = _lib.AlignCfg()
+        self.L.amx_align_default_cfg(C.byref(cfg))
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("LatticeArcAligner: unknown parameter %r" % k)
+            setattr(cfg, k, float(v) if k in ViterbiAligner.FLOATS else int(v))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_arcalign_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_arcalign_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def kernel_shape(wide):
+        """dict(states_per_lane, keys_per_workgroup, lds_bytes_per_wave, lds_arcs) of the variant for graphs of <= 64 (wide False) or <= 256 states"""
+        v = [C.c_int() for _ in range(4)]
+        _lib.lib().amx_arcalign_kernel_shape(int(bool(wide)), *(C.byref(x) for x in v))
+        return dict(zip(("states_per_lane", "keys_per_workgroup", "lds_bytes_per_wave", "lds_arcs"), (x.value for x in v)))
+
+    def set_workspace_cap(self, n_bytes):
+        """diagnostic: bytes of back-pointers per launch (0: the default)"""
+        _lib.check(self.L.amx_arcalign_set_workspace_cap(self.h, int(n_bytes)))
+
+    def last_launches(self):
+        return int(self.L.amx_arcalign_last_launches(self.h))
+
+    def run(self, graphs, key_graph, key_segment, key_tbeg, key_tend, frame_offsets, scores_dev, scores_ld, n_columns=None, label_dev=None,
+            emission_dev=None, arc_score_dev=None, key_score_dev=None, key_emission_score_dev=None):
+        """graphs: what graphs() returns, or the list it takes (the acceptor cache).  Key k = graph key_graph[k] on the frames
+        [key_tbeg[k], key_tend[k]) of segment key_segment[k] of scores_dev (segment s starts at row frame_offsets[s]).  Buffers that are
+        not given are created (torch, on the matrix's device).  Returns dict(slot_offsets, label_dev, emission_dev, arc_score_dev,
+        key_score_dev, key_emission_score_dev, results, counters): key k owns the slots [slot_offsets[k], slot_offsets[k + 1]) of the
+        three item arrays; results is a list of dicts per key, counters (keys that met a NaN, passes run, passes counted)."""
+        off = _offsets(frame_offsets, "LatticeArcAligner.run")
+        if not isinstance(graphs, dict):
+            graphs = self.graphs(graphs)
+        keep = {k: np.ascontiguousarray(v) for k, v in graphs.items()}
+        g = _lib.AlignGraphs(**{k: v.ctypes.data for k, v in keep.items()})
+        keys = [np.ascontiguousarray(v, dtype=np.int32) for v in (key_graph, key_segment, key_tbeg, key_tend)]
+        n_keys = len(keys[0])
+        if any(k.ndim != 1 or len(k) != n_keys for k in keys):
+            raise ValueError("LatticeArcAligner.run: the four key tables need one entry per key")
+        slots = int(np.maximum(keys[3].astype(np.int64) - keys[2], 0).sum())
+        if self.ctx is not None and n_keys:
+            import torch
+            new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=scores_dev.device)
+            label_dev = new(slots, torch.int32) if label_dev is None else label_dev
+            emission_dev = new(slots, torch.int32) if emission_dev is None else emission_dev
+            arc_score_dev = new(slots, torch.float32) if arc_score_dev is None else arc_score_dev
+            key_score_dev = new(n_keys, torch.float32) if key_score_dev is None else key_score_dev
+            key_emission_score_dev = new(n_keys, torch.float32) if key_emission_score_dev is None else key_emission_score_dev
+        slot_offsets = np.zeros(n_keys + 1, np.int64)
+        res = (_lib.AlignResult * max(n_keys, 1))()
+        counters = np.zeros(3, np.uint64)
+        _lib.check(self.L.amx_arcalign_run_dev(self.h, len(keep["state_offsets"]) - 1, C.byref(g), n_keys, *(k.ctypes.data for k in keys), len(off) - 1,
+                                               off.ctypes.data, _ptr(scores_dev), int(scores_ld), int(n_columns if n_columns is not None else scores_ld),
+                                               slot_offsets.ctypes.data, _ptr(label_dev), _ptr(emission_dev), _ptr(arc_score_dev), _ptr(key_score_dev),
+                                               _ptr(key_emission_score_dev), C.cast(res, C.c_void_p), counters.ctypes.data))
+        results = [dict(score=np.float32(r.score), reached=bool(r.reached_final), n_iterations=int(r.n_iterations),
+                        last_threshold=np.float32(r.last_threshold), average_states=float(r.average_states), state_sum=int(r.state_sum))
+                   for r in res[:n_keys]]
+        return dict(slot_offsets=slot_offsets, label_dev=label_dev, emission_dev=emission_dev, arc_score_dev=arc_score_dev, key_score_dev=key_score_dev,
+                    key_emission_score_dev=key_emission_score_dev, results=results, counters=tuple(int(c) for c in counters))
+
+    def arc_scores_dev(self, arc_key, which, arc_score_dev):
+        """the last run's key scores ("alignment" | "emission") in arc order into arc_score_dev f32 [n_arcs]; key -1 gives 0"""
+        ak = np.ascontiguousarray(arc_key, dtype=np.int32)
+        _lib.check(self.L.amx_arcalign_arc_scores_dev(self.h, len(ak), _ptr(ak), self.WHICH[which], _ptr(arc_score_dev)))
+
+    @staticmethod
+    def expand(key_segment, key_tbeg, key_tend, slot_offsets, slot_emission, arc_offsets, arc_key, count_only=False):
+        """the item tables of the lattice's arcs (amx_arcalign_expand) from the keys and a host copy of emission_dev: dict(arc_offsets,
+        item_offsets, item_frame, item_emission), what EbwAccumulator and SegmentwiseNnTrainer take; count_only: the number of items"""
+        L = _lib.lib()
+        ks, kb, ke, ak = (np.ascontiguousarray(v, dtype=np.int32) for v in (key_segment, key_tbeg, key_tend, arc_key))
+        so, ao = np.ascontiguousarray(slot_offsets, dtype=np.int64), np.ascontiguousarray(arc_offsets, dtype=np.int64)
+        se = np.ascontiguousarray(slot_emission, dtype=np.int32)
+        if len(ao) < 1 or len(ak) != int(ao[-1]) or len(so) != len(ks) + 1 or len(se) < int(so[-1]):
+            raise ValueError("LatticeArcAligner.expand: the tables do not fit each other")
+        call = lambda io, fr, em: L.amx_arcalign_expand(len(ks), _ptr(ks), _ptr(kb), _ptr(ke), _ptr(so), _ptr(se), len(ao) - 1, _ptr(ao), _ptr(ak),
+                                                        _ptr(io), _ptr(fr), _ptr(em))
+        n = call(None, None, None)
+        if n < 0:
+            _lib.check(int(n))
+        if count_only:
+            return int(n)
+        io, fr, em = np.zeros(len(ak) + 1, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _lib.check(min(int(call(io, fr, em)), 0))
+        return dict(arc_offsets=ao, item_offsets=io, item_frame=fr, item_emission=em)
 
 
 class LinearSegmenter:

@@ -640,7 +640,17 @@ SIGNATURES = {
     "amx_nnseq_get_weights": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "amx_nnseq_kernel_shape": (None, [C.POINTER(C.c_int)] * 4),
     "amx_nnseq_last_shape": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_arcalign_create": (C.c_int, [_P, C.POINTER(AlignCfg), C.POINTER(_P)]),
+    "amx_arcalign_destroy": (None, [_P]),
+    "amx_arcalign_run_dev": (C.c_int, [_P, C.c_int, C.POINTER(AlignGraphs), C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 8),
+    "amx_arcalign_arc_scores_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "amx_arcalign_expand": (C.c_long, [C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "amx_arcalign_kernel_shape": (None, [C.c_int] + [C.POINTER(C.c_int)] * 4),
+    "amx_arcalign_set_workspace_cap": (C.c_int, [_P, C.c_longlong]),
+    "amx_arcalign_last_launches": (C.c_int, [_P]),
 }
+AMX_ARCALIGN_MAX_STATES, AMX_ARCALIGN_MAX_IN_ARCS, AMX_ARCALIGN_MAX_FRAMES = 256, 255, 65535
+AMX_ARCALIGN_ALIGNMENT_SCORE, AMX_ARCALIGN_EMISSION_SCORE = 0, 1
 AMX_NNSEQ_ADD, AMX_NNSEQ_ADD_REJECT, AMX_NNSEQ_ADD_REJECT_CLEAR = 0, 1, 2
 AMX_NNSEQ_SEG_OK, AMX_NNSEQ_SEG_SKIPPED, AMX_NNSEQ_SEG_NO_ALIGNMENT = 0, 1, 2
 AMX_CMLLR_NAIVE, AMX_CMLLR_MMI_PRIME, AMX_CMLLR_HLDA = 0, 1, 2
