@@ -2456,6 +2456,81 @@ void amx_arcalign_kernel_shape(int wide, int* states_per_lane, int* keys_per_wor
 int  amx_arcalign_set_workspace_cap(amx_arcalign* h, long long bytes);
 int  amx_arcalign_last_launches(const amx_arcalign* h);
 
+/* ------------------------------------------------------------------ Lattice arc accuracies: phone and state accuracy per arc key
+ * Lattice/Accuracy.cc: getApproximatePhoneAccuracy (MPE; ApproximatePhoneAccuracyAutomaton, :478-641, with
+ * ApproximateAccuracyAutomaton::accuracy, :361-380), getFramePhoneAccuracy (FramePhoneAccuracyAutomaton::accuracy, :747-762) and
+ * getFrameStateAccuracy (state-level MBR; FrameStateAccuracyAutomaton, :778-879).  All three read the alignment of every arc of the
+ * hypothesis lattice and of the reference ("correct") lattice: here, the item arrays amx_arcalign_run_dev has left in device memory.
+ * An arc's accuracy depends only on its key and on its segment's reference, so the keys are the unit of work and
+ * amx_accuracy_arc_dev gathers the key values into arc order: what amx_latpost_run_dev (AMX_LATPOST_EXPECTATION) takes as arc_risk.
+ *   token(item) = label_token ? label_token[item] : item.  Phone modes: the items are item_label_dev and label_token[l] is the central
+ *     phoneme of allophone-state label l (:501-503).  State mode: the items are item_emission_dev, no table (:800-802).
+ *   short_pause[token] != 0: the reference's ShortPauses set over tokens (Fsa::Epsilon, which the automata add to it, is the adapter's
+ *     to map to a token).
+ *   run: a maximal stretch of consecutive frames of a key with one token (:614-620, :538-546), [start, end) in segment frames.  A key
+ *     whose items are -1 (no final state reached) has no runs and the value 0.
+ *   reference table of a segment (LatticeToActiveStates::discoverState, :523-553): the runs (token, start, end) of every key flagged
+ *     key_is_reference, short pauses included, ascending in (start, end, token), duplicates removed (they change no result; the
+ *     reference keeps its sets by the run's first label but compares only label() of it).
+ *   AMX_ACCURACY_APPROXIMATE_PHONE (:361-380, :601-641): for each run [hs, he) of the key that is no short pause, in run order: over the
+ *     table's intervals with rs < he and re > hs -- the union over the run's frames, frames beyond the reference contribute nothing
+ *     (:625) -- the maximum of -1 + (same token ? 2 : 1) * o, o = f32(min(he, re) - max(hs, rs)) / f32(re - rs), one correctly rounded
+ *     division; 0 where there is no such interval.  2 * o is exact: the site does not depend on amx_set_contract.  The key's value is
+ *     one f32 chain from 0 over its runs.
+ *   AMX_ACCURACY_FRAME_PHONE (:747-762): per run the number of its frames covered by an interval of the same token, divided in f32 by
+ *     1 + normalization * (n - 1), n the run's frames.  The denominator is a contraction site of the reference's default build: one
+ *     fused multiply-add under AMX_CONTRACT_FMA, two roundings otherwise, as the context says at the time of the call.  Runs and chain
+ *     as above.
+ *   AMX_ACCURACY_FRAME_STATE (:822-840, :856-879): the reference is per (segment, frame) the set of tokens of the reference keys'
+ *     items, short pauses included (the table then holds (token, frame, frame + 1)); the key's value is the number of its frames whose
+ *     token is no short pause and is in its frame's set, an exact f32.  For a frame beyond the reference's last frame the reference
+ *     reads past its vector; the library gives 0 there.
+ * Every value equals the reference's in every bit, alone and in any batch.
+ * Not built: getApproximateWordAccuracy (it needs no alignment), the mask, soft and weighted frame-phone variants, the
+ * forced-alignment constructors (AlignmentToActiveStates), the exact (edit-distance) accuracies, and a device-side arc_risk for
+ * amx_latpost_run_dev (copy arc_accuracy_dev to the host with amx_copy_to_host). */
+#define AMX_ACCURACY_APPROXIMATE_PHONE 0
+#define AMX_ACCURACY_FRAME_PHONE 1
+#define AMX_ACCURACY_FRAME_STATE 2
+typedef struct amx_accuracy_cfg {
+    int            mode;
+    float          normalization; /* AMX_ACCURACY_FRAME_PHONE only; finite */
+    int            n_labels;      /* entries of label_token; unused without it */
+    const int32_t* label_token;   /* host [n_labels], each in [0, n_tokens); NULL: the item is the token; copied */
+    int            n_tokens;      /* >= 1 */
+    const uint8_t* short_pause;   /* host [n_tokens]; NULL: no short pauses; copied */
+} amx_accuracy_cfg;
+typedef struct amx_accuracy_info {
+    unsigned long long runs;                   /* runs of all keys, short pauses included (state mode: frames of the aligned keys) */
+    unsigned long long reference_intervals;    /* entries of all segments' tables */
+    unsigned long long keys_without_alignment; /* keys whose items are -1 */
+} amx_accuracy_info;
+typedef struct amx_accuracy amx_accuracy;
+/* AMX_ERR_INVALID: an unknown mode, a normalization that is not finite, a label_token entry outside [0, n_tokens), n_tokens < 1 */
+int  amx_accuracy_create(amx_ctx* ctx /* nullable: validation only */, const amx_accuracy_cfg* cfg, amx_accuracy** out);
+void amx_accuracy_destroy(amx_accuracy* h);
+/* The key tables are host tables as amx_arcalign_run_dev takes and returns them; key_is_reference[k] != 0 puts key k's runs into its
+ * segment's table (a key may be reference and hypothesis at once).  item_dev: the int32 slot array on the device, item_label_dev in
+ * the phone modes, item_emission_dev in state mode.  key_accuracy_dev: f32 [n_keys].  info: nullable.  The call synchronises the stream.
+ * Checked on the host before anything is launched, AMX_ERR_INVALID naming the first offender: tbeg >= tend, a negative tbeg, a segment
+ * index out of range, slot_offsets that are not the prefix sum of the windows.  Checked on the device before anything is written,
+ * AMX_ERR_INVALID naming key and slot: an item outside [-1, n_labels) (without a table: [-1, n_tokens)), a key that mixes -1 with
+ * other items.  The outputs are untouched in both cases.  n_keys = 0 does nothing. */
+int  amx_accuracy_run_dev(amx_accuracy* h, int n_keys, const int* key_segment, const int* key_tbeg, const int* key_tend,
+                          const long* slot_offsets /*[n_keys+1]*/, const uint8_t* key_is_reference, const int32_t* item_dev, int n_seg,
+                          float* key_accuracy_dev, amx_accuracy_info* info);
+/* The last run's key values in arc order: arc_accuracy_dev[a] = value of key arc_key[a] (host table), 0 for key -1 (an arc without
+ * pronunciation, :604-606). */
+int  amx_accuracy_arc_dev(amx_accuracy* h, int n_arcs, const int32_t* arc_key, float* arc_accuracy_dev);
+/* DIAGNOSTICS for tests and probes.  kernel_shape: keys a workgroup of the accuracy kernel takes, frames a wave takes per trip,
+ * reference intervals a workgroup keeps in LDS (any pointer nullable).  set_lds_intervals: lowers that capacity (0: the default), so
+ * that small tables take the global-memory path of the sort and of the accuracy kernel; the bits do not change.  last_reference:
+ * returns the number of intervals of a segment's table of the last run and, where the three host tables are given and hold it,
+ * copies it out; or a negative amx_status. */
+void amx_accuracy_kernel_shape(int* keys_per_workgroup, int* frames_per_trip, int* lds_intervals);
+int  amx_accuracy_set_lds_intervals(amx_accuracy* h, int n);
+int  amx_accuracy_last_reference(amx_accuracy* h, int segment, int capacity, int32_t* token, int32_t* start, int32_t* end);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ same reference interfaces for tests and benchmarks:
   ViterbiAligner       Search::Aligner in Viterbi mode (Speech::AlignmentNode): search, traceback and labels on the score matrix
   BaumWelchAligner     Search::Aligner in mode baum-welch: forward-backward on the score matrix, per-frame item lists with posterior weights
   LatticeArcAligner    Speech::PhonemeSequenceAlignmentGenerator: one Viterbi alignment per (pronunciation, begin, end) of a word lattice's arcs
+  LatticeAccuracy      Lattice/Accuracy.cc: approximate phone, frame-phone and frame-state accuracy per arc key from the arc alignments
   StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
   CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
@@ -31,7 +32,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LatticeAccuracy", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
@@ -1638,6 +1639,82 @@ class LatticeArcAligner:
         io, fr, em = np.zeros(len(ak) + 1, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
         _lib.check(min(int(call(io, fr, em)), 0))
         return dict(arc_offsets=ao, item_offsets=io, item_frame=fr, item_emission=em)
+
+
+class LatticeAccuracy:
+    """The accuracy lattice of MPE and state-level MBR (Lattice/Accuracy.cc) per arc key, from the item arrays LatticeArcAligner.run has
+    left on the device.  mode "approximate-phone" (getApproximatePhoneAccuracy) and "frame-phone" (getFramePhoneAccuracy, with
+    normalization) take label_dev and label_token, the central phoneme of every allophone-state label; "frame-state"
+    (getFrameStateAccuracy) takes emission_dev and no table.  short_pause: the tokens of the reference's ShortPauses set.  ctx None
+    gives a handle that only checks configurations and key tables.  The frame-phone denominator follows the context's contract."""
+
+    MODES = {"approximate-phone": _lib.AMX_ACCURACY_APPROXIMATE_PHONE, "frame-phone": _lib.AMX_ACCURACY_FRAME_PHONE,
+             "frame-state": _lib.AMX_ACCURACY_FRAME_STATE}
+
+    def __init__(self, ctx, mode, n_tokens, label_token=None, short_pause=(), normalization=0.0):
+        self.L, self.h, self.ctx = _lib.lib(), None, ctx
+        lt = None if label_token is None else np.ascontiguousarray(label_token, dtype=np.int32)
+        sp = np.zeros(max(int(n_tokens), 0), np.uint8)
+        sp[np.asarray(list(short_pause), np.int64)] = 1
+        cfg = _lib.AccuracyCfg(self.MODES.get(mode, mode), float(normalization), 0 if lt is None else len(lt), _ptr(lt), int(n_tokens), _ptr(sp))
+        h = C.c_void_p()
+        _lib.check(self.L.amx_accuracy_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_accuracy_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def kernel_shape():
+        """dict(keys_per_workgroup, frames_per_trip, lds_intervals)"""
+        v = [C.c_int() for _ in range(3)]
+        _lib.lib().amx_accuracy_kernel_shape(*(C.byref(x) for x in v))
+        return dict(zip(("keys_per_workgroup", "frames_per_trip", "lds_intervals"), (x.value for x in v)))
+
+    def set_lds_intervals(self, n):
+        """diagnostic: reference intervals a workgroup keeps in LDS (0: the default); tables above it are read from global memory"""
+        _lib.check(self.L.amx_accuracy_set_lds_intervals(self.h, int(n)))
+
+    def run(self, key_segment, key_tbeg, key_tend, slot_offsets, key_is_reference, item_dev, n_seg, key_accuracy_dev=None):
+        """The key tables as LatticeArcAligner.run takes and returns them, key_is_reference a flag per key, item_dev the int32 slot array
+        on the device.  -> (key_accuracy_dev f32 [n_keys], dict(runs, reference_intervals, keys_without_alignment))"""
+        ks, kb, ke = (np.ascontiguousarray(v, dtype=np.int32) for v in (key_segment, key_tbeg, key_tend))
+        so, ref = np.ascontiguousarray(slot_offsets, dtype=np.int64), np.ascontiguousarray(key_is_reference).astype(np.uint8)
+        n_keys = len(ks)
+        if any(len(v) != n_keys for v in (kb, ke, ref)) or len(so) != n_keys + 1:
+            raise ValueError("LatticeAccuracy.run: the key tables need one entry per key and slot_offsets one more")
+        if key_accuracy_dev is None and self.ctx is not None and n_keys:
+            import torch
+            key_accuracy_dev = torch.empty(n_keys, dtype=torch.float32, device=item_dev.device)
+        info = _lib.AccuracyInfo()
+        _lib.check(self.L.amx_accuracy_run_dev(self.h, n_keys, _ptr(ks), _ptr(kb), _ptr(ke), _ptr(so), _ptr(ref), _ptr(item_dev), int(n_seg),
+                                               _ptr(key_accuracy_dev), C.byref(info)))
+        return key_accuracy_dev, {n: int(getattr(info, n)) for n, _ in _lib.AccuracyInfo._fields_}
+
+    def arc_accuracies(self, arc_key, arc_accuracy_dev=None):
+        """the last run's key values in arc order, f32 [n_arcs] on the device; key -1 gives 0.  What LatticePosterior("expectation") takes
+        as arc_risk once it is on the host"""
+        ak = np.ascontiguousarray(arc_key, dtype=np.int32)
+        if arc_accuracy_dev is None:
+            import torch
+            arc_accuracy_dev = torch.empty(max(len(ak), 1), dtype=torch.float32, device=torch.device("cuda", self.ctx.device))[:len(ak)]
+        _lib.check(self.L.amx_accuracy_arc_dev(self.h, len(ak), _ptr(ak), _ptr(arc_accuracy_dev)))
+        return arc_accuracy_dev
+
+    def last_reference(self, segment):
+        """DIAGNOSTIC: the segment's reference table of the last run, int32 [n, 3] rows (token, start, end) ascending in (start, end, token)"""
+        n = self.L.amx_accuracy_last_reference(self.h, int(segment), 0, None, None, None)
+        if n < 0:
+            _lib.check(int(n))
+        tok, start, end = (np.zeros(n, np.int32) for _ in range(3))
+        r = self.L.amx_accuracy_last_reference(self.h, int(segment), n, _ptr(tok), _ptr(start), _ptr(end))
+        if r < 0:
+            _lib.check(int(r))
+        return np.stack([tok, start, end], axis=1)
 
 
 class LinearSegmenter:

@@ -199,6 +199,15 @@ class LatpostInfo(C.Structure):
                                 "undefined_states", "undefined_arcs", "levels_forward", "levels_backward")]
 
 
+class AccuracyCfg(C.Structure):
+    _fields_ = [("mode", C.c_int), ("normalization", C.c_float), ("n_labels", C.c_int), ("label_token", C.c_void_p), ("n_tokens", C.c_int),
+                ("short_pause", C.c_void_p)]
+
+
+class AccuracyInfo(C.Structure):
+    _fields_ = [(n, C.c_ulonglong) for n in ("runs", "reference_intervals", "keys_without_alignment")]
+
+
 class NnSeqCfg(C.Structure):
     _fields_ = [("weight_threshold", C.c_double), ("ce_smoothing_weight", C.c_float), ("frame_rejection_threshold", C.c_float),
                 ("log_prior", C.c_void_p), ("prior_scale", C.c_float), ("full_batch", C.c_int), ("accumulate_prior", C.c_int),
@@ -648,7 +657,15 @@ SIGNATURES = {
     "amx_arcalign_kernel_shape": (None, [C.c_int] + [C.POINTER(C.c_int)] * 4),
     "amx_arcalign_set_workspace_cap": (C.c_int, [_P, C.c_longlong]),
     "amx_arcalign_last_launches": (C.c_int, [_P]),
+    "amx_accuracy_create": (C.c_int, [_P, C.POINTER(AccuracyCfg), C.POINTER(_P)]),
+    "amx_accuracy_destroy": (None, [_P]),
+    "amx_accuracy_run_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.POINTER(AccuracyInfo)]),
+    "amx_accuracy_arc_dev": (C.c_int, [_P, C.c_int, _P, _P]),
+    "amx_accuracy_kernel_shape": (None, [C.POINTER(C.c_int)] * 3),
+    "amx_accuracy_set_lds_intervals": (C.c_int, [_P, C.c_int]),
+    "amx_accuracy_last_reference": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
 }
+AMX_ACCURACY_APPROXIMATE_PHONE, AMX_ACCURACY_FRAME_PHONE, AMX_ACCURACY_FRAME_STATE = 0, 1, 2
 AMX_ARCALIGN_MAX_STATES, AMX_ARCALIGN_MAX_IN_ARCS, AMX_ARCALIGN_MAX_FRAMES = 256, 255, 65535
 AMX_ARCALIGN_ALIGNMENT_SCORE, AMX_ARCALIGN_EMISSION_SCORE = 0, 1
 AMX_NNSEQ_ADD, AMX_NNSEQ_ADD_REJECT, AMX_NNSEQ_ADD_REJECT_CLEAR = 0, 1, 2
