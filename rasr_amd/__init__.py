@@ -1452,6 +1452,18 @@ def _offsets(frame_offsets, who):
     return off
 
 
+def _accumulate_keyed(entry, handle, who, feats_dev, feats_ld, frame_offsets, seg_key, emission_dev, best_density_dev, acc_dev, best_density_ld, weight_dev):
+    """the arguments of amx_cmllr_accumulate_dev and amx_mllr_accumulate_dev: segments with a key each"""
+    if handle is None:
+        raise RuntimeError("%s: created without a scorer" % who)
+    off = _offsets(frame_offsets, who)
+    keys = np.ascontiguousarray(seg_key, dtype=np.int32)
+    if len(keys) != len(off) - 1:
+        raise ValueError("seg_key holds %d keys for %d segments" % (len(keys), len(off) - 1))
+    _lib.check(entry(handle, _ptr(feats_dev), int(feats_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(emission_dev), _ptr(best_density_dev),
+                     int(best_density_ld), _ptr(weight_dev), _ptr(acc_dev)))
+
+
 class ViterbiAligner:
     """Search::Aligner in Viterbi mode (what Speech::AlignmentNode runs) for a batch of segments whose [frames x emissions] score matrix
     is on the device.  Keyword names are the fields of amx_align_cfg (= the aligner's parameters); ctx None gives a handle that only
@@ -2489,14 +2501,8 @@ class AffineFeatureTransformEstimator:
     def accumulate_dev(self, feats_dev, feats_ld, frame_offsets, seg_key, emission_dev, best_density_dev, acc_dev, best_density_ld=0, weight_dev=None):
         """add the segments' frames to their keys: emission_dev int32 (-1 skips a frame), best_density_dev u32 (matrix with best_density_ld
         columns, or one per frame with 0), weight_dev f64 or None, acc_dev f64 [accumulator_size()]"""
-        if self.h is None:
-            raise RuntimeError("AffineFeatureTransformEstimator.accumulate_dev: created without a scorer")
-        off = _offsets(frame_offsets, "AffineFeatureTransformEstimator.accumulate_dev")
-        keys = np.ascontiguousarray(seg_key, dtype=np.int32)
-        if len(keys) != len(off) - 1:
-            raise ValueError("seg_key holds %d keys for %d segments" % (len(keys), len(off) - 1))
-        _lib.check(self.L.amx_cmllr_accumulate_dev(self.h, _ptr(feats_dev), int(feats_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(emission_dev),
-                                                   _ptr(best_density_dev), int(best_density_ld), _ptr(weight_dev), _ptr(acc_dev)))
+        _accumulate_keyed(self.L.amx_cmllr_accumulate_dev, self.h, "AffineFeatureTransformEstimator.accumulate_dev", feats_dev, feats_ld, frame_offsets, seg_key,
+                          emission_dev, best_density_dev, acc_dev, best_density_ld, weight_dev)
 
     def _key(self, acc_host, key):
         a = np.ascontiguousarray(acc_host, dtype=np.float64).reshape(-1)
@@ -2674,14 +2680,8 @@ class ModelTransformEstimator:
 
     def accumulate_dev(self, feats_dev, feats_ld, frame_offsets, seg_key, emission_dev, best_density_dev, acc_dev, best_density_ld=0, weight_dev=None):
         """add the segments' frames to (their key, their emission's leaf): arguments as AffineFeatureTransformEstimator.accumulate_dev"""
-        if self.h is None:
-            raise RuntimeError("ModelTransformEstimator.accumulate_dev: created without a scorer")
-        off = _offsets(frame_offsets, "ModelTransformEstimator.accumulate_dev")
-        keys = np.ascontiguousarray(seg_key, dtype=np.int32)
-        if len(keys) != len(off) - 1:
-            raise ValueError("seg_key holds %d keys for %d segments" % (len(keys), len(off) - 1))
-        _lib.check(self.L.amx_mllr_accumulate_dev(self.h, _ptr(feats_dev), int(feats_ld), len(keys), off.ctypes.data, keys.ctypes.data, _ptr(emission_dev),
-                                                  _ptr(best_density_dev), int(best_density_ld), _ptr(weight_dev), _ptr(acc_dev)))
+        _accumulate_keyed(self.L.amx_mllr_accumulate_dev, self.h, "ModelTransformEstimator.accumulate_dev", feats_dev, feats_ld, frame_offsets, seg_key,
+                          emission_dev, best_density_dev, acc_dev, best_density_ld, weight_dev)
 
     def _key(self, acc_host, key):
         a = np.ascontiguousarray(acc_host, dtype=np.float64).reshape(-1)

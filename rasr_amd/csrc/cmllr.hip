@@ -11,7 +11,8 @@
 // owns one (j, k) pair of the triangle and kCmllrTileM model components, forms p = xi_j * xi_k once per frame and divides it by the
 // frame's variances, staged in LDS beside xi.  Triangles longer than a workgroup and models wider than a tile span several workgroups
 // of one key (grid x and z).  cmllr_small_kernel carries beta, k, mean and cov (one cell per lane); it is bound by the latency of its
-// chains and is not tuned.  A frame's (mean, covariance) indices are resolved and checked once, before anything is written.
+// chains and is not tuned.  A frame's (mean, covariance) indices are resolved and checked once, before anything is written
+// (key_plan.hpp and key_frames.hpp, shared with mllr.hip).
 // The library is compiled with -ffp-contract=off; mad<FMA> marks the sites the reference's -march=native build contracts
 // (tests/golden/ref_cmllr.npz holds both builds).
 #include <algorithm>
@@ -21,6 +22,7 @@
 
 #include "common.hpp"
 #include "gmm_internal.hpp"
+#include "key_frames.hpp"
 
 namespace amx {
 
@@ -30,10 +32,6 @@ constexpr int kCmllrTileM   = 16;    // model components per workgroup of cmllr_
 constexpr int kCmllrTileWide = 48;   // the A/B shape: a lane keeps (nearly) all of a 45-dimensional model's accumulators
 constexpr int kCmllrMaxDim  = 255;   // F + 1 <= 256: a stage of xi is at most 32 KB of LDS
 constexpr int kCmllrMaxKeys = 65535; // a key is one row (y) of the two kernels' grids
-
-struct CmllrSeg {
-    long long begin, end;   // frames [begin, end) of one segment
-};
 
 struct CmllrArgs {
     const float*    feats;
@@ -46,7 +44,7 @@ struct CmllrArgs {
     const float*    means;        // [n_mean x M]
     const float*    vars;         // [n_cov x M]
     const int*      key_seg;      // [n_keys + 1] into segs
-    const CmllrSeg* segs;
+    const KeySeg*   segs;
     double*         acc;
     long long       key_stride, off_mean, off_cov, off_g, tri;
 };
@@ -60,44 +58,6 @@ __device__ inline void cmllr_tri_decode(long long cell, int R, int* j, int* k) {
     }
     *j = row;
     *k = row + (int)cell;
-}
-
-// ---- every frame's (mean, covariance) and the checks, before anything is written.  bad = min over the offending frames of
-// (frame << 3 | kind): 1 emission outside the model, 2 density outside the mixture, 3 non-finite feature, 4 non-finite weight
-__global__ __launch_bounds__(kCmllrThreads) void cmllr_resolve_kernel(const float* __restrict__ feats, long long ld, int F, long long t0, long long n,
-                                                                      const int32_t* __restrict__ emission, const uint32_t* __restrict__ best, int best_ld,
-                                                                      const double* __restrict__ weight, int n_mix, const uint32_t* __restrict__ mix_off,
-                                                                      const uint32_t* __restrict__ k_dens, const uint32_t* __restrict__ d_mean,
-                                                                      const uint32_t* __restrict__ d_cov, int* __restrict__ frame_mean,
-                                                                      int* __restrict__ frame_cov, unsigned long long* bad) {
-    const long long i = (long long)blockIdx.x * kCmllrThreads + threadIdx.x;
-    if (i >= n)
-        return;
-    const long long t = t0 + i;
-    const int32_t   e = emission[t];
-    int             mi = -1, ci = -1, kind = 0;
-    if (e != -1) {
-        if (e < 0 || e >= n_mix)
-            kind = 1;
-        else {
-            const uint32_t kk = best_ld > 0 ? best[t * best_ld + e] : best[t];
-            if (kk >= mix_off[e + 1] - mix_off[e])
-                kind = 2;
-            else {
-                const uint32_t d = k_dens[mix_off[e] + kk];
-                mi = (int)d_mean[d], ci = (int)d_cov[d];
-                for (int c = 0; c < F; ++c)
-                    if (!isfinite(feats[t * ld + c]))
-                        kind = 3;
-                if (weight && !isfinite(weight[t]))
-                    kind = kind ? kind : 4;
-            }
-        }
-    }
-    frame_mean[i] = kind ? -1 : mi;
-    frame_cov[i]  = kind ? -1 : ci;
-    if (kind)
-        atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)kind);
 }
 
 // xi = [1, x] of frames [t, t + n) into s_x [n][R]; their flags, weights and indices into the s_* of the caller (all lanes call)
@@ -140,7 +100,7 @@ __global__ __launch_bounds__(kCmllrThreads) void cmllr_g_kernel(CmllrArgs a) {
         sum[i] = active && i0 + i < a.M ? g[(long long)i * a.tri] : 0.0;
 
     for (int s = s_begin; s < s_end; ++s) {
-        const CmllrSeg seg = a.segs[s];
+        const KeySeg seg = a.segs[s];
         for (long long t = seg.begin; t < seg.end; t += kCmllrStage) {
             const int n = seg.end - t < kCmllrStage ? (int)(seg.end - t) : kCmllrStage;
             cmllr_stage(a, t, n, s_x, s_mi, s_ci, s_w);
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(kCmllrThreads) void cmllr_small_kernel(CmllrArgs a)
     double  sum = active ? *p : 0.0;
 
     for (int s = s_begin; s < s_end; ++s) {
-        const CmllrSeg seg = a.segs[s];
+        const KeySeg seg = a.segs[s];
         for (long long t = seg.begin; t < seg.end; t += kCmllrStage) {
             const int n = seg.end - t < kCmllrStage ? (int)(seg.end - t) : kCmllrStage;
             cmllr_stage(a, t, n, s_x, s_mi, s_ci, s_w);
@@ -277,7 +237,7 @@ struct amx_cmllr {
     // per-call workspace
     amx::DevBuf<int>                d_frame;   // [2 x frames]: mean index, covariance index
     amx::DevBuf<int>                d_key_seg;
-    amx::DevBuf<amx::CmllrSeg>      d_segs;
+    amx::DevBuf<amx::KeySeg>        d_segs;
     amx::DevBuf<unsigned long long> d_bad;
 };
 
@@ -354,69 +314,24 @@ int amx_cmllr_accumulate_dev(amx_cmllr* h, const float* feats_dev, int feats_ld,
     AMX_REQUIRE(n_seg >= 0 && feats_ld >= h->F, AMX_ERR_INVALID, "%s: n_seg %d, feats_ld %d (feature_dim %d)", who, n_seg, feats_ld, h->F);
     AMX_REQUIRE(best_density_ld == 0 || best_density_ld >= h->gmm.n_mix, AMX_ERR_INVALID, "%s: best_density_ld %d is neither 0 nor >= %d mixtures", who,
                 best_density_ld, h->gmm.n_mix);
-    if (n_seg == 0)
-        return AMX_OK;
-    AMX_REQUIRE(frame_offsets && seg_key, AMX_ERR_INVALID, "%s: NULL frame_offsets or seg_key", who);
-    AMX_REQUIRE(frame_offsets[0] >= 0, AMX_ERR_INVALID, "%s: frame_offsets[0] = %ld is negative", who, frame_offsets[0]);
-    for (int s = 0; s < n_seg; ++s) {
-        AMX_REQUIRE(frame_offsets[s + 1] >= frame_offsets[s], AMX_ERR_INVALID, "%s: frame_offsets decrease at segment %d (%ld after %ld)", who, s,
-                    frame_offsets[s + 1], frame_offsets[s]);
-        AMX_REQUIRE(seg_key[s] >= 0 && seg_key[s] < h->n_keys, AMX_ERR_INVALID, "%s: segment %d: key %d is outside [0, %d)", who, s, seg_key[s], h->n_keys);
-    }
-    const long long t0 = frame_offsets[0], n = frame_offsets[n_seg] - t0;
+    amx::KeyPlan plan;   // every key's segments in ascending order
+    AMX_TRY(amx::plan_keys(who, n_seg, frame_offsets, seg_key, h->n_keys, false, &plan));
+    const long long t0 = plan.t0, n = plan.n;
     if (n == 0)
         return AMX_OK;
-    AMX_REQUIRE(n < (1ll << 30), AMX_ERR_INVALID, "%s: %lld frames are more than one call takes", who, n);
     AMX_REQUIRE(feats_dev && emission_dev && best_density_dev && acc_dev, AMX_ERR_INVALID, "%s: NULL feats_dev, emission_dev, best_density_dev or acc_dev", who);
     amx_ctx* ctx = h->gmm.ctx;
     AMX_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    // every key's segments in ascending order (a counting sort by key keeps it)
-    std::vector<int>           key_seg((size_t)h->n_keys + 1, 0);
-    std::vector<amx::CmllrSeg> segs;
-    for (int s = 0; s < n_seg; ++s)
-        if (frame_offsets[s + 1] > frame_offsets[s])
-            ++key_seg[(size_t)seg_key[s] + 1];
-    for (int k = 0; k < h->n_keys; ++k)
-        key_seg[(size_t)k + 1] += key_seg[(size_t)k];
-    segs.resize((size_t)key_seg[(size_t)h->n_keys]);
-    {
-        std::vector<int> cursor(key_seg.begin(), key_seg.end() - 1);
-        for (int s = 0; s < n_seg; ++s)
-            if (frame_offsets[s + 1] > frame_offsets[s])
-                segs[(size_t)cursor[(size_t)seg_key[s]]++] = amx::CmllrSeg{frame_offsets[s], frame_offsets[s + 1]};
-    }
     AMX_TRY(h->d_frame.reserve((size_t)2 * n));
-    AMX_TRY(h->d_key_seg.reserve(key_seg.size()));
-    AMX_TRY(h->d_segs.reserve(segs.size()));
+    AMX_TRY(amx::upload_plan(st, plan, h->d_key_seg, h->d_segs));
     int* frame_mean = h->d_frame.get();
     int* frame_cov  = frame_mean + n;
-    AMX_HIP(hipMemcpyAsync(h->d_key_seg.get(), key_seg.data(), key_seg.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    AMX_HIP(hipMemcpyAsync(h->d_segs.get(), segs.data(), segs.size() * sizeof(amx::CmllrSeg), hipMemcpyHostToDevice, st));
-    AMX_HIP(hipMemsetAsync(h->d_bad.get(), 0xff, sizeof(unsigned long long), st));
 
     // 1. indices and checks, before anything is written
-    hipLaunchKernelGGL(amx::cmllr_resolve_kernel, dim3((unsigned)amx::ceil_div(n, amx::kCmllrThreads)), dim3(amx::kCmllrThreads), 0, st, feats_dev,
-                       (long long)feats_ld, h->F, t0, n, emission_dev, best_density_dev, best_density_ld, weight_dev, h->gmm.n_mix, h->gmm.d_mix_off,
-                       h->gmm.d_k_dens, h->gmm.d_d_mean, h->gmm.d_d_cov, frame_mean, frame_cov, h->d_bad.get());
-    AMX_HIP(hipGetLastError());
-    unsigned long long bad = 0;
-    AMX_HIP(hipMemcpyAsync(&bad, h->d_bad.get(), sizeof(bad), hipMemcpyDeviceToHost, st));
-    AMX_HIP(hipStreamSynchronize(st));
-    if (bad != ~0ull) {
-        const long long t    = t0 + (long long)(bad >> 3);
-        const int       kind = (int)(bad & 7);
-        int32_t         e    = 0;
-        AMX_HIP(hipMemcpy(&e, emission_dev + t, sizeof(e), hipMemcpyDeviceToHost));
-        if (kind == 1)
-            amx::set_error("%s: frame %lld: emission index %d is outside [0, %d) and is not -1", who, t, e, h->gmm.n_mix);
-        else if (kind == 2)
-            amx::set_error("%s: frame %lld: the density of emission %d is outside its mixture", who, t, e);
-        else
-            amx::set_error("%s: frame %lld: non-finite %s", who, t, kind == 3 ? "feature" : "weight");
-        return AMX_ERR_INVALID;
-    }
+    AMX_TRY(amx::resolve_frames<false>(who, ctx, nullptr, h->gmm, feats_dev, feats_ld, h->F, t0, n, emission_dev, best_density_dev, best_density_ld,
+                                       weight_dev, nullptr, frame_mean, frame_cov, nullptr, h->d_bad.get()));
 
     // 2. the chains
     amx::CmllrArgs a{};

@@ -4,7 +4,8 @@
 // mllr_host.cpp's.
 //
 // Order.  Per (key, leaf, cell) the reference adds that key's frames of that leaf in corpus order into an f64.  Three steps:
-//   1. mllr_resolve_kernel: every frame's (mean, covariance, leaf) and the checks, before anything is written.
+//   1. frame_resolve_kernel (key_frames.hpp, shared with cmllr.hip): every frame's (mean, covariance, leaf) and the checks, before
+//      anything is written.
 //   2. mllr_lists_kernel, one workgroup per key: it walks the key's segments in ascending order twice.  The first walk counts the
 //      frames of every leaf (integer counters in LDS), an exclusive scan of the counters gives every leaf's place in the key's part
 //      of the list, the second walk writes every frame to (its leaf's cursor + the number of earlier frames of that leaf in the same
@@ -24,6 +25,7 @@
 
 #include "common.hpp"
 #include "gmm_internal.hpp"
+#include "key_frames.hpp"
 
 namespace amx {
 
@@ -33,52 +35,8 @@ constexpr int kMllrMaxDim   = 255;
 constexpr int kMllrMaxKeys  = 65535;  // a key is one workgroup of mllr_lists_kernel
 constexpr int kMllrMaxLeafs = 4096;   // a counter per leaf in LDS (16 KB)
 
-struct MllrSeg {
-    long long begin, end;   // frames [begin, end) of one segment
-};
-
-// ---- every frame's (mean, covariance, leaf) and the checks.  bad = min over the offending frames of (frame << 3 | kind):
-// 1 emission outside the model, 2 density outside the mixture, 3 non-finite feature, 4 non-finite weight
-__global__ __launch_bounds__(kMllrThreads) void mllr_resolve_kernel(const float* __restrict__ feats, long long ld, int D, long long t0, long long n,
-                                                                    const int32_t* __restrict__ emission, const uint32_t* __restrict__ best, int best_ld,
-                                                                    const double* __restrict__ weight, int n_mix, const uint32_t* __restrict__ mix_off,
-                                                                    const uint32_t* __restrict__ k_dens, const uint32_t* __restrict__ d_mean,
-                                                                    const uint32_t* __restrict__ d_cov, const int* __restrict__ leaf_of_mix,
-                                                                    int* __restrict__ frame_mean, int* __restrict__ frame_cov, int* __restrict__ frame_leaf,
-                                                                    unsigned long long* bad) {
-    const long long i = (long long)blockIdx.x * kMllrThreads + threadIdx.x;
-    if (i >= n)
-        return;
-    const long long t = t0 + i;
-    const int32_t   e = emission[t];
-    int             mi = -1, ci = -1, leaf = -1, kind = 0;
-    if (e != -1) {
-        if (e < 0 || e >= n_mix)
-            kind = 1;
-        else {
-            const uint32_t kk = best_ld > 0 ? best[t * best_ld + e] : best[t];
-            if (kk >= mix_off[e + 1] - mix_off[e])
-                kind = 2;
-            else {
-                const uint32_t d = k_dens[mix_off[e] + kk];
-                mi = (int)d_mean[d], ci = (int)d_cov[d], leaf = leaf_of_mix[e];
-                for (int c = 0; c < D; ++c)
-                    if (!isfinite(feats[t * ld + c]))
-                        kind = 3;
-                if (weight && !isfinite(weight[t]))
-                    kind = kind ? kind : 4;
-            }
-        }
-    }
-    frame_mean[i] = kind ? -1 : mi;
-    frame_cov[i]  = kind ? -1 : ci;
-    frame_leaf[i] = kind ? -1 : leaf;
-    if (kind)
-        atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)kind);
-}
-
 // ---- per (key, leaf) the ascending list of its frames (indices relative to t_base).  grid: x = key.  LDS: n_leafs counters.
-__global__ __launch_bounds__(kMllrThreads) void mllr_lists_kernel(const int* __restrict__ key_seg, const MllrSeg* __restrict__ segs, long long t_base,
+__global__ __launch_bounds__(kMllrThreads) void mllr_lists_kernel(const int* __restrict__ key_seg, const KeySeg* __restrict__ segs, long long t_base,
                                                                   const int* __restrict__ frame_leaf, int n_leafs, const int* __restrict__ key_base,
                                                                   int* __restrict__ list, int* __restrict__ list_start, int* __restrict__ list_count) {
     extern __shared__ int s_cnt[];   // [n_leafs]: counts, then cursors
@@ -89,7 +47,7 @@ __global__ __launch_bounds__(kMllrThreads) void mllr_lists_kernel(const int* __r
         s_cnt[l] = 0;
     __syncthreads();
     for (int s = s_begin; s < s_end; ++s) {
-        const MllrSeg seg = segs[s];
+        const KeySeg seg = segs[s];
         for (long long t = seg.begin + tid; t < seg.end; t += kMllrThreads) {
             const int l = frame_leaf[t - t_base];
             if (l >= 0)
@@ -109,7 +67,7 @@ __global__ __launch_bounds__(kMllrThreads) void mllr_lists_kernel(const int* __r
     }
     __syncthreads();
     for (int s = s_begin; s < s_end; ++s) {
-        const MllrSeg seg = segs[s];
+        const KeySeg seg = segs[s];
         for (long long t = seg.begin; t < seg.end; t += kMllrThreads) {   // all lanes run every chunk
             const bool in = t + tid < seg.end;
             const int  l  = in ? frame_leaf[t + tid - t_base] : -1;
@@ -263,7 +221,7 @@ struct amx_mllr {
     // per-call workspace
     amx::DevBuf<int>                d_frame;   // [4 x frames]: mean, covariance, leaf, list
     amx::DevBuf<int>                d_key;     // key_seg [n_keys + 1], key_base [n_keys]
-    amx::DevBuf<amx::MllrSeg>       d_segs;
+    amx::DevBuf<amx::KeySeg>        d_segs;
     amx::DevBuf<int>                d_lists;   // start, count [n_keys x n_leafs] each
     amx::DevBuf<unsigned long long> d_bad;
     amx::DevBuf<double>             d_mats;
@@ -352,54 +310,21 @@ int amx_mllr_accumulate_dev(amx_mllr* h, const float* feats_dev, int feats_ld, i
     AMX_REQUIRE(n_seg >= 0 && feats_ld >= h->D, AMX_ERR_INVALID, "%s: n_seg %d, feats_ld %d (dimension %d)", who, n_seg, feats_ld, h->D);
     AMX_REQUIRE(best_density_ld == 0 || best_density_ld >= h->gmm.n_mix, AMX_ERR_INVALID, "%s: best_density_ld %d is neither 0 nor >= %d mixtures", who,
                 best_density_ld, h->gmm.n_mix);
-    if (n_seg == 0)
-        return AMX_OK;
-    AMX_REQUIRE(frame_offsets && seg_key, AMX_ERR_INVALID, "%s: NULL frame_offsets or seg_key", who);
-    AMX_REQUIRE(frame_offsets[0] >= 0, AMX_ERR_INVALID, "%s: frame_offsets[0] = %ld is negative", who, frame_offsets[0]);
-    for (int s = 0; s < n_seg; ++s) {
-        AMX_REQUIRE(frame_offsets[s + 1] >= frame_offsets[s], AMX_ERR_INVALID, "%s: frame_offsets decrease at segment %d (%ld after %ld)", who, s,
-                    frame_offsets[s + 1], frame_offsets[s]);
-        AMX_REQUIRE(seg_key[s] >= 0 && seg_key[s] < h->n_keys, AMX_ERR_INVALID, "%s: segment %d: key %d is outside [0, %d)", who, s, seg_key[s], h->n_keys);
-    }
-    const long long t0 = frame_offsets[0], n = frame_offsets[n_seg] - t0;
+    // every key's segments in ascending order and the key's place in the list: the frames of the keys before it
+    amx::KeyPlan plan;
+    AMX_TRY(amx::plan_keys(who, n_seg, frame_offsets, seg_key, h->n_keys, true, &plan));
+    const long long t0 = plan.t0, n = plan.n;
     if (n == 0)
         return AMX_OK;
-    AMX_REQUIRE(n < (1ll << 30), AMX_ERR_INVALID, "%s: %lld frames are more than one call takes", who, n);
     AMX_REQUIRE(feats_dev && emission_dev && best_density_dev && acc_dev, AMX_ERR_INVALID, "%s: NULL feats_dev, emission_dev, best_density_dev or acc_dev", who);
     amx_ctx* ctx = h->gmm.ctx;
     AMX_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    // every key's segments in ascending order (a counting sort by key keeps it) and the key's place in the list: the frames of the
-    // keys before it
-    const int                 n_keys = h->n_keys, n_leafs = h->n_leafs;
-    std::vector<int>          key_tab((size_t)2 * n_keys + 1, 0);   // key_seg [n_keys + 1] | key_base [n_keys]
-    std::vector<amx::MllrSeg> segs;
-    int*                      key_seg  = key_tab.data();
-    int*                      key_base = key_tab.data() + n_keys + 1;
-    std::vector<long long>    key_frames((size_t)n_keys, 0);
-    for (int s = 0; s < n_seg; ++s)
-        if (frame_offsets[s + 1] > frame_offsets[s]) {
-            ++key_seg[seg_key[s] + 1];
-            key_frames[(size_t)seg_key[s]] += frame_offsets[s + 1] - frame_offsets[s];
-        }
-    long long run = 0;
-    for (int k = 0; k < n_keys; ++k) {
-        key_seg[k + 1] += key_seg[k];
-        key_base[k] = (int)run;
-        run += key_frames[(size_t)k];
-    }
-    segs.resize((size_t)key_seg[n_keys]);
-    {
-        std::vector<int> cursor(key_seg, key_seg + n_keys);
-        for (int s = 0; s < n_seg; ++s)
-            if (frame_offsets[s + 1] > frame_offsets[s])
-                segs[(size_t)cursor[(size_t)seg_key[s]]++] = amx::MllrSeg{frame_offsets[s], frame_offsets[s + 1]};
-    }
+    const int       n_keys = h->n_keys, n_leafs = h->n_leafs;
     const long long n_pairs = (long long)n_keys * n_leafs;
     AMX_TRY(h->d_frame.reserve((size_t)4 * n));
-    AMX_TRY(h->d_key.reserve(key_tab.size()));
-    AMX_TRY(h->d_segs.reserve(segs.size()));
+    AMX_TRY(amx::upload_plan(st, plan, h->d_key, h->d_segs));
     AMX_TRY(h->d_lists.reserve((size_t)2 * n_pairs));
     int* frame_mean = h->d_frame.get();
     int* frame_cov  = frame_mean + n;
@@ -407,41 +332,16 @@ int amx_mllr_accumulate_dev(amx_mllr* h, const float* feats_dev, int feats_ld, i
     int* list       = frame_leaf + n;
     int* list_start = h->d_lists.get();
     int* list_count = list_start + n_pairs;
-    AMX_HIP(hipMemcpyAsync(h->d_key.get(), key_tab.data(), key_tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    AMX_HIP(hipMemcpyAsync(h->d_segs.get(), segs.data(), segs.size() * sizeof(amx::MllrSeg), hipMemcpyHostToDevice, st));
-    AMX_HIP(hipMemsetAsync(h->d_bad.get(), 0xff, sizeof(unsigned long long), st));
 
     // 1. indices and checks, before anything is written
-    {
-        amx::ScopedKernelTimer timer(ctx, "mllr_resolve");
-        hipLaunchKernelGGL(amx::mllr_resolve_kernel, dim3((unsigned)amx::ceil_div(n, amx::kMllrThreads)), dim3(amx::kMllrThreads), 0, st, feats_dev,
-                           (long long)feats_ld, h->D, t0, n, emission_dev, best_density_dev, best_density_ld, weight_dev, h->gmm.n_mix, h->gmm.d_mix_off,
-                           h->gmm.d_k_dens, h->gmm.d_d_mean, h->gmm.d_d_cov, (const int*)h->d_leaf_of_mix.get(), frame_mean, frame_cov, frame_leaf,
-                           h->d_bad.get());
-        AMX_HIP(hipGetLastError());
-    }
-    unsigned long long bad = 0;
-    AMX_HIP(hipMemcpyAsync(&bad, h->d_bad.get(), sizeof(bad), hipMemcpyDeviceToHost, st));
-    AMX_HIP(hipStreamSynchronize(st));
-    if (bad != ~0ull) {
-        const long long t    = t0 + (long long)(bad >> 3);
-        const int       kind = (int)(bad & 7);
-        int32_t         e    = 0;
-        AMX_HIP(hipMemcpy(&e, emission_dev + t, sizeof(e), hipMemcpyDeviceToHost));
-        if (kind == 1)
-            amx::set_error("%s: frame %lld: emission index %d is outside [0, %d) and is not -1", who, t, e, h->gmm.n_mix);
-        else if (kind == 2)
-            amx::set_error("%s: frame %lld: the density of emission %d is outside its mixture", who, t, e);
-        else
-            amx::set_error("%s: frame %lld: non-finite %s", who, t, kind == 3 ? "feature" : "weight");
-        return AMX_ERR_INVALID;
-    }
+    AMX_TRY(amx::resolve_frames<true>(who, ctx, "mllr_resolve", h->gmm, feats_dev, feats_ld, h->D, t0, n, emission_dev, best_density_dev, best_density_ld,
+                                      weight_dev, h->d_leaf_of_mix.get(), frame_mean, frame_cov, frame_leaf, h->d_bad.get()));
 
     // 2. the lists
     {
         amx::ScopedKernelTimer timer(ctx, "mllr_lists");
         hipLaunchKernelGGL(amx::mllr_lists_kernel, dim3((unsigned)n_keys), dim3(amx::kMllrThreads), (size_t)n_leafs * sizeof(int), st,
-                           (const int*)h->d_key.get(), (const amx::MllrSeg*)h->d_segs.get(), t0, (const int*)frame_leaf, n_leafs,
+                           (const int*)h->d_key.get(), (const amx::KeySeg*)h->d_segs.get(), t0, (const int*)frame_leaf, n_leafs,
                            (const int*)(h->d_key.get() + n_keys + 1), list, list_start, list_count);
         AMX_HIP(hipGetLastError());
     }

@@ -5,8 +5,8 @@ restatement of tests/nnseq_reference.py.
 Shapes.  Network 20-33-17-50, sigmoid then rectified, 60 classes of which ten have no output; segments of 1, 255, 256, 257 and 300
 frames (the frame chunk AMX_NNTRAIN_CHUNK from both sides, and two chunks), the features from row 2 of a wider matrix whose other cells
 hold NaN.  Arc tables: 13 arcs per segment (65: no multiple of the score kernel's 4 arcs per workgroup), every fifth without items, one
-of up to 200 items (more than the 64 a wave stages); item counts one below, at and one above the sort's workgroup (kernel_shape), keys
-of 17 bits (three digit passes).
+of up to 200 items (more than the 64 a wave stages); item counts one below, at and one above the sort's workgroup (kernel_shape) and
+one above eight of them (nine workgroups: the scan of the digit table recurses), keys of 17 bits (three digit passes).
 
 Bars.  Arc scores, the error signal before and after smoothing, the frame weights, the rejected counts, classification errors,
 observations and the total weight are compared in every bit (the smoothing on the device's own softmax: its exp is the device
@@ -157,7 +157,9 @@ def test_collection_around_the_sorts_workgroup_and_the_order_sensitive_key(ctx):
     e0 = int(sr.valid_classes(net)[7])
     lead_t, lead_w, thr = sr.order_case(e0)
     tr, seq = trainers(ctx, net, weight_threshold=thr)
-    for n_items in (block - 1, block, block + 1, 2 * block + 5):
+    # 8 blocks + 1: nine workgroups, whose 9 x 256 counters are more than one workgroup of the scan takes (its second level runs)
+    assert 256 * 9 > block
+    for n_items in (block - 1, block, block + 1, 2 * block + 5, 8 * block + 1):
         tables, w = items_table(net, n_items - 4, T, rng, lead=(lead_t, lead_w))
         assert len(tables["item_frame"]) == n_items
         passes = [dict(tables=tables, arc_weight=w, factor=1.0)]
