@@ -2531,6 +2531,94 @@ void amx_accuracy_kernel_shape(int* keys_per_workgroup, int* frames_per_trip, in
 int  amx_accuracy_set_lds_intervals(amx_accuracy* h, int n);
 int  amx_accuracy_last_reference(amx_accuracy* h, int segment, int capacity, int32_t* token, int32_t* start, int32_t* end);
 
+/* ------------------------------------------------------------------ segment clustering: the key per segment of the speaker-adaptive steps
+ * Signal::SegmentClusteringNode<CorrFullCovMonoGaussianModel> (the node signal-segment-clustering, Signal/SegmentClustering.{hh,cc}): one
+ * full-covariance Gaussian per segment, agglomerative clustering under the correlation distance, the BIC stopping rule.  Its result, a class id
+ * per segment, is the seg_key of amx_cmllr_accumulate_dev and amx_mllr_accumulate_dev on a corpus without speaker labels.
+ *   accumulate (:53-61): per segment sum += (f64) x, sq[i][j] += (f64) x_i * (f64) x_j, one chain per cell in frame order: the reference's bits.
+ *   finalize (:63-77): inv = (f64)(1.0F / n), an f32 division; mean = sum * inv; var = sq * inv - mean mean^T; while the LU with partial
+ *     pivoting meets an exact zero pivot, var += 0.1 I (a one-frame segment takes that loop once).  likelihood = f32(logdet) * (f32) n, logdet
+ *     the sum of log|u_ii|.
+ *   R(i|j) = f32(0.5 n_i (-logdet_j - tr(var_j^-1 var_i) - (mean_i - mean_j)^T var_j^-1 (mean_i - mean_j) - D LN_2PI)) (:110-129), computed as
+ *     ONE f64 matrix product around the frame-weighted global mean.
+ *   alpha < 0 (.hh:607-645): f32 bisection from 0 with step 0.5 on the mean over i of exp(alpha R[i][i] - logSum(alpha R[i][.])), until it lies
+ *     in [minalpha, maxalpha] or the step is within 100 ulp of 0.  logSum is Math::Vector<f32>::logSum (Math/Vector.hh:187-201), the
+ *     reference's own rule: a running f32 sum, MINLOGEPS = 11.513f, no action for diff > MINLOGEPS, log(1.0 + exp(.)) in double.
+ *   feature of a model: the f32 vector exp(alpha R(m|j) - logSum) over the N ORIGINAL segment models j (:166-185); distance of two models:
+ *     minus the dot product of their features (:187-193).
+ *   loop (.hh:850-866): the strict minimum over the active pairs i > j, i ascending, then j ascending; merge (:79-103) by the text's
+ *     elementwise operations; tracker score = 0.5f (L - L_x - L_y) - threshold, threshold = cfg.threshold + 0.25f D (3 + D) lambda
+ *     log((f32) totalframes); amalgamation 0 recomputes the parent's distances to every active slot, 1 takes the elementwise maximum.  Cells
+ *     of inactive slots are left as they are.  The loop runs until one cluster is left.
+ *   choice (.hh:775-814): findBestBIC and returnClustering over the N - 1 tracker records, amx_segclust_choose.
+ * Segments with fewer than minframes frames go to the default cluster 0 and every other class id is then one higher (printClustering).
+ * Tolerances: the sums are exact.  Everything behind an LU (R, alpha, the distances, the scores) carries the bars of DESIGN.md section 6:
+ * nothing of it can be pinned to LAPACK's bits.  The order in which equal distances merge is the reference's; distances that differ
+ * within those bars may merge in another order.
+ * amx_set_contract has no observable effect: the accumulators add exact products, and everything behind the LAPACK calls carries a tolerance
+ * anyway.
+ * Bounds, chosen and not tuned: 1 <= dim <= 64 (a lane per column of a model), 1 <= segments after the filter <= 8192 (three N x N f32
+ * matrices), at most 65535 accumulated segments.
+ * Refused: AMX_ERR_UNSUPPORTED naming the parameter for infile (a predefined clustering), dim outside 1...64, more than 8192 segments after
+ * the filter, mincluster above their number (the reference's unsigned difference wraps); AMX_ERR_INVALID for no segment at all (the
+ * reference's critical error), a feature that is not finite (the call's segments are not appended), a merged covariance whose LU meets a
+ * zero pivot (the reference's critical LAPACK error).  The handle stays usable after each.
+ * Not built: the other registered models (BIC and KL2 distance), the diagonal model, infile. */
+typedef struct amx_segclust_cfg {
+    int         minframes;    /* 0 */
+    int         mincluster;   /* 2 */
+    int         maxcluster;   /* 100000 */
+    float       threshold;    /* 0 */
+    float       lambda;       /* 1 */
+    float       alpha;        /* -1: automatic */
+    float       minalpha;     /* 0.40 */
+    float       maxalpha;     /* 0.60 */
+    int         amalgamation; /* 0 concatenation, 1 max linkage */
+    const char* infile;       /* must be NULL or empty */
+} amx_segclust_cfg;
+typedef struct amx_segclust_info {
+    int   n_segments;       /* N: segments that entered the clustering */
+    int   n_filtered;       /* segments below minframes: the default cluster */
+    int   n_clusters;       /* clusters among the N, the default cluster not counted */
+    int   n_regularised;    /* models that took the +0.1 loop */
+    int   best_index;       /* the last tracker record applied, -1 for none */
+    int   alpha_iterations; /* steps of the automatic search, 0 for a given alpha */
+    float alpha;
+    float threshold;        /* the parameter plus the penalty */
+} amx_segclust_info;
+typedef struct amx_segclust amx_segclust;
+void amx_segclust_default_cfg(amx_segclust_cfg* cfg);
+int  amx_segclust_create(amx_ctx* ctx /* nullable: validation only */, int dim, amx_segclust** out);
+void amx_segclust_destroy(amx_segclust* h);
+/* Appends n_seg segments: segment s covers the frames [frame_offsets[s], frame_offsets[s + 1]) of feats_dev [frame x feats_ld], at least one
+ * frame each.  May be called many times; the sums of a segment do not depend on how the segments are spread over calls. */
+int  amx_segclust_accumulate_dev(amx_segclust* h, const float* feats_dev, int feats_ld, int n_seg, const long* frame_offsets);
+long amx_segclust_segments(const amx_segclust* h); /* accumulated so far; 0 for NULL */
+int  amx_segclust_reset(amx_segclust* h);          /* forgets the accumulated segments */
+/* Clusters the accumulated segments; may be called again with another configuration.  All results on the host: class_ids [segments],
+ * tracker_* [N - 1] (nullable), info (nullable).  The call synchronises the stream. */
+int  amx_segclust_cluster(amx_segclust* h, const amx_segclust_cfg* cfg, int32_t* class_ids, int32_t* tracker_parent, int32_t* tracker_child,
+                          float* tracker_score, amx_segclust_info* info);
+/* Pure host functions.  choose: findBestBIC and returnClustering over n - 1 records; class_ids [n] are slot indices (the cluster's smallest
+ * member), not shifted.  AMX_ERR_INVALID for a record that is no merge of two live clusters with parent < child.
+ * write_map: the `coprus-key-map` document (sic) the corpus-key map reads: the default cluster's keys with value 0, then ids [n] with
+ * class_ids [n] as given, one map-item per line. */
+int  amx_segclust_choose(int n, const int32_t* parent, const int32_t* child, const float* score, int mincluster, int maxcluster, int32_t* class_ids,
+                         int* n_clusters, int* best_index);
+int  amx_segclust_write_map(const char* path, const char* const* ids, int n_default, const char* const* default_ids, int n, const int32_t* class_ids);
+/* DIAGNOSTICS for tests and probes.  kernel_shape: frames per LDS stage and cells per workgroup of the accumulation, tile and stage of the
+ * two matrix products (any pointer nullable).  set_debug(h, 1): a clustering keeps its finalized models and initial distances.  debug_read:
+ * returns the number of elements of an item, copied out where `out` holds them, or a negative amx_status.  SUMS: f64 [segments x (D + D (D +
+ * 1) / 2)], sum then the lower triangle of the square sum; R: f32 [N x N]; DIST: f32 [N x N], cells j < i, the rest 0; MODELS: f64 [N x (D + D
+ * D + 1)], mean, variance, log-determinant. */
+#define AMX_SEGCLUST_DEBUG_SUMS 0
+#define AMX_SEGCLUST_DEBUG_R 1
+#define AMX_SEGCLUST_DEBUG_DIST 2
+#define AMX_SEGCLUST_DEBUG_MODELS 3
+void amx_segclust_kernel_shape(int* stage_frames, int* tile_cells, int* gemm_tile, int* gemm_stage);
+int  amx_segclust_set_debug(amx_segclust* h, int keep);
+long amx_segclust_debug_read(amx_segclust* h, int what, void* out, long capacity);
+
 #ifdef __cplusplus
 }
 #endif

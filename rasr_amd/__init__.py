@@ -15,6 +15,7 @@ same reference interfaces for tests and benchmarks:
   BaumWelchAligner     Search::Aligner in mode baum-welch: forward-backward on the score matrix, per-frame item lists with posterior weights
   LatticeArcAligner    Speech::PhonemeSequenceAlignmentGenerator: one Viterbi alignment per (pronunciation, begin, end) of a word lattice's arcs
   LatticeAccuracy      Lattice/Accuracy.cc: approximate phone, frame-phone and frame-state accuracy per arc key from the arc alignments
+  SegmentClustering    Signal::SegmentClusteringNode (signal-segment-clustering): BIC speaker clustering of segments, the key per segment of CMLLR and MLLR
   StatePosteriorScorer Mm::StatePosteriorFeatureScorer (state posteriors, the tandem feature path and the discriminative accumulators' first step)
   CombinedScorer       Mm::CombinedFeatureScorer (log-linear combination of several models' score matrices)
   QuantileEqualization Signal::QuantileEqualization in segment mode (signal-quantile-equalization); QuantileEstimator: its estimate mode
@@ -32,7 +33,7 @@ from ._lib import (AMX_ACT_NONE, AMX_ACT_RELU, AMX_ACT_SIGMOID, AMX_ACT_TANH, AM
 __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer", "NnBatchFeatureScorer", "FileArchive", "AmxError", "read_pms", "write_pms",
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
-           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LatticeAccuracy", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
+           "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LatticeAccuracy", "SegmentClustering", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
            "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
@@ -3228,3 +3229,114 @@ class SegmentwiseNnTrainer:
         a, b = C.c_int(), C.c_int()
         _lib.check(self.L.amx_nnseq_last_shape(self.h, C.byref(a), C.byref(b)))
         return dict(sort_passes=a.value, sort_blocks=b.value)
+
+
+class SegmentClustering:
+    """Signal::SegmentClusteringNode<CorrFullCovMonoGaussianModel> (the node signal-segment-clustering): one full-covariance Gaussian per
+    segment, agglomerative clustering under the correlation distance, the BIC stopping rule.  Keyword names are the node's parameters
+    (lambda is spelt lambda_); ctx None gives a handle that only checks configurations.  cluster() returns the class id per accumulated
+    segment: the seg_key of AffineFeatureTransformEstimator.accumulate_dev and ModelTransformEstimator.accumulate_dev."""
+
+    def __init__(self, ctx, dim, **params):
+        self.L, self.h, self.ctx, self.dim = _lib.lib(), None, ctx, int(dim)
+        self.cfg = _lib.SegclustCfg()
+        self.L.amx_segclust_default_cfg(C.byref(self.cfg))
+        self.configure(**params)
+        h = C.c_void_p()
+        _lib.check(self.L.amx_segclust_create(ctx.h if ctx is not None else None, self.dim, C.byref(h)))
+        self.h = h
+
+    def configure(self, **params):
+        for k, v in params.items():
+            k = "lambda" if k == "lambda_" else k
+            if k not in dict(self.cfg._fields_):
+                raise TypeError("SegmentClustering: unknown parameter %r" % k)
+            if k == "infile":
+                v = None if v is None else os.fsencode(v)
+            setattr(self.cfg, k, v if k == "infile" else (float(v) if isinstance(getattr(self.cfg, k), float) else int(v)))
+
+    def close(self):
+        if self.h:
+            self.L.amx_segclust_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def kernel_shape():
+        """dict(stage_frames, tile_cells, gemm_tile, gemm_stage)"""
+        v = [C.c_int() for _ in range(4)]
+        _lib.lib().amx_segclust_kernel_shape(*(C.byref(x) for x in v))
+        return dict(zip(("stage_frames", "tile_cells", "gemm_tile", "gemm_stage"), (x.value for x in v)))
+
+    def segments(self):
+        return int(self.L.amx_segclust_segments(self.h))
+
+    def reset(self):
+        _lib.check(self.L.amx_segclust_reset(self.h))
+
+    def accumulate_dev(self, feats_dev, frame_offsets, feats_ld=None):
+        """append the segments [frame_offsets[s], frame_offsets[s + 1]) of the f32 feature matrix on the device"""
+        off = _offsets(frame_offsets, "SegmentClustering.accumulate_dev")
+        ld = self.dim if feats_ld is None else int(feats_ld)
+        _lib.check(self.L.amx_segclust_accumulate_dev(self.h, _ptr(feats_dev), ld, len(off) - 1, off.ctypes.data))
+
+    def cluster(self, **params):
+        """-> dict(class_ids int32 [segments], tracker (parent, child, score) of the N - 1 merges, and the fields of amx_segclust_info)"""
+        self.configure(**params)
+        S = self.segments()
+        ids = np.zeros(max(S, 1), np.int32)
+        tp, tc, ts = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.float32)
+        info = _lib.SegclustInfo()
+        _lib.check(self.L.amx_segclust_cluster(self.h, C.byref(self.cfg), _ptr(ids), _ptr(tp), _ptr(tc), _ptr(ts), C.byref(info)))
+        out = {n: getattr(info, n) for n, _ in _lib.SegclustInfo._fields_}
+        m = max(out["n_segments"] - 1, 0)
+        out.update(class_ids=ids[:S], tracker=(tp[:m], tc[:m], ts[:m]))
+        return out
+
+    @staticmethod
+    def choose(parent, child, score, n, mincluster=2, maxcluster=100000):
+        """findBestBIC and returnClustering over a tracker list -> (class_ids [n] as slot indices, n_clusters, best_index)"""
+        tp, tc = (np.ascontiguousarray(v, dtype=np.int32) for v in (parent, child))
+        ts = np.ascontiguousarray(score, dtype=np.float32)
+        if not len(tp) == len(tc) == len(ts) == n - 1:
+            raise ValueError("SegmentClustering.choose: %d segments need %d tracker records" % (n, n - 1))
+        ids, nc, best = np.zeros(max(n, 1), np.int32), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().amx_segclust_choose(int(n), _ptr(tp), _ptr(tc), _ptr(ts), int(mincluster), int(maxcluster), _ptr(ids), C.byref(nc), C.byref(best)))
+        return ids[:n], nc.value, best.value
+
+    @staticmethod
+    def write_map(path, ids, class_ids, default_ids=()):
+        """the `coprus-key-map` file of the node: default_ids with value 0, then ids with class_ids as given"""
+        cls = np.ascontiguousarray(class_ids, dtype=np.int32)
+        if len(cls) != len(ids):
+            raise ValueError("SegmentClustering.write_map: %d ids for %d class ids" % (len(ids), len(cls)))
+        a = (C.c_char_p * max(len(ids), 1))(*[os.fsencode(i) for i in ids])
+        d = (C.c_char_p * max(len(default_ids), 1))(*[os.fsencode(i) for i in default_ids])
+        _lib.check(_lib.lib().amx_segclust_write_map(os.fsencode(path), a, len(default_ids), d, len(ids), _ptr(cls)))
+
+    def set_debug(self, keep=True):
+        _lib.check(self.L.amx_segclust_set_debug(self.h, int(keep)))
+
+    def debug_read(self, what):
+        """DIAGNOSTIC: "sums" f64 [segments, D + D (D + 1) / 2]; "R" and "dist" f32 [N, N]; "models" f64 [N, D + D D + 1]"""
+        code, dtype = {"sums": (_lib.AMX_SEGCLUST_DEBUG_SUMS, np.float64), "R": (_lib.AMX_SEGCLUST_DEBUG_R, np.float32),
+                       "dist": (_lib.AMX_SEGCLUST_DEBUG_DIST, np.float32), "models": (_lib.AMX_SEGCLUST_DEBUG_MODELS, np.float64)}[what]
+        n = self.L.amx_segclust_debug_read(self.h, code, None, 0)
+        if n < 0:
+            _lib.check(int(n))
+        out = np.zeros(n, dtype)
+        r = self.L.amx_segclust_debug_read(self.h, code, _ptr(out), n) if n else 0
+        if r < 0:
+            _lib.check(int(r))
+        D = self.dim
+        if what == "sums":
+            return out.reshape(-1, D + D * (D + 1) // 2)
+        if what == "models":
+            return out.reshape(-1, D + D * D + 1)
+        side = int(round(n ** 0.5))
+        return out.reshape(side, side)

@@ -208,6 +208,16 @@ class AccuracyInfo(C.Structure):
     _fields_ = [(n, C.c_ulonglong) for n in ("runs", "reference_intervals", "keys_without_alignment")]
 
 
+class SegclustCfg(C.Structure):
+    _fields_ = [("minframes", C.c_int), ("mincluster", C.c_int), ("maxcluster", C.c_int), ("threshold", C.c_float), ("lambda", C.c_float),
+                ("alpha", C.c_float), ("minalpha", C.c_float), ("maxalpha", C.c_float), ("amalgamation", C.c_int), ("infile", C.c_char_p)]
+
+
+class SegclustInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_segments", "n_filtered", "n_clusters", "n_regularised", "best_index", "alpha_iterations")] + \
+        [("alpha", C.c_float), ("threshold", C.c_float)]
+
+
 class NnSeqCfg(C.Structure):
     _fields_ = [("weight_threshold", C.c_double), ("ce_smoothing_weight", C.c_float), ("frame_rejection_threshold", C.c_float),
                 ("log_prior", C.c_void_p), ("prior_scale", C.c_float), ("full_batch", C.c_int), ("accumulate_prior", C.c_int),
@@ -664,7 +674,20 @@ SIGNATURES = {
     "amx_accuracy_kernel_shape": (None, [C.POINTER(C.c_int)] * 3),
     "amx_accuracy_set_lds_intervals": (C.c_int, [_P, C.c_int]),
     "amx_accuracy_last_reference": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "amx_segclust_default_cfg": (None, [C.POINTER(SegclustCfg)]),
+    "amx_segclust_create": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "amx_segclust_destroy": (None, [_P]),
+    "amx_segclust_accumulate_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "amx_segclust_segments": (C.c_long, [_P]),
+    "amx_segclust_reset": (C.c_int, [_P]),
+    "amx_segclust_cluster": (C.c_int, [_P, C.POINTER(SegclustCfg), _P, _P, _P, _P, C.POINTER(SegclustInfo)]),
+    "amx_segclust_choose": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_segclust_write_map": (C.c_int, [C.c_char_p, _P, C.c_int, _P, C.c_int, _P]),
+    "amx_segclust_kernel_shape": (None, [C.POINTER(C.c_int)] * 4),
+    "amx_segclust_set_debug": (C.c_int, [_P, C.c_int]),
+    "amx_segclust_debug_read": (C.c_long, [_P, C.c_int, _P, C.c_long]),
 }
+AMX_SEGCLUST_DEBUG_SUMS, AMX_SEGCLUST_DEBUG_R, AMX_SEGCLUST_DEBUG_DIST, AMX_SEGCLUST_DEBUG_MODELS = 0, 1, 2, 3
 AMX_ACCURACY_APPROXIMATE_PHONE, AMX_ACCURACY_FRAME_PHONE, AMX_ACCURACY_FRAME_STATE = 0, 1, 2
 AMX_ARCALIGN_MAX_STATES, AMX_ARCALIGN_MAX_IN_ARCS, AMX_ARCALIGN_MAX_FRAMES = 256, 255, 65535
 AMX_ARCALIGN_ALIGNMENT_SCORE, AMX_ARCALIGN_EMISSION_SCORE = 0, 1
