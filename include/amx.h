@@ -1623,6 +1623,22 @@ int amx_f64_to_counts_dev(amx_ctx* ctx, const double* in_dev, unsigned long long
  * ascending-t f32 chain, the chunk partials are added in f32 in ascending order, and the total is widened into the buffer.  Objective
  * terms are summed in f64.  The same call gives the same bits.
  *
+ * Split-bf16 GEMMs (cfg.gemm = AMX_NNTRAIN_GEMM_BF16X3; the default AMX_NNTRAIN_GEMM_F32 is everything above, bit for bit).  The three
+ * matrix products of a pass -- W X (forward), W^T E (backpropagation), X E^T (gradient) -- take every operand element v as hi + lo, hi =
+ * bf16(v), lo = bf16(v - hi), both round to nearest even (v - hi is exact in f32), and a product a b as a_hi b_hi + a_hi b_lo + a_lo b_hi
+ * (a: the operand named first above): the lo lo term and lo's own rounding are dropped, about 3 * 2^-18 |a| |b| per product.  An output
+ * element is ONE f32 accumulator chain of v_mfma_f32_32x32x16_bf16 from zero over ascending k in steps of 16, each step adding its
+ * three products in the order written; for X E^T k is the frame, a chain covers one chunk of AMX_NNTRAIN_CHUNK frames, and the chunk
+ * partials are added as above.  So the order of every sum is still fixed by the call alone, and the same call gives the same bits.
+ * Everything else is unchanged and f32: parameters and both weight images, layer outputs, error signals, bias, activation, derivative
+ * and clip (applied to the f32 accumulator exactly as in the f32 pass), softmax, criterion, column sums, files, the step's update.
+ * model->precision stays AMX_PREC_FP32: it names the parameters' storage.  Zero splits into two zeros: padding stays exact.
+ * Outside the promise: a magnitude whose bf16 rounding overflows (about 3.39e38 and above: hi becomes infinite); and lo values below
+ * the smallest normal bf16 (|v - hi| < 2^-126, i.e. |v| below about 2^-118): whether the conversion and the matrix pipe keep bf16
+ * subnormals has not been measured, so such an element may count as hi alone.
+ * Workspace: the planes hold 4 bytes per element as they lie and 4 more transposed, so every layer's input and error signal takes
+ * three times its f32 size, and each weight image twice.
+ *
  * Labels are checked on the device before anything is written: emission_dev[t] >= n_classes, or an output index >= n_outputs, makes
  * the call return AMX_ERR_INVALID naming the first such frame (the reference `require`s), acc_dev untouched; a bad label never
  * becomes an address.  At most AMX_NNTRAIN_MAX_FRAMES frames per call (split longer batches: the buffer adds up).  The cap bounds the
@@ -1640,6 +1656,7 @@ enum { AMX_NNSTAT_CLASS_COUNTS = 1, AMX_NNSTAT_MEAN_AND_VARIANCE = 2, AMX_NNSTAT
 #define AMX_NNTRAIN_CHUNK 256
 #define AMX_NNTRAIN_MAX_FRAMES 4096
 #define AMX_NNTRAIN_MAX_LAYERS 16
+enum { AMX_NNTRAIN_GEMM_F32 = 0, AMX_NNTRAIN_GEMM_BF16X3 = 1 };
 typedef struct {
     int          statistics;        /* AMX_NNSTAT_* mask (default BASE | GRADIENT) */
     float        error_signal_clip; /* `error-signal-clip`; Core::Type<f32>::max = off (default) */
@@ -1648,6 +1665,7 @@ typedef struct {
     int          n_outputs;         /* model == NULL only: the number of network outputs (class counts) */
     int          n_classes;         /* model == NULL only: length of class_to_output (ignored when that is NULL) */
     const int*   class_to_output;   /* model == NULL only: as amx_ffnn_model.class_to_output, nullable */
+    int          gemm;              /* AMX_NNTRAIN_GEMM_*: the arithmetic of the three GEMM kinds (default F32); anything else: AMX_ERR_INVALID */
 } amx_nntrain_cfg;
 typedef struct {
     int  n_layers, feature_dim, n_outputs;

@@ -2106,13 +2106,15 @@ class FeedForwardTrainer:
     """Nn::FeedForwardTrainer in batch mode and Nn::MeanAndVarianceTrainer: the statistics pass over aligned frames into ONE flat f64
     accumulator (include/amx.h, "NN training statistics").  Ws[l] is [out, in] as NnBatchFeatureScorer takes it; Ws=None builds no
     network (class counts and mean and variance only; give feature_dim / n_outputs).  ctx may be None for host-only use (files, prior,
-    mean and deviation)."""
+    mean and deviation).  gemm: "f32" (default: the f32 matrix pipe, the reference's bits of a product) or "bf16x3" (split bf16: three
+    bf16 products per f32 product, f32 accumulation; parameters, outputs and statistics stay f32)."""
 
     FLAGS = {"class-counts": _lib.AMX_NNSTAT_CLASS_COUNTS, "mean-and-variance": _lib.AMX_NNSTAT_MEAN_AND_VARIANCE,
              "base": _lib.AMX_NNSTAT_BASE, "gradient": _lib.AMX_NNSTAT_GRADIENT}
+    GEMMS = {"f32": _lib.AMX_NNTRAIN_GEMM_F32, "bf16x3": _lib.AMX_NNTRAIN_GEMM_BF16X3}
 
     def __init__(self, ctx, Ws=None, biases=None, activations=None, statistics=("base", "gradient"), error_signal_clip=None, class_weights=None,
-                 class_to_output=None, preprocessing=None, maxout=None, feature_dim=0, n_outputs=0, precision="fp32"):
+                 class_to_output=None, preprocessing=None, maxout=None, feature_dim=0, n_outputs=0, precision="fp32", gemm="f32"):
         self.ctx, self.L = ctx, _lib.lib()
         mask = statistics if isinstance(statistics, int) else sum(self.FLAGS[s] for s in set(statistics))
         cfg = _lib.NnTrainCfg()
@@ -2120,6 +2122,8 @@ class FeedForwardTrainer:
         cfg.statistics = mask
         if error_signal_clip is not None:
             cfg.error_signal_clip = error_signal_clip
+        # the arithmetic of the three GEMM kinds; an integer goes through as it is (the library refuses what it does not know)
+        cfg.gemm = gemm if isinstance(gemm, int) else self.GEMMS[gemm]
         self._cw = None if class_weights is None else np.ascontiguousarray(class_weights, dtype=np.float32)
         self._map = None if class_to_output is None else np.ascontiguousarray(class_to_output, dtype=np.int32)
         cfg.class_weights = _ptr(self._cw)

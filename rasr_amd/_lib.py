@@ -306,11 +306,12 @@ class FfnnLayers(C.Structure):
 
 AMX_NNSTAT_CLASS_COUNTS, AMX_NNSTAT_MEAN_AND_VARIANCE, AMX_NNSTAT_BASE, AMX_NNSTAT_GRADIENT = 1, 2, 4, 8
 AMX_NNTRAIN_CHUNK, AMX_NNTRAIN_MAX_FRAMES, AMX_NNTRAIN_MAX_LAYERS = 256, 4096, 16
+AMX_NNTRAIN_GEMM_F32, AMX_NNTRAIN_GEMM_BF16X3 = 0, 1
 
 
 class NnTrainCfg(C.Structure):
     _fields_ = [("statistics", C.c_int), ("error_signal_clip", C.c_float), ("class_weights", C.c_void_p), ("feature_dim", C.c_int),
-                ("n_outputs", C.c_int), ("n_classes", C.c_int), ("class_to_output", C.c_void_p)]
+                ("n_outputs", C.c_int), ("n_classes", C.c_int), ("class_to_output", C.c_void_p), ("gemm", C.c_int)]
 
 
 class NnTrainLayout(C.Structure):

@@ -664,7 +664,7 @@ int amx_nnseq_forward_dev(amx_nnseq* h, const float* feats, int ldf, int n_seg, 
     }
     {
         amx::ScopedKernelTimer timer(t->ctx, "nnseq_gemm_forward");
-        amx::nntrain_launch_forward(t, R, R, st);
+        AMX_TRY(amx::nntrain_launch_forward(t, R, R, st));
         AMX_HIP(hipGetLastError());
     }
     {
@@ -832,7 +832,7 @@ int amx_nnseq_accumulate_dev(amx_nnseq* h, int n_pass, const amx_nnseq_pass* pas
         if (grad) {
             {
                 amx::ScopedKernelTimer timer(t->ctx, "nnseq_gemm_backward");
-                amx::nntrain_launch_backward(t, R, FLT_MAX, st);  // the segment-wise trainer has no error-signal-clip
+                AMX_TRY(amx::nntrain_launch_backward(t, R, FLT_MAX, st));  // the segment-wise trainer has no error-signal-clip
                 AMX_HIP(hipGetLastError());
             }
             const int n_chunks = R / AMX_NNTRAIN_CHUNK;
@@ -840,7 +840,7 @@ int amx_nnseq_accumulate_dev(amx_nnseq* h, int n_pass, const amx_nnseq_pass* pas
                 const int Kp = t->Pin[l], Np = t->Pout[l];
                 {
                     amx::ScopedKernelTimer timer(t->ctx, "nnseq_gemm_tn");
-                    amx::nntrain_launch_gemm_tn(t, l, R, n_chunks, st);
+                    AMX_TRY(amx::nntrain_launch_gemm_tn(t, l, R, n_chunks, st));
                 }
                 amx::ScopedKernelTimer timer(t->ctx, "nnseq_gradient_sums");
                 hipLaunchKernelGGL(amx::nnseq_reduce_kernel, dim3(blocks_for((long long)t->in[l] * t->out[l])), dim3(amx::kSeqThreads), 0, st,

@@ -542,6 +542,8 @@ int step_estimate(amx_nntrain* h, int normalize, const char* who) {
                            s.log_step ? up_b : 0, s.d_group.get() + amx::GRP_STEP + l);
     }
     AMX_HIP(hipGetLastError());
+    if (h->gemm == AMX_NNTRAIN_GEMM_BF16X3)  // both weight images have changed: their planes follow
+        AMX_TRY(amx::nntrain_x3_split_weights(h, st));
     return AMX_OK;
 }
 

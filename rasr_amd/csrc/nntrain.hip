@@ -438,6 +438,8 @@ inline int pad128(int n) {
 
 }  // namespace amx
 
+#include "nntrain_x3.hpp"  // the same three GEMM kinds on split bf16 (amx_nntrain_cfg.gemm)
+
 // ------------------------------------------------------------------------------------ handle
 
 namespace {
@@ -529,10 +531,13 @@ int amx_nntrain_create(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
     *out = nullptr;
     AMX_REQUIRE(cfg->statistics > 0 && cfg->statistics < 16, AMX_ERR_INVALID, "amx_nntrain_create: statistics = %d is no mask of the four statistics flags", cfg->statistics);
     AMX_REQUIRE(cfg->error_signal_clip > 0.f, AMX_ERR_INVALID, "amx_nntrain_create: error_signal_clip must be positive");
+    AMX_REQUIRE(cfg->gemm == AMX_NNTRAIN_GEMM_F32 || cfg->gemm == AMX_NNTRAIN_GEMM_BF16X3, AMX_ERR_INVALID,
+                "amx_nntrain_create: gemm = %d (0: the f32 matrix pipe, 1: split bf16)", cfg->gemm);
     std::unique_ptr<amx_nntrain> h(new amx_nntrain);
     h->ctx  = ctx;
     h->mask = cfg->statistics;
     h->clip = cfg->error_signal_clip;
+    h->gemm = cfg->gemm;
     const int*  c2o       = nullptr;
     if (!m) {
         AMX_REQUIRE(!(h->mask & (AMX_NNSTAT_BASE | AMX_NNSTAT_GRADIENT)), AMX_ERR_INVALID,
@@ -626,6 +631,11 @@ int amx_nntrain_create(amx_ctx* ctx, const amx_ffnn_model* m, const amx_ffnn_lay
             AMX_TRY(upload_padded(h->d_WT[l], WT));
             AMX_TRY(upload_padded(h->d_bias[l], b));
         }
+        if (h->gemm == AMX_NNTRAIN_GEMM_BF16X3) {
+            for (auto* v : {&h->p_W, &h->p_WT, &h->p_x, &h->p_xT, &h->p_E, &h->p_ET})
+                *v = std::vector<amx::DevBuf<amx::x3_bf16_t>>(h->L);
+            AMX_TRY(amx::nntrain_x3_split_weights(h.get(), ctx->stream));
+        }
         if (m && ext && ext->n_pre > 0) {
             h->d_pre_mean = std::vector<amx::DevBuf<float>>(ext->n_pre);
             h->d_pre_rstd = std::vector<amx::DevBuf<float>>(ext->n_pre);
@@ -664,7 +674,9 @@ int amx_nntrain_layout(const amx_nntrain* h, amx_nntrain_layout_info* info) {
 namespace amx {
 
 // ---- the launches of a pass that the segment-wise trainer (nnseq.hip) runs on its own rows: nntrain_pass goes through these too
-void nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st) {
+int nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st) {
+    if (h->gemm == AMX_NNTRAIN_GEMM_BF16X3)
+        return nntrain_x3_forward(h, Tpad, T, st);
     const int L = h->L, n_out = h->n_outputs;
     for (int l = 0; l < L; ++l) {
         const int    ntn = h->Pout[l] / amx::BN, ntt = Tpad / amx::BT;
@@ -689,6 +701,7 @@ void nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st) {
             }
         }
     }
+    return AMX_OK;
 }
 
 void nntrain_launch_softmax(amx_nntrain* h, int T, hipStream_t st) {
@@ -702,7 +715,9 @@ void nntrain_launch_softmax(amx_nntrain* h, int T, hipStream_t st) {
                        (const float*)row_sum);
 }
 
-void nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st) {
+int nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st) {
+    if (h->gemm == AMX_NNTRAIN_GEMM_BF16X3)
+        return nntrain_x3_backward(h, Tpad, clip, st);
     const int L = h->L;
     for (int l = L - 1; l >= 1; --l) {
         const int    ntn = h->Pin[l] / amx::BN, ntt = Tpad / amx::BT, do_clip = (l - 1 > 0 && clip < FLT_MAX) ? 1 : 0;
@@ -723,12 +738,16 @@ void nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t s
                 hipLaunchKernelGGL(amx::nntrain_gemm_bwd_kernel<AMX_ACT_NONE>, grid, block, 0, st, WT, E, Y, o, h->Pout[l], h->Pin[l], ntn, clip, do_clip);
         }
     }
+    return AMX_OK;
 }
 
-void nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st) {
+int nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st) {
+    if (h->gemm == AMX_NNTRAIN_GEMM_BF16X3)
+        return nntrain_x3_gemm_tn(h, l, Tpad, tn_chunks, st);
     const int Kp = h->Pin[l], Np = h->Pout[l], ntn = Np / 128, ntk = Kp / 128;
     hipLaunchKernelGGL(amx::nntrain_gemm_tn_kernel, dim3(ntk * ntn, tn_chunks), dim3(256), 0, st, (const float*)h->d_x[l].get(),
                        (const float*)h->d_E[l].get(), h->d_part.get(), Kp, Np, Tpad, ntn);
+    return AMX_OK;
 }
 
 void nntrain_launch_bias_sums(amx_nntrain* h, int l, int T, int n_chunks, hipStream_t st) {
@@ -814,7 +833,7 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
         }
         {
             amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_forward");
-            amx::nntrain_launch_forward(h, Tpad, T, st);
+            AMX_TRY(amx::nntrain_launch_forward(h, Tpad, T, st));
             AMX_HIP(hipGetLastError());
         }
         {   // the softmax of the forward node on the dense [T x n_out] scores (= -activation)
@@ -841,7 +860,7 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
         // 6. error backpropagation: E_{l-1} = (W_l^T E_l) (.) f'(Y_{l-1}); E_{l-1} is clipped unless it is the lowest layer's
         {
             amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_backward");
-            amx::nntrain_launch_backward(h, Tpad, h->clip, st);
+            AMX_TRY(amx::nntrain_launch_backward(h, Tpad, h->clip, st));
             AMX_HIP(hipGetLastError());
         }
         // 7. gradients: G_l += X_l E_l^T, g_l += the column sums of E_l
@@ -851,7 +870,7 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
                 const int Kp = h->Pin[l], Np = h->Pout[l];
                 {
                     amx::ScopedKernelTimer timer(h->ctx, "nntrain_gemm_tn");
-                    amx::nntrain_launch_gemm_tn(h, l, Tpad, tn_chunks, st);
+                    AMX_TRY(amx::nntrain_launch_gemm_tn(h, l, Tpad, tn_chunks, st));
                 }
                 amx::ScopedKernelTimer timer(h->ctx, "nntrain_gradient_sums");
                 const long long total = (long long)h->in[l] * h->out[l];

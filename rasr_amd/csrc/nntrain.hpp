@@ -8,6 +8,8 @@
 
 namespace amx {
 
+typedef unsigned short x3_bf16_t;  // a bf16 of the split planes (nntrain_x3.hpp)
+
 // Where the pass of nntrain.hip puts a call's results in mini-batch training (nnstep.hip) instead of the caller's f64 buffer: the
 // call's tail, and the call's gradient added into the group's f32 statistic with the regulariser's axpy behind it.
 struct StepSink {
@@ -53,6 +55,7 @@ struct amx_nntrain {
     amx_ctx* ctx  = nullptr;
     int      mask = 0;
     float    clip = FLT_MAX;
+    int      gemm = AMX_NNTRAIN_GEMM_F32;  // AMX_NNTRAIN_GEMM_*: which kernels the three launch functions below take
     int      L = 0, feature_dim = 0, n_outputs = 0, n_classes = 0;
     std::vector<int>   in, out, act, Pin, Pout;
     std::vector<int>   class_to_output;  // empty = identity
@@ -71,6 +74,9 @@ struct amx_nntrain {
     amx::DevBuf<int>      d_label;
     amx::DevBuf<unsigned> d_err, d_bad;
     amx::DevBuf<unsigned, true> h_bad;
+    // AMX_NNTRAIN_GEMM_BF16X3 only (nntrain_x3.hpp): hi plane, then lo plane, of the weight images (split whenever they change), of every
+    // layer's input and error signal as they lie, and of both transposed [units x Tpad] for X E^T
+    std::vector<amx::DevBuf<amx::x3_bf16_t>> p_W, p_WT, p_x, p_xT, p_E, p_ET;
     amx::NnStep           step;
     unsigned long         workspace_epoch = 0;  // counts the calls that fill the workspace: nnseq.hip sees whether its batch is still there
 };
@@ -86,11 +92,19 @@ int nntrain_pass(amx_nntrain* h, const float* feats, int ldf, int T, const uint3
 // and d_w itself; nntrain_pass goes through the same functions.  forward: every layer from d_x[0] [Tpad x Pin], the negated top
 // output into d_top [T x n_outputs]; softmax: d_top in place (d_rowstat holds 2 T floats); backward: d_E[l - 1] from d_E[l], clip ==
 // FLT_MAX: none; gemm_tn: the chunk partials of X_l E_l^T into d_part; bias_sums: the chunk partials of E_l's column sums into d_part.
-void nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st);
+// The three GEMM kinds switch on h->gemm; with the split planes they may have to grow the planes, hence the status.
+int  nntrain_launch_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st);
 void nntrain_launch_softmax(amx_nntrain* h, int T, hipStream_t st);
-void nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st);
-void nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st);
+int  nntrain_launch_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st);
+int  nntrain_launch_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st);
 void nntrain_launch_bias_sums(amx_nntrain* h, int l, int T, int n_chunks, hipStream_t st);
+
+// nntrain_x3.hpp: the same three on the split-bf16 planes.  forward splits every layer's input in front of its GEMM (d_x[0] is the
+// caller's), backward splits d_E[top] first and every error signal it writes; split_weights: after anything that wrote d_W / d_WT
+int nntrain_x3_split_weights(amx_nntrain* h, hipStream_t st);
+int nntrain_x3_forward(amx_nntrain* h, int Tpad, int T, hipStream_t st);
+int nntrain_x3_backward(amx_nntrain* h, int Tpad, float clip, hipStream_t st);
+int nntrain_x3_gemm_tn(amx_nntrain* h, int l, int Tpad, int tn_chunks, hipStream_t st);
 
 // the regulariser's axpy alone on the sink's statistic as it stands (amx_nntrain_estimate): factor = group_tail[0] + call_tail[0]
 int nntrain_add_regularizer(amx_nntrain* h, const StepSink* sink);

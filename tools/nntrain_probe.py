@@ -14,7 +14,9 @@ GEMM kinds have pairs that enclose their launches and nothing else: nntrain_gemm
 (6 x nntrain_gemm_bwd_kernel), nntrain_gemm_tn (7 x nntrain_gemm_tn_kernel, one pair per layer); each kind's rate is its multiply-adds
 (2 T sum in x out; the backward kind has no first layer) over its time per call.  The other pairs: nntrain_pack, nntrain_softmax,
 nntrain_error, nntrain_gradient_sums (the partial adds into the f64 buffer and the bias column sums), nntrain_feature_sums.  No time is
-fixed in advance."""
+fixed in advance.
+--gemm f32,bf16x3 (a step's list): one handle per arithmetic in ONE process, the rounds alternating between them, one JSON line each.
+With bf16x3 the GEMM kinds' pairs enclose their split passes too (nntrain_x3.hpp), which nntrain_x3_split reports on its own."""
 import argparse
 import json
 import os
@@ -28,7 +30,7 @@ sys.path.insert(0, ROOT)
 
 STEPS = ("accumulate", "gemm_kinds")
 SECTIONS = ("nntrain_feature_sums", "nntrain_pack", "nntrain_gemm_forward", "nntrain_softmax", "nntrain_error", "nntrain_gemm_backward", "nntrain_gemm_tn",
-            "nntrain_gradient_sums")
+            "nntrain_gradient_sums", "nntrain_x3_split")
 
 
 def step(a):
@@ -40,51 +42,58 @@ def step(a):
     ctx.use_torch_stream()
     dims = [440] + [2048] * 6 + [10000]
     Ws, bs, acts, _ = synth.ffnn(dims, seed=7)
-    tr = rasr_amd.FeedForwardTrainer(ctx, Ws, bs, acts, statistics=("class-counts", "mean-and-variance", "base", "gradient"))
+    gemms = a.gemm.split(",")
+    trs = {g: rasr_amd.FeedForwardTrainer(ctx, Ws, bs, acts, statistics=("class-counts", "mean-and-variance", "base", "gradient"), gemm=g) for g in gemms}
     T = a.frames
     rng = np.random.Generator(np.random.PCG64(5))
     feats = torch.from_numpy(rng.standard_normal((T, dims[0])).astype(np.float32)).cuda()
     emission = torch.from_numpy(rng.integers(0, dims[-1], T).astype(np.int32)).cuda()
-    acc = torch.zeros(tr.accumulator_size(), dtype=torch.float64, device="cuda")
+    acc = torch.zeros(trs[gemms[0]].accumulator_size(), dtype=torch.float64, device="cuda")
 
-    def run():
-        tr.accumulate_dev(feats, dims[0], T, emission, acc)
+    def run(g):
+        trs[g].accumulate_dev(feats, dims[0], T, emission, acc)
     mac = [i * n for i, n in zip(dims[:-1], dims[1:])]
     flop = {"nntrain_gemm_forward": 2.0 * T * sum(mac), "nntrain_gemm_backward": 2.0 * T * sum(mac[1:]), "nntrain_gemm_tn": 2.0 * T * sum(mac)}
-    res = {"step": a.step, "network": "440-6x2048-10000", "frames": T, "reps": a.reps, "iters": a.iters, "accumulator_mb": round(acc.numel() * 8 / 1e6, 1)}
-    run()
+    res = {g: {"step": a.step, "gemm": g, "network": "440-6x2048-10000", "frames": T, "reps": a.reps, "iters": a.iters,
+               "accumulator_mb": round(acc.numel() * 8 / 1e6, 1)} for g in gemms}
+    for g in gemms:
+        run(g)
     torch.cuda.synchronize()
     if a.step == "accumulate":
-        times = []
+        times = {g: [] for g in gemms}
         for _ in range(a.reps):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(a.iters):
-                run()
-            e.record()
-            torch.cuda.synchronize()
-            times.append(s.elapsed_time(e) / a.iters)
-        v = np.array(times)
-        res.update(median_ms=round(float(np.median(v)), 4), min_ms=round(float(v.min()), 4), max_ms=round(float(v.max()), 4),
-                   gemm_tflops=round(sum(flop.values()) / float(np.median(v)) / 1e9, 2))
-        print("accumulate   median %.4f ms  spread %.4f .. %.4f ms  (%.1f TF over the three GEMM kinds)" % (res["median_ms"], res["min_ms"], res["max_ms"], res["gemm_tflops"]))
+            for g in gemms:
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(a.iters):
+                    run(g)
+                e.record()
+                torch.cuda.synchronize()
+                times[g].append(s.elapsed_time(e) / a.iters)
+        for g in gemms:
+            v, r = np.array(times[g]), res[g]
+            r.update(median_ms=round(float(np.median(v)), 4), min_ms=round(float(v.min()), 4), max_ms=round(float(v.max()), 4),
+                     gemm_tflops=round(sum(flop.values()) / float(np.median(v)) / 1e9, 2))
+            print("accumulate %-7s median %.4f ms  spread %.4f .. %.4f ms  (%.1f TF over the three GEMM kinds)" % (g, r["median_ms"], r["min_ms"], r["max_ms"], r["gemm_tflops"]))
     else:
         ctx.profile(True)
-        ctx.profile_reset()
-        for _ in range(a.iters):
-            run()
-        torch.cuda.synchronize()
-        for k in SECTIONS:
-            ms, launches = ctx.profile_get(k)   # the mean over the event pairs of that name, and how many there were
-            if launches:
-                ms = ms * launches / a.iters    # per call (nntrain_gemm_tn and nntrain_gradient_sums have one pair per layer)
-                res[k + "_ms"] = round(ms, 4)
-                if k in flop:
-                    res[k + "_tflops"] = round(flop[k] / ms / 1e9, 2)
-                print("%-24s %.4f ms per call%s" % (k, ms, "  %.1f TF" % res[k + "_tflops"] if k in flop else ""))
+        for g in gemms:
+            ctx.profile_reset()
+            for _ in range(a.iters):
+                run(g)
+            torch.cuda.synchronize()
+            for k in SECTIONS:
+                ms, launches = ctx.profile_get(k)   # the mean over the event pairs of that name, and how many there were
+                if launches:
+                    ms = ms * launches / a.iters    # per call (nntrain_gemm_tn and nntrain_gradient_sums have one pair per layer)
+                    res[g][k + "_ms"] = round(ms, 4)
+                    if k in flop:
+                        res[g][k + "_tflops"] = round(flop[k] / ms / 1e9, 2)
+                    print("%-7s %-24s %.4f ms per call%s" % (g, k, ms, "  %.1f TF" % res[g][k + "_tflops"] if k in flop else ""))
         ctx.profile(False)
-    print(json.dumps(res))
-    tr.close()
+    for g in gemms:
+        print(json.dumps(res[g]))
+        trs[g].close()
     ctx.close()
 
 
@@ -94,6 +103,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--gemm", default="f32", help="f32, bf16x3 or both separated by a comma (alternating in one process)")
     ap.add_argument("--timeout", type=int, default=180, help="seconds for each step of the driver")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nntrain_probe.jsonl"))
     a = ap.parse_args()
@@ -102,14 +112,14 @@ def main():
     lines = []
     for name in STEPS:
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(a.reps), "--iters", str(a.iters),
-               "--frames", str(a.frames)]
+               "--frames", str(a.frames), "--gemm", a.gemm]
         r = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:   # nothing more is started after a step that failed, faulted or ran into its limit
             sys.stderr.write(r.stderr)
             sys.exit("nntrain_probe: step %s ended with status %d; stopping" % (name, r.returncode))
-        lines.append([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    with open(a.out, "w") as f:
+        lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
+    with open(a.out, "a") as f:
         f.write("\n".join(lines) + "\n")
     print("wrote %s" % a.out)
 
