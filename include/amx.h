@@ -2296,6 +2296,94 @@ int  amx_latpost_last_potentials(const amx_latpost* h, long n_states, double* fo
  * the kernels' times are the event timers' (amx_profile_get "latpost_potentials", "latpost_arcs") */
 int  amx_latpost_last_timing(const amx_latpost* h, double* plan_ms, double* upload_ms);
 
+/* ------------------------------------------------------------------ Lattice best path and forward-backward pruning */
+
+/* The tropical-semiring half of the lattice chain, for a batch of lattices per call, the results left on the device: Fsa::bestscore and
+ * Fsa::best (Fsa/tBest.cc:30-123; Nn/SegmentwiseNnTrainer.cc:716, Speech/AdvancedLatticeSetProcessor.cc:113) and Fsa::prunePosterior
+ * (Fsa/tPrune.cc:28-146, reached through Lattice::prune, Lattice/Posterior.cc:114-133), in f32.  Fsa::TropicalSemiring is
+ * TropicalSemiring_(1): compare(a, b) is 0 when a == b or when the two are within ONE ulp (Core::isAlmostEqualUlp on the bit patterns,
+ * signs mirrored, Core/Utility.cc:61-73), so nothing below is an exact minimum: each result is one ordered chain of such comparisons.
+ *   forward      fw = sssp(f) (Fsa/tSssp.cc:150-227): d = Zero (f32 max), d[initial] = One (0).  States are dequeued in the order of
+ *                Fsa::topologicallySort (descending finishing time of the stack walk of Fsa/tDfs.cc:21-68); per arc ext = f32(d[source] + w),
+ *                and d[target] becomes ext iff ext < d[target] and the two are not within one ulp.  A state whose d was never replaced is
+ *                never queued and relaxes nothing.
+ *   backward     bw = sssp(transpose(f)): the same loop on the transposed automaton (arc order and new initial state as described for
+ *                the arc posteriors above), in ITS topological order; the new initial state's arcs carry the final weights and are
+ *                relaxed first.  best_score = bw[initial].
+ *   best arc     BestAutomaton::getState (tBest.cc:70-95): over the outgoing arcs in arc order w = f32(weight + bw[target]); an arc wins
+ *                when compare(w, min) < 0, min starting at f32 max; a final weight wins only when compare(final, min) < 0.
+ *                best_arc_dev[state] is the winning arc counted over the call, -1 for none, for a final state that wins, and for a state
+ *                the walk does not reach.  path_dev: per segment, from state_offsets[g] on, the arcs met by following best_arc from the
+ *                initial state, then -1 up to the segment's end.
+ *   pruning      w(a) = f32(fw[source] + f32(weight + bw[target])) (tPrune.cc:104-105).  relative = 1: minWeight starts at f32 max and
+ *                runs as one chain over the arcs of the states in discover order, within a state in arc order, replaced when
+ *                compare(w, minWeight) < 0; then minWeight = f32(minWeight + threshold).  relative = 0: f32(bw[initial] + threshold).
+ *                keep_dev[arc] = compare(w(a), minWeight) <= 0; arcs of states the walk does not reach are not kept.  A threshold that is
+ *                not below f32 max keeps every arc and runs no pruning (Posterior.cc:116).
+ *   trim         cfg.trim = 1: afterwards keep is cleared for every arc whose source is not reachable from the initial state over kept
+ *                arcs or whose target reaches no final state over kept arcs (the trimming the comment at tPrune.cc:24-27 recommends).
+ *   kept_index_dev[arc]  the position of a kept arc among its segment's kept arcs, -1 otherwise.
+ * Input: the CSR tables of amx_latpost_run_dev, in host memory, and the same refusals (AMX_ERR_INVALID naming the first offender, outputs
+ * untouched): a cycle, a target outside its segment, an initial state out of range, a NaN weight, offsets that do not ascend.
+ * A segment in which no final state is reached has reason AMX_LATBEST_NO_FINAL: best_score is the semiring's invalid() (f32 min =
+ * -f32 max, tBest.cc:112), the backward potentials stay Zero, there is no best arc and no path, and pruning keeps nothing.
+ * Order and determinism as for the arc posteriors: no floating-point atomics, a segment gives the same bits alone and in any batch.
+ * NOT BUILT: the f32 log-semiring form of prunePosterior; pruneSync; the fail-arc variants (*4SpecialSymbols); nbest and firstbest; a
+ * pin of the restatement (tests/latbest_reference.py) on the reference's compiled text, a fixture in the style of ref_latpost.npz. */
+enum { AMX_LATBEST_OK = 0, AMX_LATBEST_NO_FINAL = 1 };
+typedef struct amx_latbest amx_latbest;
+typedef struct {
+    float threshold;  /* f32 max: no pruning */
+    int   relative;   /* 1 */
+    int   trim;       /* 0 */
+    int   potentials; /* AMX_LATPOST_POTENTIALS_AUTO: in LDS while a segment's states fit (amx_latbest_kernel_shape); _GLOBAL: always global */
+} amx_latbest_cfg;
+typedef struct {
+    float best_score;            /* bw[initial]; f32 min with NO_FINAL */
+    float min_weight;            /* minWeight before the threshold is added (f32 max without pruning or with NO_FINAL) */
+    float min_weight_threshold;  /* ... and after */
+    int   reason;                /* AMX_LATBEST_OK | AMX_LATBEST_NO_FINAL */
+    int   path_length;           /* arcs of the best path */
+    int   kept_arcs, total_arcs;
+    int   states_reached;        /* by the walk from the initial state */
+    int   states_coreached;      /* by the transposed walk (the new initial state not counted) */
+    int   levels_forward, levels_backward; /* barriers of the two workgroups */
+} amx_latbest_info;
+void amx_latbest_cfg_default(amx_latbest_cfg* cfg);
+/* ctx NULL: a host-only handle (amx_latbest_plan_host) */
+int  amx_latbest_create(amx_ctx* ctx, const amx_latbest_cfg* cfg /* NULL: defaults */, amx_latbest** out);
+void amx_latbest_destroy(amx_latbest* h);
+/* the potentials kernel's launch shape: threads of a workgroup, the largest number of states of a segment whose f32 potentials live in
+ * LDS, the number of arcs from which a chain is shared by a wave */
+void amx_latbest_kernel_shape(int* threads, int* lds_states, int* wave_arcs);
+/* Device outputs: best_arc_dev [n_states], path_dev [n_states], keep_dev [n_arcs], kept_index_dev [n_arcs]; info [n_seg] in host memory,
+ * nullable.  Synchronises the stream once, at the end. */
+int  amx_latbest_run_dev(amx_latbest* h, int n_seg, const long* state_offsets /*[n_seg+1]*/, const long* arc_offsets /*[n_states+1]*/,
+                         const int32_t* arc_target, const float* arc_weight, const int32_t* initial /*[n_seg]*/, const uint8_t* final_flag,
+                         const float* final_weight, int32_t* best_arc_dev, int32_t* path_dev, uint8_t* keep_dev, int32_t* kept_index_dev,
+                         amx_latbest_info* info);
+/* The host plan alone (no device): the checks and, per state counted over the call, discover_index, topo_forward / topo_backward (the
+ * state's number in Fsa::topologicallySort of the automaton / of its transpose, -1: not reached), level_forward / level_backward (the
+ * level at which the state's chain runs, -1: not walked); topo_super [n_seg]: the new initial state's number in the transposed order (0),
+ * -1 with NO_FINAL.  Every output nullable; info's discrete fields that need no device are filled. */
+int  amx_latbest_plan_host(const amx_latbest* h, int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target,
+                           const float* arc_weight, const int32_t* initial, const uint8_t* final_flag, const float* final_weight,
+                           int32_t* discover_index, int32_t* topo_forward, int32_t* topo_backward, int32_t* topo_super, int32_t* level_forward,
+                           int32_t* level_backward, amx_latbest_info* info);
+/* Host only: the pruned CSR tables from a keep array (amx_copy_to_host of keep_dev).  State ids are unchanged, as in
+ * PosteriorPruneAutomaton, so state_offsets, initial and the final tables go on as they are: out_arc_offsets [n_states + 1],
+ * out_arc_target / out_arc_weight [room for n_arcs], old_to_new [n_arcs] (nullable; -1: dropped), *n_kept (nullable).  The result goes
+ * straight into amx_latpost_run_dev and the arc aligner's key tables. */
+int  amx_latbest_compact(int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target, const float* arc_weight,
+                         const uint8_t* keep, long* out_arc_offsets, int32_t* out_arc_target, float* out_arc_weight, int32_t* old_to_new,
+                         long* n_kept);
+/* DIAGNOSTIC (tests, probes): the potentials of the last amx_latbest_run_dev, per state counted over the call.  Both nullable. */
+int  amx_latbest_last_potentials(const amx_latbest* h, long n_states, float* forward, float* backward);
+/* DIAGNOSTIC (tools/latbest_probe.py): host wall time of the last call's plan and of packing and enqueueing its uploads, in ms; the
+ * kernels' times are the event timers' (amx_profile_get "latbest_potentials", "latbest_arc", "latbest_path", "latbest_min",
+ * "latbest_keep", "latbest_trim", "latbest_scan") */
+int  amx_latbest_last_timing(const amx_latbest* h, double* plan_ms, double* upload_ms);
+
 /* ------------------------------------------------------------------ NN sequence-discriminative training (MMI, ME)
  * Nn::SegmentwiseNnTrainer in full-batch mode (Nn/SegmentwiseNnTrainer.cc:121-250 processWordLattice) for a batch of segments per
  * call, on an amx_nntrain handle whose mask has BASE (and GRADIENT for anything but the base statistics): the handle's weights, its

@@ -34,7 +34,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LatticeAccuracy", "SegmentClustering", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "LatticeBest", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -3087,6 +3087,119 @@ class LatticePosterior:
         out = {k: np.zeros(n_states, np.float64) for k in ("forward", "backward", "generalized_forward", "generalized_backward")}
         _lib.check(self.L.amx_latpost_last_potentials(self.h, n_states, *(_ptr(out[k]) for k in ("forward", "backward", "generalized_forward",
                                                                                                  "generalized_backward"))))
+        return out
+
+
+class LatticeBest:
+    """Best score, best path and forward-backward pruning of word lattices in the tropical semiring, a batch per call, left on the
+    device: Fsa::bestscore, Fsa::best and Fsa::prunePosterior in f32 with the reference's one-ulp tolerant comparison, every chain in the
+    reference's order (include/amx.h, "Lattice best path and forward-backward pruning").  Lattices are LatticePosterior's dicts.
+    threshold None: no pruning (every arc is kept)."""
+
+    INFO = tuple(n for n, _ in _lib.LatbestInfo._fields_)
+    REASONS = {_lib.AMX_LATBEST_OK: "ok", _lib.AMX_LATBEST_NO_FINAL: "no-final"}
+
+    def __init__(self, ctx, threshold=None, relative=True, trim=False, potentials="auto"):
+        self.L = _lib.lib()
+        self.ctx, self.h, self.mode = ctx, None, "best"
+        if potentials not in ("auto", "global"):
+            raise ValueError("LatticeBest: potentials must be 'auto' or 'global', not %r" % (potentials,))
+        cfg = _lib.LatbestCfg()
+        self.L.amx_latbest_cfg_default(C.byref(cfg))
+        if threshold is not None:
+            cfg.threshold = float(threshold)
+        cfg.relative, cfg.trim = int(bool(relative)), int(bool(trim))
+        cfg.potentials = _lib.AMX_LATPOST_POTENTIALS_GLOBAL if potentials == "global" else _lib.AMX_LATPOST_POTENTIALS_AUTO
+        h = C.c_void_p()
+        _lib.check(self.L.amx_latbest_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.amx_latbest_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def kernel_shape():
+        """dict(threads, lds_states, wave_arcs): the potentials kernel's workgroup, the largest segment kept in LDS, the number of arcs
+        from which a wave shares a chain"""
+        t, s, w = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_latbest_kernel_shape(C.byref(t), C.byref(s), C.byref(w))
+        return dict(threads=t.value, lds_states=s.value, wave_arcs=w.value)
+
+    def tables(self, lattices):
+        """the call's CSR tables from a list of lattice dicts (LatticePosterior.tables without risks)"""
+        return LatticePosterior.tables(self, lattices)
+
+    def _args(self, t):
+        return [_ptr(t[k]) for k in ("state_offsets", "arc_offsets", "arc_target", "arc_weight", "initial", "final_flag", "final_weight")]
+
+    def run(self, lattices):
+        """-> dict(best_arc [n_states], path [n_states], keep [n_arcs] (uint8), kept_index [n_arcs]: device tensors over the call, arc
+        numbers counted over the call; info: a list of dicts per lattice; tables).  A refused input raises AmxError."""
+        import torch
+        t = self.tables(lattices)
+        n_states, n_arcs = int(t["state_offsets"][-1]), len(t["arc_target"])
+        dev = torch.device("cuda", self.ctx.device)
+        out = dict(best_arc=torch.empty(max(n_states, 1), dtype=torch.int32, device=dev), path=torch.empty(max(n_states, 1), dtype=torch.int32, device=dev),
+                   keep=torch.empty(max(n_arcs, 1), dtype=torch.uint8, device=dev), kept_index=torch.empty(max(n_arcs, 1), dtype=torch.int32, device=dev))
+        info = self.run_dev(t, out["best_arc"], out["path"], out["keep"], out["kept_index"])
+        out = {k: v[:n_arcs if k in ("keep", "kept_index") else n_states] for k, v in out.items()}
+        out["info"], out["tables"] = info, t
+        return out
+
+    def run_dev(self, t, best_arc_dev, path_dev, keep_dev, kept_index_dev):
+        """the same into buffers of the caller's (t: what tables() returns)"""
+        infos = (_lib.LatbestInfo * max(t["n_seg"], 1))()
+        _lib.check(self.L.amx_latbest_run_dev(self.h, t["n_seg"], *self._args(t), _ptr(best_arc_dev), _ptr(path_dev), _ptr(keep_dev), _ptr(kept_index_dev),
+                                              C.cast(infos, C.c_void_p)))
+        return [{n: getattr(i, n) for n in self.INFO} for i in infos[:t["n_seg"]]]
+
+    def plan(self, lattices):
+        """the host plan alone (no device): dict(discover_index, topo_forward, topo_backward, topo_super, level_forward, level_backward,
+        info) over the call's states"""
+        t = self.tables(lattices)
+        n_states, n_seg = int(t["state_offsets"][-1]), t["n_seg"]
+        names = ("discover_index", "topo_forward", "topo_backward", "topo_super", "level_forward", "level_backward")
+        out = {k: np.zeros(n_seg if k == "topo_super" else n_states, np.int32) for k in names}
+        infos = (_lib.LatbestInfo * max(n_seg, 1))()
+        _lib.check(self.L.amx_latbest_plan_host(self.h, n_seg, *self._args(t), *(_ptr(out[k]) for k in names), C.cast(infos, C.c_void_p)))
+        out["info"] = [{n: getattr(i, n) for n in self.INFO} for i in infos[:n_seg]]
+        out["tables"] = t
+        return out
+
+    @staticmethod
+    def compact(t, keep):
+        """host only: (tables with the kept arcs alone, state ids unchanged; old_to_new [n_arcs], -1: dropped).  t: what tables() returns;
+        keep: one flag per arc (host array).  The result is what LatticePosterior.run_dev takes."""
+        n_states, n_arcs = int(t["state_offsets"][-1]), len(t["arc_target"])
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if len(keep) != n_arcs:
+            raise ValueError("LatticeBest.compact: %d keep flags for %d arcs" % (len(keep), n_arcs))
+        off, tgt, w = np.zeros(n_states + 1, np.int64), np.zeros(max(n_arcs, 1), np.int32), np.zeros(max(n_arcs, 1), np.float32)
+        o2n, nk = np.zeros(max(n_arcs, 1), np.int32), C.c_long()
+        _lib.check(_lib.lib().amx_latbest_compact(t["n_seg"], _ptr(t["state_offsets"]), _ptr(t["arc_offsets"]), _ptr(t["arc_target"]), _ptr(t["arc_weight"]),
+                                                  _ptr(keep), _ptr(off), _ptr(tgt), _ptr(w), _ptr(o2n), C.cast(C.byref(nk), C.c_void_p)))
+        out = dict(t)
+        out.update(arc_offsets=off, arc_target=tgt[:nk.value].copy(), arc_weight=w[:nk.value].copy())
+        return out, o2n[:n_arcs]
+
+    def last_timing(self):
+        """DIAGNOSTIC: (plan ms, upload ms) of the last run"""
+        a, b = C.c_double(), C.c_double()
+        _lib.check(self.L.amx_latbest_last_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_potentials(self, n_states):
+        """DIAGNOSTIC: dict(forward, backward) of the last run, f32 per state over the call"""
+        out = {k: np.zeros(n_states, np.float32) for k in ("forward", "backward")}
+        _lib.check(self.L.amx_latbest_last_potentials(self.h, n_states, _ptr(out["forward"]), _ptr(out["backward"])))
         return out
 
 

@@ -199,6 +199,16 @@ class LatpostInfo(C.Structure):
                                 "undefined_states", "undefined_arcs", "levels_forward", "levels_backward")]
 
 
+class LatbestCfg(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("relative", C.c_int), ("trim", C.c_int), ("potentials", C.c_int)]
+
+
+class LatbestInfo(C.Structure):
+    _fields_ = [("best_score", C.c_float), ("min_weight", C.c_float), ("min_weight_threshold", C.c_float)] + \
+        [(n, C.c_int) for n in ("reason", "path_length", "kept_arcs", "total_arcs", "states_reached", "states_coreached", "levels_forward",
+                                "levels_backward")]
+
+
 class AccuracyCfg(C.Structure):
     _fields_ = [("mode", C.c_int), ("normalization", C.c_float), ("n_labels", C.c_int), ("label_token", C.c_void_p), ("n_tokens", C.c_int),
                 ("short_pause", C.c_void_p)]
@@ -648,6 +658,15 @@ SIGNATURES = {
     "amx_latpost_plan_host": (C.c_int, [_P, C.c_int] + [_P] * 17),
     "amx_latpost_last_potentials": (C.c_int, [_P, C.c_long, _P, _P, _P, _P]),
     "amx_latpost_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "amx_latbest_cfg_default": (None, [C.POINTER(LatbestCfg)]),
+    "amx_latbest_create": (C.c_int, [_P, C.POINTER(LatbestCfg), C.POINTER(_P)]),
+    "amx_latbest_destroy": (None, [_P]),
+    "amx_latbest_kernel_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_latbest_run_dev": (C.c_int, [_P, C.c_int] + [_P] * 12),
+    "amx_latbest_plan_host": (C.c_int, [_P, C.c_int] + [_P] * 14),
+    "amx_latbest_compact": (C.c_int, [C.c_int] + [_P] * 10),
+    "amx_latbest_last_potentials": (C.c_int, [_P, C.c_long, _P, _P]),
+    "amx_latbest_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "amx_nnseq_default_cfg": (None, [C.POINTER(NnSeqCfg)]),
     "amx_nnseq_create": (C.c_int, [_P, C.POINTER(NnSeqCfg), C.POINTER(_P)]),
     "amx_nnseq_destroy": (None, [_P]),
@@ -701,6 +720,7 @@ AMX_EBW_ESTIMATOR_EBW, AMX_EBW_ESTIMATOR_RPROP = 0, 1
 AMX_LATPOST_LOG, AMX_LATPOST_PROB, AMX_LATPOST_EXPECTATION = 0, 1, 2
 AMX_LATPOST_OK, AMX_LATPOST_NO_FINAL = 0, 1
 AMX_LATPOST_POTENTIALS_AUTO, AMX_LATPOST_POTENTIALS_GLOBAL = 0, 1
+AMX_LATBEST_OK, AMX_LATBEST_NO_FINAL = 0, 1
 AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2
 AMX_COMM_ID_BYTES = 128
 
