@@ -2384,6 +2384,83 @@ int  amx_latbest_last_potentials(const amx_latbest* h, long n_states, float* for
  * "latbest_keep", "latbest_trim", "latbest_scan") */
 int  amx_latbest_last_timing(const amx_latbest* h, double* plan_ms, double* upload_ms);
 
+/* ------------------------------------------------------------------ Lattice word measures */
+
+/* The word-level risks and the time-frame word posteriors of word lattices, for a batch of lattices per call, one f32 per arc left on
+ * the device in the input's arc order (usable as arc_risk of AMX_LATPOST_EXPECTATION).  No alignment is needed: the inputs are the CSR
+ * tables of amx_latpost_run_dev, a time per state (frames) and a label per arc.  The label is the word id the ADAPTER has mapped:
+ * Mapping::map (Lattice/TimeframeError.cc:26-65: pronunciation or lemma id, short pauses -> Fsa::Epsilon) for the time-frame and
+ * frame-word modes, label() (Lattice/Accuracy.cc:402-412) for the approximate mode; the library never sees an alphabet.
+ *   AMX_LATWORD_TIMEFRAME_ERROR_SUM / _MAX   Lattice::getSumTimeframeErrors / getMaximumTimeframeErrors (Lattice/TimeframeError.cc:86-289).
+ *       arc_weight_dev holds the arcs' -log posteriors (arc_out_dev of AMX_LATPOST_LOG).  Per (segment, frame t, label) the reference's
+ *       LogCollector (Fsa/tRealSemiring.cc:168-194) runs over the arcs with start <= t < end, fed in discover order of their source states
+ *       (the stack walk of Fsa/tDfs.cc:21-68) and, within a state, in arc order: the first feed is the initial minimum; a later feed a
+ *       stores max(a, minimum so far) (a tie is stored) and lowers the minimum; the result is p = f32(min - log1p(sum)) with
+ *       sum = exp(min - v_1), sum = f32(sum + exp(min - v_i)): min - v_i is an f32 difference, ::exp and ::log1p resolve to the f64
+ *       overloads in that translation unit and `sum +=` adds in f64 and narrows (DESIGN.md has the finding); a single feed gives p = min.
+ *       The cell's score is f32(1 - exp(-(f64)p)).  SUM: an f32 chain of the scores over the arc's frames in time order, divided by
+ *       den = 1 + normalization * f32(u32(end - start - 1)) -- a contraction site of the reference's default build: one fused
+ *       multiply-add under amx_set_contract(AMX_CONTRACT_FMA), two roundings otherwise.  MAX: std::max from f32 min (-f32 max).
+ *       An arc of no duration gives 0 / den and f32 min, as the reference's text does.
+ *       A cell with p <= -0.001 (or NaN) is where the reference verifies: AMX_ERR_INVALID naming segment, frame and label, outputs untouched.
+ *   AMX_LATWORD_FRAME_WORD_ACCURACY   Lattice::getWordTimeframeAccuracy (TimeframeError.cc:294-395): the arcs of the correct lattice mark
+ *       their (frame, label) cells; an arc's value is the number of its frames whose cell is marked (exact in f32) over den.  A frame
+ *       beyond the correct lattice's last frame counts 0 (the reference reads past its vector there).
+ *   AMX_LATWORD_APPROXIMATE_WORD   Lattice::getApproximateWordAccuracy (Lattice/Accuracy.cc:387-473, accuracy() :361-380), the risk of
+ *       minimum word error training: the correct lattice's distinct (label, start, end) with start < end; for an arc whose label is
+ *       not in short_pause_label (the adapter puts Fsa::Epsilon there, as the constructor at :351-359 does) the maximum of
+ *       -1 + (same label ? 2 : 1) * o over the intervals that overlap a frame of the arc, o = f32(min(he, re) - max(hs, rs)) / f32(re - rs);
+ *       0 where none overlaps and for short pauses and arcs of no duration.
+ * In every mode the arcs of states the walk from the initial state does not reach feed nothing and get 0 (info.states_unreached).
+ * Order and determinism as for the arc posteriors: no floating-point atomics, a segment gives the same bits alone and in any batch.
+ * The accuracy modes are f32 divisions, chains and comparisons only.  exp and log1p are the device library's, so the time-frame scores
+ * are close to, not equal to, the host's.
+ * Refused with AMX_ERR_INVALID naming the first offender: what amx_latpost_run_dev refuses in the tables, a time outside [0, 2^30), a
+ * state_time that decreases along an arc, an accuracy mode without the correct lattices or with another number of them.
+ * NOT BUILT: the exact (edit-distance) accuracies, SmoothedAccuracy, the mask, soft and weighted variants, word confidences written
+ * into lattices; a pin of the restatement (tests/latword_reference.py) on the reference's compiled text. */
+enum { AMX_LATWORD_TIMEFRAME_ERROR_SUM = 0, AMX_LATWORD_TIMEFRAME_ERROR_MAX = 1, AMX_LATWORD_FRAME_WORD_ACCURACY = 2, AMX_LATWORD_APPROXIMATE_WORD = 3 };
+typedef struct amx_latword amx_latword;
+typedef struct {
+    int   mode;          /* AMX_LATWORD_TIMEFRAME_ERROR_SUM */
+    float normalization; /* 0; read by SUM and FRAME_WORD_ACCURACY */
+} amx_latword_cfg;
+/* a batch of lattices in host memory: the tables of amx_latpost_run_dev, state_time [n_states], arc_label [n_arcs] */
+typedef struct {
+    int            n_seg;
+    const long*    state_offsets; /* [n_seg + 1] */
+    const long*    arc_offsets;   /* [n_states + 1] */
+    const int32_t* arc_target;
+    const int32_t* initial;       /* [n_seg] */
+    const int32_t* state_time;
+    const int32_t* arc_label;
+} amx_latword_lattices;
+typedef struct {
+    int  states_reached, states_unreached, arcs_reached;
+    int  labels;    /* rows of the table: the distinct labels of the arcs that feed it (FRAME_WORD_ACCURACY: of the correct lattice) */
+    int  frames;    /* the largest end time of a reached arc */
+    int  intervals; /* APPROXIMATE_WORD: distinct intervals of the correct lattice */
+    long feeds;     /* cells fed, each as often as it is fed: the sum of the feeding arcs' durations */
+} amx_latword_info;
+void amx_latword_cfg_default(amx_latword_cfg* cfg);
+/* ctx NULL: a host-only handle (the checks of amx_latword_run_dev run, then AMX_ERR_STATE) */
+int  amx_latword_create(amx_ctx* ctx, const amx_latword_cfg* cfg /* NULL: defaults */, amx_latword** out);
+void amx_latword_destroy(amx_latword* h);
+/* the table kernel's shape (tests pick their sizes around it): frames of a wave's block, the number of a label's feeding arcs from which
+ * its blocks get lists of the arcs that touch them, the duration from which an arc is taken by a wave instead of a lane */
+void amx_latword_kernel_shape(int* block_frames, int* list_arcs, int* wave_arc_frames);
+/* correct: the accuracy modes (one lattice per segment), else ignored; short_pause_label: APPROXIMATE_WORD; arc_weight_dev: the
+ * time-frame modes.  arc_value_dev [n_arcs]; info [n_seg] in host memory, nullable.  Synchronises the stream. */
+int  amx_latword_run_dev(amx_latword* h, const amx_latword_lattices* lat, const amx_latword_lattices* correct, const int32_t* short_pause_label,
+                         int n_short_pause, const float* arc_weight_dev, float* arc_value_dev, amx_latword_info* info);
+/* DIAGNOSTIC (tests): the scores of a (segment, label) of the last time-frame call: the frames [*lo, *hi) its arcs span (both 0: no such
+ * label) and, with score given, the hi - lo cells (0 where no arc covers the frame) */
+int  amx_latword_last_row(const amx_latword* h, int segment, int32_t label, int* lo, int* hi, int capacity, float* score);
+/* DIAGNOSTIC (tools/latword_probe.py): host wall time of the last call's plan and of enqueueing its uploads, in ms; the kernels' times
+ * are the event timers' (amx_profile_get "latword_list", "latword_cells", "latword_prefix", "latword_arcs", "latword_arcs_wave",
+ * "latword_approximate") */
+int  amx_latword_last_timing(const amx_latword* h, double* plan_ms, double* upload_ms);
+
 /* ------------------------------------------------------------------ NN sequence-discriminative training (MMI, ME)
  * Nn::SegmentwiseNnTrainer in full-batch mode (Nn/SegmentwiseNnTrainer.cc:121-250 processWordLattice) for a batch of segments per
  * call, on an amx_nntrain handle whose mask has BASE (and GRADIENT for anything but the base statistics): the handle's weights, its
@@ -2592,7 +2669,7 @@ int  amx_arcalign_last_launches(const amx_arcalign* h);
  *     token is no short pause and is in its frame's set, an exact f32.  For a frame beyond the reference's last frame the reference
  *     reads past its vector; the library gives 0 there.
  * Every value equals the reference's in every bit, alone and in any batch.
- * Not built: getApproximateWordAccuracy (it needs no alignment), the mask, soft and weighted frame-phone variants, the
+ * Not built (getApproximateWordAccuracy is amx_latword_*'s): the mask, soft and weighted frame-phone variants, the
  * forced-alignment constructors (AlignmentToActiveStates), the exact (edit-distance) accuracies, and a device-side arc_risk for
  * amx_latpost_run_dev (copy arc_accuracy_dev to the host with amx_copy_to_host). */
 #define AMX_ACCURACY_APPROXIMATE_PHONE 0

@@ -34,7 +34,7 @@ __all__ = ["Context", "MfccExtractor", "VoicednessExtractor", "GmmFeatureScorer"
            "read_nn_matrix", "write_nn_matrix", "layer_from_parameters", "prior_from_mixture_set", "gmm_estimate",
            "ScatterMatricesEstimator", "read_matrix_f64", "write_matrix_f64", "HistogramEstimator", "HistogramNormalization",
            "BayesClassifier", "ViterbiAligner", "BaumWelchAligner", "LatticeArcAligner", "LatticeAccuracy", "SegmentClustering", "LinearSegmenter", "gather_rows", "StatePosteriorScorer", "CombinedScorer", "QuantileEqualization", "QuantileEstimator", "read_quantiles", "write_quantiles",
-           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "LatticeBest", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
+           "FeedForwardTrainer", "MiniBatchTrainer", "AffineFeatureTransformEstimator", "ModelTransformEstimator", "MixtureSetAdaptor", "EbwAccumulator", "EbwEstimator", "LatticePosterior", "LatticeBest", "LatticeWordMeasures", "SegmentwiseNnTrainer", "AffineFeatureTransform", "write_transform", "read_transform", "combine_nn_statistics", "prior_from_class_counts", "mean_and_deviation",
            "AMX_GMM_VITERBI", "AMX_GMM_BAUM_WELCH"]
 
 
@@ -3201,6 +3201,115 @@ class LatticeBest:
         out = {k: np.zeros(n_states, np.float32) for k in ("forward", "backward")}
         _lib.check(self.L.amx_latbest_last_potentials(self.h, n_states, _ptr(out["forward"]), _ptr(out["backward"])))
         return out
+
+
+class LatticeWordMeasures:
+    """Word-level measures of word lattices' arcs, a batch per call, one f32 per arc left on the device (include/amx.h, "Lattice word
+    measures"): the time-frame word posteriors 1 - p_t(w | x) summed ("timeframe-error-sum") or maximised ("timeframe-error-max") over an
+    arc's frames, the frame-word accuracy ("frame-word-accuracy") and the approximate word accuracy of minimum word error training
+    ("approximate-word").  A lattice is a LatticePosterior dict (the weights and the final tables are not read) with state_time [n]
+    (frames) and arc_label: the word id the caller has mapped already (short pauses to epsilon for the time-frame and frame-word
+    modes).  short_pauses: label ids whose arcs get 0 in "approximate-word" (epsilon among them).  The contract of the denominator is
+    the context's."""
+
+    MODES = {"timeframe-error-sum": _lib.AMX_LATWORD_TIMEFRAME_ERROR_SUM, "timeframe-error-max": _lib.AMX_LATWORD_TIMEFRAME_ERROR_MAX,
+             "frame-word-accuracy": _lib.AMX_LATWORD_FRAME_WORD_ACCURACY, "approximate-word": _lib.AMX_LATWORD_APPROXIMATE_WORD}
+    INFO = tuple(n for n, _ in _lib.LatwordInfo._fields_)
+
+    def __init__(self, ctx, mode="timeframe-error-sum", normalization=0.0, short_pauses=()):
+        self.L = _lib.lib()
+        self.ctx, self.h = ctx, None
+        if mode not in self.MODES:
+            raise ValueError("LatticeWordMeasures: unknown mode %r" % (mode,))
+        cfg = _lib.LatwordCfg()
+        self.L.amx_latword_cfg_default(C.byref(cfg))
+        cfg.mode, cfg.normalization = self.MODES[mode], float(normalization)
+        h = C.c_void_p()
+        _lib.check(self.L.amx_latword_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
+        self.h, self.mode = h, mode
+        self.short_pauses = np.ascontiguousarray(list(short_pauses), dtype=np.int32)
+
+    def close(self):
+        if self.h:
+            self.L.amx_latword_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def kernel_shape():
+        """dict(block_frames, list_arcs, wave_arc_frames): the frames of a wave's block of the table, the number of a label's feeding
+        arcs from which its blocks get lists, the duration from which an arc is taken by a wave"""
+        b, l, w = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_latword_kernel_shape(C.byref(b), C.byref(l), C.byref(w))
+        return dict(block_frames=b.value, list_arcs=l.value, wave_arc_frames=w.value)
+
+    @staticmethod
+    def tables(lattices):
+        """the call's tables from a list of lattice dicts"""
+        so, ao, tgt, ini, tm, lab = [0], [np.zeros(1, np.int64)], [], [], [], []
+        n_arcs = 0
+        for k, lat in enumerate(lattices):
+            off = np.ascontiguousarray(lat["arc_offsets"], dtype=np.int64)
+            n, t = len(off) - 1, np.ascontiguousarray(lat["arc_target"], dtype=np.int32)
+            if n < 0 or off[0] != 0 or off[-1] != len(t) or len(lat["state_time"]) != n or len(lat["arc_label"]) != len(t):
+                raise ValueError("LatticeWordMeasures: lattice %d: %d states, %d targets, %d times, %d labels" %
+                                 (k, n, len(t), len(lat["state_time"]), len(lat["arc_label"])))
+            so.append(so[-1] + n), ao.append(off[1:] + n_arcs)
+            n_arcs += len(t)
+            tgt.append(t), ini.append(int(lat["initial"])), tm.append(np.asarray(lat["state_time"], np.int32)), lab.append(np.asarray(lat["arc_label"], np.int32))
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dt), dtype=dt)   # noqa: E731
+        return dict(n_seg=len(lattices), state_offsets=np.array(so, np.int64), arc_offsets=cat(ao, np.int64), arc_target=cat(tgt, np.int32),
+                    initial=np.array(ini, np.int32), state_time=cat(tm, np.int32), arc_label=cat(lab, np.int32))
+
+    @staticmethod
+    def _struct(t):
+        if t is None:
+            return None
+        s = _lib.LatwordLattices()
+        s.n_seg = t["n_seg"]
+        for k in ("state_offsets", "arc_offsets", "arc_target", "initial", "state_time", "arc_label"):
+            setattr(s, k, _ptr(t[k]))
+        return s
+
+    def run(self, lattices, arc_weight=None, correct=None):
+        """-> (arc values, info): an f32 device tensor, one value per arc in the order of the input (lattice after lattice), usable as
+        arc_risk, and a list of dicts per lattice.  arc_weight: the arcs' -log posteriors (LatticePosterior("log")'s device tensor),
+        time-frame modes only; correct: the correct lattices, accuracy modes only.  A refused input raises AmxError."""
+        import torch
+        t = self.tables(lattices)
+        c = self.tables(correct) if correct is not None else None
+        n_arcs = len(t["arc_target"])
+        out = torch.empty(max(n_arcs, 1), dtype=torch.float32, device=torch.device("cuda", self.ctx.device))
+        info = self.run_dev(t, c, arc_weight, out)
+        return out[:n_arcs], info
+
+    def run_dev(self, t, c, arc_weight_dev, arc_value_dev):
+        """the same into a buffer of the caller's (t, c: what tables() returns; c None without correct lattices)"""
+        infos = (_lib.LatwordInfo * max(t["n_seg"], 1))()
+        st, sc = self._struct(t), self._struct(c)
+        _lib.check(self.L.amx_latword_run_dev(self.h, C.byref(st), C.byref(sc) if sc is not None else None, _ptr(self.short_pauses), len(self.short_pauses),
+                                              _ptr(arc_weight_dev), _ptr(arc_value_dev), C.cast(infos, C.c_void_p)))
+        return [{n: getattr(i, n) for n in self.INFO} for i in infos[:t["n_seg"]]]
+
+    def last_row(self, segment, label):
+        """DIAGNOSTIC: (lo, scores [hi - lo]) of a (segment, label) of the last time-frame call; (0, empty) for a label that feeds nothing"""
+        lo, hi = C.c_int(), C.c_int()
+        _lib.check(self.L.amx_latword_last_row(self.h, segment, label, C.byref(lo), C.byref(hi), 0, None))
+        out = np.zeros(hi.value - lo.value, np.float32)
+        if len(out):
+            _lib.check(self.L.amx_latword_last_row(self.h, segment, label, C.byref(lo), C.byref(hi), len(out), _ptr(out)))
+        return lo.value, out
+
+    def last_timing(self):
+        """DIAGNOSTIC: (plan ms, upload ms) of the last run"""
+        a, b = C.c_double(), C.c_double()
+        _lib.check(self.L.amx_latword_last_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 class SegmentwiseNnTrainer:

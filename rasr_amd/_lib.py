@@ -209,6 +209,18 @@ class LatbestInfo(C.Structure):
                                 "levels_backward")]
 
 
+class LatwordCfg(C.Structure):
+    _fields_ = [("mode", C.c_int), ("normalization", C.c_float)]
+
+
+class LatwordLattices(C.Structure):
+    _fields_ = [("n_seg", C.c_int)] + [(n, C.c_void_p) for n in ("state_offsets", "arc_offsets", "arc_target", "initial", "state_time", "arc_label")]
+
+
+class LatwordInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("states_reached", "states_unreached", "arcs_reached", "labels", "frames", "intervals")] + [("feeds", C.c_long)]
+
+
 class AccuracyCfg(C.Structure):
     _fields_ = [("mode", C.c_int), ("normalization", C.c_float), ("n_labels", C.c_int), ("label_token", C.c_void_p), ("n_tokens", C.c_int),
                 ("short_pause", C.c_void_p)]
@@ -667,6 +679,13 @@ SIGNATURES = {
     "amx_latbest_compact": (C.c_int, [C.c_int] + [_P] * 10),
     "amx_latbest_last_potentials": (C.c_int, [_P, C.c_long, _P, _P]),
     "amx_latbest_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "amx_latword_cfg_default": (None, [C.POINTER(LatwordCfg)]),
+    "amx_latword_create": (C.c_int, [_P, C.POINTER(LatwordCfg), C.POINTER(_P)]),
+    "amx_latword_destroy": (None, [_P]),
+    "amx_latword_kernel_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "amx_latword_run_dev": (C.c_int, [_P, C.POINTER(LatwordLattices), C.POINTER(LatwordLattices), _P, C.c_int, _P, _P, _P]),
+    "amx_latword_last_row": (C.c_int, [_P, C.c_int, C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P]),
+    "amx_latword_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "amx_nnseq_default_cfg": (None, [C.POINTER(NnSeqCfg)]),
     "amx_nnseq_create": (C.c_int, [_P, C.POINTER(NnSeqCfg), C.POINTER(_P)]),
     "amx_nnseq_destroy": (None, [_P]),
@@ -721,6 +740,7 @@ AMX_LATPOST_LOG, AMX_LATPOST_PROB, AMX_LATPOST_EXPECTATION = 0, 1, 2
 AMX_LATPOST_OK, AMX_LATPOST_NO_FINAL = 0, 1
 AMX_LATPOST_POTENTIALS_AUTO, AMX_LATPOST_POTENTIALS_GLOBAL = 0, 1
 AMX_LATBEST_OK, AMX_LATBEST_NO_FINAL = 0, 1
+AMX_LATWORD_TIMEFRAME_ERROR_SUM, AMX_LATWORD_TIMEFRAME_ERROR_MAX, AMX_LATWORD_FRAME_WORD_ACCURACY, AMX_LATWORD_APPROXIMATE_WORD = 0, 1, 2, 3
 AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2
 AMX_COMM_ID_BYTES = 128
 
