@@ -2242,6 +2242,7 @@ int  amx_ebw_accumulator_combine(const amx_gmm_model* topology, double* acc, con
 enum { AMX_LATPOST_LOG = 0, AMX_LATPOST_PROB = 1, AMX_LATPOST_EXPECTATION = 2 };
 enum { AMX_LATPOST_OK = 0, AMX_LATPOST_NO_FINAL = 1 };
 enum { AMX_LATPOST_POTENTIALS_AUTO = 0, AMX_LATPOST_POTENTIALS_GLOBAL = 1 };
+enum { AMX_LATPOST_PLAN_HOST = 0, AMX_LATPOST_PLAN_DEVICE = 1 };
 typedef struct amx_latpost amx_latpost;
 typedef struct {
     int mode;         /* AMX_LATPOST_LOG */
@@ -2250,6 +2251,10 @@ typedef struct {
     int tolerance;    /* 100: posterior-tolerance of the flow comparison */
     int potentials;   /* AMX_LATPOST_POTENTIALS_AUTO: in LDS while a segment's states fit (amx_latpost_kernel_shape); _GLOBAL: always in
                          global memory (tests: both paths give the same bits) */
+    int plan;         /* AMX_LATPOST_PLAN_HOST: one host thread checks and plans the call, lattice after lattice; _DEVICE: the CSR tables
+                         are uploaded raw and the plan is built on the device, a workgroup per lattice (latplan.hip).  The two kernels
+                         read the same chains in the same order: every output bit is the same.  A refused input is refused by the host
+                         plan, with its status and text */
 } amx_latpost_cfg;
 typedef struct {
     double total_inv;     /* -bw[initial] (Posterior64Automaton::totalInv) */
@@ -2288,12 +2293,24 @@ int  amx_latpost_plan_host(const amx_latpost* h, int n_seg, const long* state_of
                            const float* final_weight, const float* final_risk, int32_t* discover_index, int32_t* level_backward,
                            int32_t* level_forward, int32_t* level_super, long* in_offsets, int32_t* in_arc, int32_t* final_order,
                            amx_latpost_info* info);
+/* The same outputs from the device plan (whatever cfg.plan says), copied back to host memory: equal to the host plan's in every integer.
+ * A handle without a context: AMX_ERR_STATE after the checks. */
+int  amx_latpost_plan_dev(amx_latpost* h, int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target,
+                          const float* arc_weight, const float* arc_risk, const int32_t* initial, const uint8_t* final_flag,
+                          const float* final_weight, const float* final_risk, int32_t* discover_index, int32_t* level_backward,
+                          int32_t* level_forward, int32_t* level_super, long* in_offsets, int32_t* in_arc, int32_t* final_order,
+                          amx_latpost_info* info);
+/* the plan kernel's switch points (tests pick their sizes around them): threads of a workgroup, the largest number of states of a segment
+ * whose per-state work arrays live in LDS, and the largest stack (the segment's arcs + 1) that lives in LDS */
+void amx_latpost_plan_shape(int* threads, int* lds_states, int* lds_stack);
 /* DIAGNOSTIC (tests, probes): the potentials of the last amx_latpost_run_dev, per state counted over the call; generalized_*: EXPECTATION
  * (else zeros).  Every array nullable. */
 int  amx_latpost_last_potentials(const amx_latpost* h, long n_states, double* forward, double* backward, double* generalized_forward,
                                  double* generalized_backward);
 /* DIAGNOSTIC (tools/latpost_probe.py): host wall time of the last amx_latpost_run_dev's plan and of packing and uploading its tables, in ms;
- * the kernels' times are the event timers' (amx_profile_get "latpost_potentials", "latpost_arcs") */
+ * the kernels' times are the event timers' (amx_profile_get "latpost_potentials", "latpost_arcs").  With the device plan: plan_ms is the
+ * host wall time from the plan kernel's launch until its status has been read back, upload_ms that of the raw uploads; the plan kernel's
+ * own time is amx_profile_get "latpost_plan" */
 int  amx_latpost_last_timing(const amx_latpost* h, double* plan_ms, double* upload_ms);
 
 /* ------------------------------------------------------------------ Lattice best path and forward-backward pruning */

@@ -2969,22 +2969,27 @@ class LatticePosterior:
     Fsa::expm ("prob") and Fsa::posteriorE over an accuracy lattice ("expectation"), in f64 in the log semiring, every sum in the
     reference's order.  A lattice is a dict of host arrays: arc_offsets [n + 1] (state s owns the arcs [arc_offsets[s], arc_offsets[s + 1])
     in the automaton's own order), arc_target (state ids of this lattice), arc_weight, initial, final_flag [n], final_weight [n] and, for
-    "expectation", arc_risk and final_risk.  The contract (the one fused multiply-add of the expectation pass) is the context's."""
+    "expectation", arc_risk and final_risk.  The contract (the one fused multiply-add of the expectation pass) is the context's.
+    plan "host": one host thread checks and plans a call; "device": the tables go up raw and a workgroup per lattice plans them
+    (every output bit is the same; a refused input is refused in the host plan's words)."""
 
     MODES = {"log": _lib.AMX_LATPOST_LOG, "prob": _lib.AMX_LATPOST_PROB, "expectation": _lib.AMX_LATPOST_EXPECTATION}
     INFO = tuple(n for n, _ in _lib.LatpostInfo._fields_)
 
-    def __init__(self, ctx, mode="log", normalize=True, v_normalized=True, tolerance=100, potentials="auto"):
+    def __init__(self, ctx, mode="log", normalize=True, v_normalized=True, tolerance=100, potentials="auto", plan="host"):
         self.L = _lib.lib()
         self.ctx, self.h = ctx, None
         if mode not in self.MODES:
             raise ValueError("LatticePosterior: unknown mode %r" % (mode,))
+        if plan not in ("host", "device"):
+            raise ValueError("LatticePosterior: plan must be 'host' or 'device', not %r" % (plan,))
         if potentials not in ("auto", "global"):
             raise ValueError("LatticePosterior: potentials must be 'auto' or 'global', not %r" % (potentials,))
         cfg = _lib.LatpostCfg()
         self.L.amx_latpost_cfg_default(C.byref(cfg))
         cfg.mode, cfg.normalize, cfg.v_normalized, cfg.tolerance = self.MODES[mode], int(bool(normalize)), int(bool(v_normalized)), int(tolerance)
         cfg.potentials = _lib.AMX_LATPOST_POTENTIALS_GLOBAL if potentials == "global" else _lib.AMX_LATPOST_POTENTIALS_AUTO
+        cfg.plan = _lib.AMX_LATPOST_PLAN_DEVICE if plan == "device" else _lib.AMX_LATPOST_PLAN_HOST
         h = C.c_void_p()
         _lib.check(self.L.amx_latpost_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(h)))
         self.h, self.mode = h, mode
@@ -3007,6 +3012,14 @@ class LatticePosterior:
         t, s, w = C.c_int(), C.c_int(), C.c_int()
         _lib.lib().amx_latpost_kernel_shape(C.byref(t), C.byref(s), C.byref(w))
         return dict(threads=t.value, lds_states=s.value, wave_arcs=w.value)
+
+    @staticmethod
+    def plan_shape():
+        """dict(threads, lds_states, lds_stack): the plan kernel's workgroup, the largest segment (states) whose work arrays live in LDS,
+        the largest stack (arcs + 1) that lives in LDS"""
+        t, s, k = C.c_int(), C.c_int(), C.c_int()
+        _lib.lib().amx_latpost_plan_shape(C.byref(t), C.byref(s), C.byref(k))
+        return dict(threads=t.value, lds_states=s.value, lds_stack=k.value)
 
     def tables(self, lattices):
         """the call's CSR tables from a list of lattice dicts"""
@@ -3059,7 +3072,7 @@ class LatticePosterior:
                                               _ptr(arc_out_dev), _ptr(final_out_dev), C.cast(infos, C.c_void_p)))
         return self._info(infos[:t["n_seg"]])
 
-    def plan(self, lattices):
+    def plan(self, lattices, _fn="amx_latpost_plan_host"):
         """the host plan alone (no device): dict(discover_index, level_backward, level_forward, level_super, in_offsets, in_arc, final_order,
         info) over the call's states and arcs"""
         t = self.tables(lattices)
@@ -3068,13 +3081,17 @@ class LatticePosterior:
                    level_super=np.zeros(n_seg, np.int32), in_offsets=np.zeros(n_states + 1, np.int64), in_arc=np.full(n_arcs, -1, np.int32),
                    final_order=np.zeros(n_states, np.int32))
         infos = (_lib.LatpostInfo * max(n_seg, 1))()
-        _lib.check(self.L.amx_latpost_plan_host(self.h, n_seg, _ptr(t["state_offsets"]), _ptr(t["arc_offsets"]), _ptr(t["arc_target"]), _ptr(t["arc_weight"]),
+        _lib.check(getattr(self.L, _fn)(self.h, n_seg, _ptr(t["state_offsets"]), _ptr(t["arc_offsets"]), _ptr(t["arc_target"]), _ptr(t["arc_weight"]),
                                                 _ptr(t["arc_risk"]), _ptr(t["initial"]), _ptr(t["final_flag"]), _ptr(t["final_weight"]), _ptr(t["final_risk"]),
                                                 *(_ptr(out[k]) for k in ("discover_index", "level_backward", "level_forward", "level_super", "in_offsets",
                                                                          "in_arc", "final_order")), C.cast(infos, C.c_void_p)))
         out["info"] = self._info(infos[:n_seg])
         out["tables"] = t
         return out
+
+    def plan_dev(self, lattices):
+        """the same dict from the device plan (whatever `plan` the handle was created with), copied back"""
+        return self.plan(lattices, "amx_latpost_plan_dev")
 
     def last_timing(self):
         """DIAGNOSTIC: (plan ms, upload ms) of the last run: host wall time of the plan and of packing and uploading the tables"""

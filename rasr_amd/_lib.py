@@ -189,7 +189,7 @@ class EbwCallShape(C.Structure):
 
 
 class LatpostCfg(C.Structure):
-    _fields_ = [("mode", C.c_int), ("normalize", C.c_int), ("v_normalized", C.c_int), ("tolerance", C.c_int), ("potentials", C.c_int)]
+    _fields_ = [("mode", C.c_int), ("normalize", C.c_int), ("v_normalized", C.c_int), ("tolerance", C.c_int), ("potentials", C.c_int), ("plan", C.c_int)]
 
 
 class LatpostInfo(C.Structure):
@@ -668,6 +668,8 @@ SIGNATURES = {
     "amx_latpost_kernel_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "amx_latpost_run_dev": (C.c_int, [_P, C.c_int] + [_P] * 12),
     "amx_latpost_plan_host": (C.c_int, [_P, C.c_int] + [_P] * 17),
+    "amx_latpost_plan_dev": (C.c_int, [_P, C.c_int] + [_P] * 17),
+    "amx_latpost_plan_shape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "amx_latpost_last_potentials": (C.c_int, [_P, C.c_long, _P, _P, _P, _P]),
     "amx_latpost_last_timing": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "amx_latbest_cfg_default": (None, [C.POINTER(LatbestCfg)]),
@@ -739,6 +741,7 @@ AMX_EBW_ESTIMATOR_EBW, AMX_EBW_ESTIMATOR_RPROP = 0, 1
 AMX_LATPOST_LOG, AMX_LATPOST_PROB, AMX_LATPOST_EXPECTATION = 0, 1, 2
 AMX_LATPOST_OK, AMX_LATPOST_NO_FINAL = 0, 1
 AMX_LATPOST_POTENTIALS_AUTO, AMX_LATPOST_POTENTIALS_GLOBAL = 0, 1
+AMX_LATPOST_PLAN_HOST, AMX_LATPOST_PLAN_DEVICE = 0, 1
 AMX_LATBEST_OK, AMX_LATBEST_NO_FINAL = 0, 1
 AMX_LATWORD_TIMEFRAME_ERROR_SUM, AMX_LATWORD_TIMEFRAME_ERROR_MAX, AMX_LATWORD_FRAME_WORD_ACCURACY, AMX_LATWORD_APPROXIMATE_WORD = 0, 1, 2, 3
 AMX_MLLR_ROOT_FALLBACK, AMX_MLLR_SILENCE_FALLBACK = 1, 2

@@ -20,20 +20,6 @@ constexpr int    kLatThreads   = 256;
 constexpr int    kLatLdsStates = 4096;   // x 8 bytes (x 2 with the generalized potentials): 32 / 64 KB of LDS
 constexpr double kLatZero      = DBL_MAX;   // Fsa/Sssp.cc:67
 
-struct LatArgs {
-    const LatWalk* walk;
-    const LatSeg*  seg;
-    const int32_t *node_arcs, *node_final, *warc_target, *order, *levels, *arc_source, *arc_target, *state_seg;
-    const float *  node_fw, *node_fr, *warc_weight, *warc_risk, *arc_weight, *arc_risk, *final_weight, *final_risk;
-    const uint8_t* final_flag;
-    const long*    arc_offsets;
-    double *       pot, *gen;   // [n_nodes] each
-    double*        ends;        // [3 x n_seg]: bw[initial], fw[new initial], gbw[initial]
-    float *        arc_out, *final_out;
-    long           n_arcs, n_states;
-    int            n_seg, mode, normalize, v_normalized, force_global;
-};
-
 __device__ __forceinline__ double lat_score(double potential, float w) {
     double s = potential + (double)w;
     return isinf(s) ? DBL_MAX : s;
@@ -305,6 +291,7 @@ struct amx_latpost {
     long                      last_nodes = 0, last_states = 0;
     int                       last_mode  = 0;
     double                    last_plan_ms = 0, last_upload_ms = 0;   // host wall time of the last call's plan and of its uploads
+    amx::LatDevPlan           dev;   // cfg.plan = device and amx_latpost_plan_dev: the tables latplan.hip builds
 };
 
 namespace amx {
@@ -312,6 +299,52 @@ const amx_latpost_cfg& latpost_cfg_of(const amx_latpost* h) {
     return h->cfg;
 }
 }  // namespace amx
+
+// the two kernels over the tables of a plan (the host's or the device's) and the read-back of the segments' ends; counts: info's discrete fields
+static int latpost_launch(amx_latpost* h, amx::LatArgs& a, size_t nN, float* arc_out_dev, float* final_out_dev, const amx_latpost_info* counts,
+                          amx_latpost_info* info) {
+    amx_ctx*   ctx   = h->ctx;
+    const bool e     = h->cfg.mode == AMX_LATPOST_EXPECTATION;
+    const int  n_seg = a.n_seg;
+    AMX_TRY(h->d_pot.reserve(2 * nN + 3 * (size_t)n_seg));
+    a.pot = h->d_pot.get(), a.gen = h->d_pot.get() + nN, a.ends = h->d_pot.get() + 2 * nN;
+    a.arc_out = arc_out_dev, a.final_out = final_out_dev;
+    a.mode = h->cfg.mode, a.normalize = h->cfg.normalize ? 1 : 0, a.v_normalized = h->cfg.v_normalized ? 1 : 0;
+    a.force_global = h->cfg.potentials == AMX_LATPOST_POTENTIALS_GLOBAL;
+    if (!e)
+        AMX_HIP(hipMemsetAsync(a.gen, 0, nN * sizeof(double), ctx->stream));
+    {
+        amx::ScopedKernelTimer timer(ctx, "latpost_potentials");
+        const dim3             grid(2 * (unsigned)n_seg), block(amx::kLatThreads);
+        if (!e)
+            hipLaunchKernelGGL((amx::latpost_potentials_kernel<false, false>), grid, block, 0, ctx->stream, a);
+        else if (ctx->contract == AMX_CONTRACT_FMA)
+            hipLaunchKernelGGL((amx::latpost_potentials_kernel<true, true>), grid, block, 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((amx::latpost_potentials_kernel<true, false>), grid, block, 0, ctx->stream, a);
+        AMX_HIP(hipGetLastError());
+    }
+    {
+        amx::ScopedKernelTimer timer(ctx, "latpost_arcs");
+        long                   most = a.n_arcs > a.n_states ? a.n_arcs : a.n_states;
+        if (most < n_seg)
+            most = n_seg;
+        hipLaunchKernelGGL(amx::latpost_arcs_kernel, dim3((unsigned)amx::ceil_div(most, 256)), dim3(256), 0, ctx->stream, a);
+        AMX_HIP(hipGetLastError());
+    }
+    std::vector<double> ends(3 * (size_t)n_seg);
+    AMX_HIP(hipMemcpyAsync(ends.data(), a.ends, ends.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    AMX_HIP(hipStreamSynchronize(ctx->stream));
+    if (info)
+        for (int g = 0; g < n_seg; ++g) {
+            info[g] = counts[g];
+            amx::latpost_fill_info(h->cfg, ends[3 * (size_t)g], ends[3 * (size_t)g + 1], ends[3 * (size_t)g + 2], &info[g]);
+        }
+    h->last_nodes  = (long)nN;
+    h->last_states = a.n_states;
+    h->last_mode   = h->cfg.mode;
+    return AMX_OK;
+}
 
 extern "C" {
 
@@ -328,6 +361,7 @@ int amx_latpost_create(amx_ctx* ctx, const amx_latpost_cfg* cfg, amx_latpost** o
     AMX_REQUIRE(c.tolerance > 0 && c.tolerance < 0x400000, AMX_ERR_INVALID, "%s: tolerance %d must lie in (0, 2^22)", who, c.tolerance);
     AMX_REQUIRE(c.potentials == AMX_LATPOST_POTENTIALS_AUTO || c.potentials == AMX_LATPOST_POTENTIALS_GLOBAL, AMX_ERR_INVALID, "%s: potentials %d", who,
                 c.potentials);
+    AMX_REQUIRE(c.plan == AMX_LATPOST_PLAN_HOST || c.plan == AMX_LATPOST_PLAN_DEVICE, AMX_ERR_INVALID, "%s: plan %d", who, c.plan);
     std::unique_ptr<amx_latpost> h(new amx_latpost);
     h->ctx = ctx;
     h->cfg = c;
@@ -357,6 +391,20 @@ int amx_latpost_run_dev(amx_latpost* h, int n_seg, const long* state_offsets, co
                         float* arc_out_dev, float* final_out_dev, amx_latpost_info* info) {
     const char* who = "amx_latpost_run_dev";
     AMX_REQUIRE(h, AMX_ERR_INVALID, "%s: NULL handle", who);
+    if (h->cfg.plan == AMX_LATPOST_PLAN_DEVICE && n_seg > 0 && h->ctx) {
+        // the plan on the device: the raw tables go up, latplan.hip builds what the two kernels read
+        amx::LatArgs a{};
+        AMX_TRY(amx::latplan_run(h->ctx, h->cfg.mode, n_seg, state_offsets, arc_offsets, arc_target, arc_weight, arc_risk, initial, final_flag, final_weight,
+                                 final_risk, who, &h->dev, &a));
+        AMX_REQUIRE(final_out_dev && (a.n_arcs == 0 || arc_out_dev), AMX_ERR_INVALID, "%s: NULL arc_out_dev or final_out_dev", who);
+        h->last_seg.clear();
+        h->last_plan_ms = h->dev.plan_ms, h->last_upload_ms = h->dev.upload_ms;
+        std::vector<amx_latpost_info> counts((size_t)n_seg, amx_latpost_info{});
+        amx::latplan_info(h->dev, counts.data());
+        AMX_TRY(latpost_launch(h, a, (size_t)h->dev.n_nodes, arc_out_dev, final_out_dev, counts.data(), info));
+        h->last_seg = h->dev.h_seg;
+        return AMX_OK;
+    }
     amx::LatPlan p;
     const auto   t0 = std::chrono::steady_clock::now();
     AMX_TRY(amx::latpost_plan(h->cfg.mode, n_seg, state_offsets, arc_offsets, arc_target, arc_weight, arc_risk, initial, final_flag, final_weight, final_risk,
@@ -400,7 +448,6 @@ int amx_latpost_run_dev(amx_latpost* h, int n_seg, const long* state_offsets, co
     AMX_TRY(h->d_final_flag.reserve(nS));
     AMX_TRY(h->d_walk.reserve(p.walk.size()));
     AMX_TRY(h->d_seg.reserve(p.seg.size()));
-    AMX_TRY(h->d_pot.reserve(2 * nN + 3 * (size_t)n_seg));
     AMX_HIP(hipMemcpyAsync(h->d_ints.get(), ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     AMX_HIP(hipMemcpyAsync(h->d_floats.get(), floats.data(), floats.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     AMX_HIP(hipMemcpyAsync(h->d_arc_offsets.get(), arc_offsets, (nS + 1) * sizeof(long), hipMemcpyHostToDevice, ctx->stream));
@@ -421,45 +468,31 @@ int amx_latpost_run_dev(amx_latpost* h, int n_seg, const long* state_offsets, co
     a.node_fw = df + f_fw, a.node_fr = df + f_fr, a.warc_weight = df + f_ww, a.warc_risk = df + f_wr, a.arc_weight = df + f_aw, a.arc_risk = df + f_ar;
     a.final_weight = df + f_fiw, a.final_risk = df + f_fir;
     a.final_flag = h->d_final_flag.get(), a.arc_offsets = h->d_arc_offsets.get();
-    a.pot = h->d_pot.get(), a.gen = h->d_pot.get() + nN, a.ends = h->d_pot.get() + 2 * nN;
-    a.arc_out = arc_out_dev, a.final_out = final_out_dev;
     a.n_arcs = p.n_arcs, a.n_states = p.n_states, a.n_seg = n_seg;
-    a.mode = h->cfg.mode, a.normalize = h->cfg.normalize ? 1 : 0, a.v_normalized = h->cfg.v_normalized ? 1 : 0;
-    a.force_global = h->cfg.potentials == AMX_LATPOST_POTENTIALS_GLOBAL;
-    if (!e)
-        AMX_HIP(hipMemsetAsync(a.gen, 0, nN * sizeof(double), ctx->stream));
-    {
-        amx::ScopedKernelTimer timer(ctx, "latpost_potentials");
-        const dim3             grid(2 * (unsigned)n_seg), block(amx::kLatThreads);
-        if (!e)
-            hipLaunchKernelGGL((amx::latpost_potentials_kernel<false, false>), grid, block, 0, ctx->stream, a);
-        else if (ctx->contract == AMX_CONTRACT_FMA)
-            hipLaunchKernelGGL((amx::latpost_potentials_kernel<true, true>), grid, block, 0, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((amx::latpost_potentials_kernel<true, false>), grid, block, 0, ctx->stream, a);
-        AMX_HIP(hipGetLastError());
-    }
-    {
-        amx::ScopedKernelTimer timer(ctx, "latpost_arcs");
-        long                   most = p.n_arcs > p.n_states ? p.n_arcs : p.n_states;
-        if (most < n_seg)
-            most = n_seg;
-        hipLaunchKernelGGL(amx::latpost_arcs_kernel, dim3((unsigned)amx::ceil_div(most, 256)), dim3(256), 0, ctx->stream, a);
-        AMX_HIP(hipGetLastError());
-    }
-    std::vector<double> ends(3 * (size_t)n_seg);
-    AMX_HIP(hipMemcpyAsync(ends.data(), a.ends, ends.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    AMX_HIP(hipStreamSynchronize(ctx->stream));
-    if (info)
-        for (int g = 0; g < n_seg; ++g) {
-            info[g] = p.info[(size_t)g];
-            amx::latpost_fill_info(h->cfg, ends[3 * (size_t)g], ends[3 * (size_t)g + 1], ends[3 * (size_t)g + 2], &info[g]);
-        }
-    h->last_seg    = std::move(p.seg);
-    h->last_nodes  = p.n_nodes;
-    h->last_states = p.n_states;
-    h->last_mode   = h->cfg.mode;
+    AMX_TRY(latpost_launch(h, a, nN, arc_out_dev, final_out_dev, p.info.data(), info));
+    h->last_seg = std::move(p.seg);
     return AMX_OK;
+}
+
+int amx_latpost_plan_dev(amx_latpost* h, int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target, const float* arc_weight,
+                         const float* arc_risk, const int32_t* initial, const uint8_t* final_flag, const float* final_weight, const float* final_risk,
+                         int32_t* discover_index, int32_t* level_backward, int32_t* level_forward, int32_t* level_super, long* in_offsets, int32_t* in_arc,
+                         int32_t* final_order, amx_latpost_info* info) {
+    const char* who = "amx_latpost_plan_dev";
+    AMX_REQUIRE(h, AMX_ERR_INVALID, "%s: NULL handle", who);
+    if (n_seg <= 0 || !h->ctx) {   // nothing for the device to do: the checks are the host plan's
+        amx::LatPlan p;
+        AMX_TRY(amx::latpost_plan(h->cfg.mode, n_seg, state_offsets, arc_offsets, arc_target, arc_weight, arc_risk, initial, final_flag, final_weight,
+                                  final_risk, who, &p));
+        AMX_REQUIRE(h->ctx, AMX_ERR_STATE, "%s: the handle was created without a context", who);
+        if (in_offsets)
+            in_offsets[0] = 0;
+        return AMX_OK;
+    }
+    AMX_TRY(amx::latplan_run(h->ctx, h->cfg.mode, n_seg, state_offsets, arc_offsets, arc_target, arc_weight, arc_risk, initial, final_flag, final_weight,
+                             final_risk, who, &h->dev, nullptr));
+    return amx::latplan_download(h->ctx, h->dev, state_offsets, arc_offsets, discover_index, level_backward, level_forward, level_super, in_offsets, in_arc,
+                                 final_order, info);
 }
 
 int amx_latpost_last_timing(const amx_latpost* h, double* plan_ms, double* upload_ms) {

@@ -319,6 +319,7 @@ void amx_latpost_cfg_default(amx_latpost_cfg* cfg) {
     cfg->v_normalized = 1;     // posteriorE's vNormalized
     cfg->tolerance    = 100;   // posterior-tolerance
     cfg->potentials   = AMX_LATPOST_POTENTIALS_AUTO;
+    cfg->plan         = AMX_LATPOST_PLAN_HOST;
 }
 
 int amx_latpost_plan_host(const amx_latpost* h, int n_seg, const long* state_offsets, const long* arc_offsets, const int32_t* arc_target,

@@ -7,8 +7,10 @@ about 2 000 states and 8 000 arcs each, in the three modes.
                                                    profiles/latpost_probe.jsonl
     python3 tools/latpost_probe.py --step NAME     one step; prints one JSON line
 
-Per call (median of --reps after a warm-up call): the wall time with the stream drained; the host's plan and its packing and upload of the
-tables (the library's own stop watch, amx_latpost_last_timing); the two kernels from the library's event timers."""
+Per call (smallest / median / largest of --reps after a warm-up call): the wall time with the stream drained; the plan and the packing and
+upload of the tables (the library's own stop watch, amx_latpost_last_timing); the kernels from the library's event timers.  --plan both
+(the default) alternates a handle with the host plan and one with the device plan call by call in ONE process, so that the two rows of a
+step have seen the same machine; each row is one JSON line."""
 import argparse
 import json
 import os
@@ -22,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = ("log", "prob", "expectation")
-KERNELS = ("latpost_potentials", "latpost_arcs")
+KERNELS = ("latpost_plan", "latpost_potentials", "latpost_arcs")
 
 
 def step(a):
@@ -34,37 +36,43 @@ def step(a):
     ctx.use_torch_stream()
     ctx.set_contract(a.contract)
     lats = [lr.random_dag(a.states, a.arcs, 900 + k, n_final=3) for k in range(a.segments)]
-    lp = rasr_amd.LatticePosterior(ctx, a.step)
-    t = lp.tables(lats)
+    plans = ("host", "device") if a.plan == "both" else (a.plan,)
+    lps = {pl: rasr_amd.LatticePosterior(ctx, a.step, plan=pl) for pl in plans}
+    t = lps[plans[0]].tables(lats)
     n_states, n_arcs = int(t["state_offsets"][-1]), len(t["arc_target"])
     arc_out = torch.empty(n_arcs, dtype=torch.float32, device="cuda")
     final_out = torch.empty(n_states, dtype=torch.float32, device="cuda")
-    info = lp.run_dev(t, arc_out, final_out)
+    for lp in lps.values():
+        info = lp.run_dev(t, arc_out, final_out)
     torch.cuda.synchronize()
-    wall, plan, upload = [], [], []
+    wall, plan, upload = ({pl: [] for pl in plans} for _ in range(3))
     for _ in range(a.reps):
-        t0 = time.perf_counter()
-        lp.run_dev(t, arc_out, final_out)
-        torch.cuda.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3)
-        p, u = lp.last_timing()
-        plan.append(p), upload.append(u)
+        for pl, lp in lps.items():
+            t0 = time.perf_counter()
+            lp.run_dev(t, arc_out, final_out)
+            torch.cuda.synchronize()
+            wall[pl].append((time.perf_counter() - t0) * 1e3)
+            p, u = lp.last_timing()
+            plan[pl].append(p), upload[pl].append(u)
     ctx.profile(True)
-    got = {n: [] for n in KERNELS}
+    got = {pl: {n: [] for n in KERNELS} for pl in plans}
     for _ in range(a.reps):
-        ctx.profile_reset()
-        lp.run_dev(t, arc_out, final_out)
-        torch.cuda.synchronize()
-        for n in KERNELS:
-            got[n].append(ctx.profile_get(n)[0])
+        for pl, lp in lps.items():
+            ctx.profile_reset()
+            lp.run_dev(t, arc_out, final_out)
+            torch.cuda.synchronize()
+            for n in KERNELS:
+                got[pl][n].append(ctx.profile_get(n)[0])
     ctx.profile(False)
-    med = lambda v: round(float(np.median(v)), 4)   # noqa: E731
-    res = dict(step=a.step, contract=a.contract, reps=a.reps, segments=a.segments, states=n_states, arcs=n_arcs,
-               levels_backward_max=max(i["levels_backward"] for i in info), levels_forward_max=max(i["levels_forward"] for i in info),
-               call_ms=med(wall), plan_ms=med(plan), upload_ms=med(upload), kernel_ms={n: med(v) for n, v in got.items()},
-               flows_agree=int(sum(i["flows_agree"] for i in info)))
-    print(json.dumps(res))
-    lp.close()
+    mmm = lambda v: [round(float(f(v)), 4) for f in (np.min, np.median, np.max)]   # noqa: E731
+    for pl, lp in lps.items():
+        res = dict(step=a.step, plan=pl, contract=a.contract, reps=a.reps, segments=a.segments, states=n_states, arcs=n_arcs,
+                   levels_backward_max=max(i["levels_backward"] for i in info), levels_forward_max=max(i["levels_forward"] for i in info),
+                   min_median_max=dict(call_ms=mmm(wall[pl]), plan_ms=mmm(plan[pl]), upload_ms=mmm(upload[pl]),
+                                       kernel_ms={n: mmm(v) for n, v in got[pl].items()}),
+                   flows_agree=int(sum(i["flows_agree"] for i in info)))
+        print(json.dumps(res))
+        lp.close()
     ctx.close()
 
 
@@ -75,7 +83,8 @@ def main():
     ap.add_argument("--states", type=int, default=2000, help="per lattice")
     ap.add_argument("--arcs", type=int, default=8000, help="per lattice")
     ap.add_argument("--contract", default="fma")
-    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--plan", choices=("host", "device", "both"), default="both")
     ap.add_argument("--timeout", type=int, default=120, help="seconds for each step of the driver")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "latpost_probe.jsonl"))
     a = ap.parse_args()
@@ -84,13 +93,13 @@ def main():
     lines = []
     for name in STEPS:
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--step", name, "--segments", str(a.segments), "--states",
-               str(a.states), "--arcs", str(a.arcs), "--contract", a.contract, "--reps", str(a.reps)]
+               str(a.states), "--arcs", str(a.arcs), "--contract", a.contract, "--reps", str(a.reps), "--plan", a.plan]
         r = subprocess.run(cmd, capture_output=True, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:   # nothing more is started after a step that failed, faulted or ran into its limit
             sys.stderr.write(r.stderr)
             sys.exit("latpost_probe: step %s ended with status %d; stopping" % (name, r.returncode))
-        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        lines += [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     with open(a.out, "a") as f:
         f.write("\n".join(json.dumps(l) for l in lines) + "\n")
     print("appended to %s" % a.out)
